@@ -8,7 +8,16 @@ each, V = 256 packet slots -> 102,400 slots), resident in HBM, reduced into one
 aggregate -- the work the Tofino's Processor registers do per slot
 (processor.p4:14-24).  value = W * n * 4 bytes * steps * ranks / max-rank time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it makes the inputs, warms up, times the K
+steps and prints the line (metric, value, unit, ms_per_step, the event-timed roofline of
+those same steps).  --dump-outputs DIR then writes what the last timed step computed (the
+aggregate a caller of ops.sum_reduce receives) to DIR/aggregate.npy as float64 -- the whole
+bucket when it is small, else a fixed, seeded sample of it; the inputs are seeded, so two
+builds can be compared output for output.  Everything below -- the parity spot checks, the
+other BASELINE configs, config 5, the switch and packet-path legs, the CPU baseline and the
+`legs` summary -- is measured only with --full.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts N ranks
 itself (torch.distributed.run, 127.0.0.1, one rank per GPU) before anything
@@ -89,6 +98,13 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workers", type=int, default=W_WORKERS)
     ap.add_argument("--values", type=int, default=N_VALUES)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the parity spot checks, configs 2, "
+                         "4 and 5, the PCIe-inclusive rate, the switch and packet-path legs and the "
+                         "CPU baseline (the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to "
+                         "DIR/<name>.npy (float64; a fixed, seeded sample of a large output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=N_VALUES,
                     help="values per worker in the CPU-baseline sample (default: the whole "
@@ -198,6 +214,34 @@ def make_inputs(W, n, seed_base, dev):
         bufs.append(torch.randint(-(1 << 20), 1 << 20, (n,), dtype=torch.int32, device=dev,
                                   generator=g))
     return bufs
+
+
+DUMP_BYTES = 32 << 20        # --dump-outputs: float64 bytes written per run, over all ranks
+
+
+def dump_output(dirname, name, out, rank=0, world=1):
+    """--dump-outputs: write the 1-D device tensor `out` (what the timed path's last step
+    returned) to DIR/<name>.npy as float64 (int32 and fp32 values are exact in it).  An output
+    of more than DUMP_BYTES / world is written as a sample: its first and last 4 Ki values and
+    positions drawn with a fixed seed, in ascending order -- the same positions in every run
+    with the same arguments.  At N > 1 every rank writes <name>_rank<r>.npy.  Returns the
+    entry the JSON line carries under "dump_outputs"."""
+    n = out.numel()
+    keep = max(1, DUMP_BYTES // 8 // world)
+    if n <= keep:
+        idx, vals = None, out
+    else:
+        edge = min(4096, keep // 4)
+        draw = np.random.default_rng(20240229).integers(0, n, keep - 2 * edge, dtype=np.int64)
+        idx = np.unique(np.concatenate([np.arange(edge), draw, np.arange(n - edge, n)]))
+        vals = out[torch.from_numpy(idx).to(out.device)]
+    arr = vals.cpu().numpy().astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    fname = f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"
+    np.save(os.path.join(dirname, fname), arr)
+    return {"file": fname, "dtype": "float64", "values": int(arr.size), "of": int(n),
+            "sample": None if idx is None else "the first and last 4 Ki positions and positions drawn by "
+                                               "numpy default_rng(20240229), ascending"}
 
 
 HEADLINE_KERNEL = "ina::k_sum_reduce_i32_vec<8,4,true>"
@@ -337,14 +381,15 @@ def _phase_times(phases, stream, world, passes=6):
     return out
 
 
-def measure_c5(args, rank, world, dev, warmup=2, collective="rs_ag", chunks=1):
+def measure_c5(args, rank, world, dev, warmup=2, collective="rs_ag", chunks=1, dump=None):
     """quantise -> reduce_scatter(int32, SUM) -> decode -> all_gather of one n-value fp32
     bucket per rank (the i32 wire gathers fp32; the i16 wire gathers the saturated int16
     sums + slot flags and dequantises after); per-phase HIP-event times on the launch
     stream.  collective="allreduce": one all-reduce of the integer wire, every rank
     decodes the whole bucket (phase "reduce_scatter" is then the all-reduce).
     chunks > 1: the pipelined step (ShardedAggregator(chunks=C)); its phases overlap, so
-    only the step time is reported."""
+    only the step time is reported.  dump: the --dump-outputs directory (the last timed
+    step's aggregate goes there as "aggregate_c5")."""
     from ina_amd import ops
     from ina_amd.dist import ShardedAggregator, all_gather_shards
     n = args.c5_values
@@ -361,9 +406,11 @@ def measure_c5(args, rank, world, dev, warmup=2, collective="rs_ag", chunks=1):
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(steps):
-        agg(bucket)
+        last_out = agg(bucket)
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
+    dumped = dump_output(dump, "aggregate_c5", last_out[:n], rank, world) if dump else None
+    del last_out
 
     # per-phase breakdown: events between the aggregator's own phases
     phase = None
@@ -475,6 +522,7 @@ def measure_c5(args, rank, world, dev, warmup=2, collective="rs_ag", chunks=1):
         "roofline": roofline,
         "parity_spot_check": parity,
         "parity_sample": f"{m} values: the first 64 Ki and the head and tail of every rank's shard",
+        **({"dump_outputs": dumped} if dumped else {}),
     }
 
 
@@ -1147,11 +1195,12 @@ def run_check_launch(args, rank, world, backend):
 
 
 def run_sharded_headline(args, rank, world, dev, backend):
-    c5 = measure_c5(args, rank, world, dev)
-    torch.cuda.empty_cache()
-    c5_b = measure_c5_layout_b(args, rank, world, dev)
-    c5_ar = c5_pl = c5_a2a = None
-    if world > 1:
+    c5 = measure_c5(args, rank, world, dev, dump=args.dump_outputs)
+    c5_b = c5_ar = c5_pl = c5_a2a = None
+    if args.full:                          # the other layouts and collectives beside the headline
+        torch.cuda.empty_cache()
+        c5_b = measure_c5_layout_b(args, rank, world, dev)
+    if args.full and world > 1:
         torch.cuda.empty_cache()
         c5_ar = measure_c5(args, rank, world, dev, collective="allreduce")
         torch.cuda.empty_cache()
@@ -1169,6 +1218,7 @@ def run_sharded_headline(args, rank, world, dev, backend):
         "rccl_world": world, "backend": backend,
         "phase_ms": c5["phase_ms"], "xgmi": c5["xgmi"],
         "parity_spot_check": c5["parity_spot_check"],
+        **({"dump_outputs": c5["dump_outputs"]} if "dump_outputs" in c5 else {}),
         "layout_b": c5_b,
         "allreduce": c5_ar,
         "pipelined": c5_pl,
@@ -1204,16 +1254,22 @@ def run_reduce(args, rank, world, dev, backend):
     avg_launch_s = max_over_ranks(my_avg_s, world)
     best_avg_s = reduce_over_ranks(my_avg_s, world, "min")
 
-    # spot check of the measured output against a numpy wrapping sum: every 997th value over
-    # the whole bucket plus its first and last 4 Ki values
     last = (args.steps - 1) % ROTATE
-    idx = _sample_idx(n)
-    ti = torch.from_numpy(idx).to(dev)
-    want = np.zeros(idx.size, np.uint32)
-    for b in sets[last]:
-        want += b[ti].cpu().numpy().view(np.uint32)
-    parity = all_ranks_true(
-        bool(np.array_equal(outs[last][ti].cpu().numpy().view(np.uint32), want)), world)
+    dumped = None
+    if args.dump_outputs:                   # the last timed step's aggregate
+        dumped = dump_output(args.dump_outputs, "aggregate", outs[last], rank, world)
+
+    parity = idx = None
+    if args.full:
+        # spot check of the measured output against a numpy wrapping sum: every 997th value
+        # over the whole bucket plus its first and last 4 Ki values
+        idx = _sample_idx(n)
+        ti = torch.from_numpy(idx).to(dev)
+        want = np.zeros(idx.size, np.uint32)
+        for b in sets[last]:
+            want += b[ti].cpu().numpy().view(np.uint32)
+        parity = all_ranks_true(
+            bool(np.array_equal(outs[last][ti].cpu().numpy().view(np.uint32), want)), world)
 
     worker_bytes = W * n * 4
     algo_bytes = (W + 1) * n * 4
@@ -1253,10 +1309,14 @@ def run_reduce(args, rank, world, dev, backend):
                      "avg_launch_us": round(avg_launch_s * 1e6, 2),
                      "per_rank_frac_min": round(algo_bytes / avg_launch_s / 1e9 / HBM_PEAK_GBS, 4),
                      "per_rank_frac_max": round(algo_bytes / best_avg_s / 1e9 / HBM_PEAK_GBS, 4)},
-        "parity_spot_check": parity,
-        "parity_sample": (f"{idx.size} values (every 997th over the whole bucket, the first and last "
-                          f"4 Ki) vs numpy wrapping int32 sum"),
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
+    if not args.full:                       # a plain run: the headline and nothing beside it
+        return line
+    line["parity_spot_check"] = parity
+    line["parity_sample"] = (f"{idx.size} values (every 997th over the whole bucket, the first and last "
+                             f"4 Ki) vs numpy wrapping int32 sum")
     cpu_in = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         # timed last: a CPU phase of seconds leaves the GPU idle and its clocks low, and
@@ -1380,7 +1440,8 @@ def main():
             os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
             json.dump(extra, open(os.path.join(REPO, "gpurun_out", "bench_extra.json"), "w"), indent=1)
         if rank == 0:
-            line["legs"] = legs_summary(line)      # the last key
+            if args.full:
+                line["legs"] = legs_summary(line)  # the last key
             print(json.dumps(line), flush=True)
     finally:
         if world > 1:

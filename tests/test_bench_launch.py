@@ -91,3 +91,35 @@ def test_leg_tuning_is_restored_when_a_leg_raises(monkeypatch):
         with bench._tuning(switch_runs=False):
             raise RuntimeError("leg failed")
     assert seen == [{"switch_runs": False}, {"switch_runs": True}]
+
+
+def test_plain_run_options_default_off():
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_output_whole_or_a_fixed_sample(tmp_path):
+    """--dump-outputs writes float64: a small output whole, a large one as the same ascending
+    sample (both ends included) every time, within the byte budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    small = torch.arange(-5, 1000, dtype=torch.int32)
+    e = bench.dump_output(str(tmp_path), "small", small)
+    got = np.load(tmp_path / e["file"])
+    assert e["sample"] is None and got.dtype == np.float64 and np.array_equal(got, small.numpy())
+    n = bench.DUMP_BYTES // 8 + 12_345
+    big = (torch.arange(n, dtype=torch.int64) * 7919 % 1_000_003 - 500_000).to(torch.int32)
+    e1 = bench.dump_output(str(tmp_path / "x"), "big", big)
+    e2 = bench.dump_output(str(tmp_path / "y"), "big", big)
+    g1, g2 = np.load(tmp_path / "x" / "big.npy"), np.load(tmp_path / "y" / "big.npy")
+    assert e1 == e2 and e1["of"] == n and e1["values"] == g1.size and np.array_equal(g1, g2)
+    assert n // 2 < g1.size and g1.nbytes <= bench.DUMP_BYTES and g1.dtype == np.float64
+    assert np.array_equal(g1[:4096], big[:4096].numpy()) and np.array_equal(g1[-4096:], big[-4096:].numpy())
+    e3 = bench.dump_output(str(tmp_path), "big", big, rank=1, world=2)       # half the budget per rank
+    assert e3["file"] == "big_rank1.npy" and np.load(tmp_path / "big_rank1.npy").nbytes <= bench.DUMP_BYTES // 2

@@ -1,5 +1,6 @@
-"""bench.py's output contract (one JSON line with the driver's keys, roofline,
-cpu_baseline, sharded_c5 and switch_c3 objects) on short runs; the bench runs as a child process.
+"""bench.py's output contract on short runs; the bench runs as a child process.  A plain run
+prints the headline alone (and --dump-outputs writes the last timed step's aggregate); --full
+adds the roofline's companions: cpu_baseline, sharded_c5, the switch_c3 objects and the rest.
 The two-rank rehearsal puts both ranks on the one GPU of the test box with a gloo group
 (bench.py --gpus 2 launching its own ranks, INA_BENCH_BACKEND=gloo): the launcher, the
 group-size assertion, the per-rank slot ranges and the config-5 path through
@@ -31,7 +32,7 @@ def _run(*args, env=None, timeout=300):
 
 @pytest.mark.gpu
 def test_bench_json_line_contract():
-    d = _line(_run("--steps", "3", "--warmup", "1", "--cpu-sample", str(1 << 16),
+    d = _line(_run("--full", "--steps", "3", "--warmup", "1", "--cpu-sample", str(1 << 16),
                    "--c5-values", str(1 << 22), "--c5-steps", "2"))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline",
@@ -114,7 +115,7 @@ def test_bench_json_line_contract():
 def test_bench_sharded_mode_line():
     """Config-5 mode on one GPU (the collectives are identities), both wires."""
     for wire in ("i32", "i16"):
-        d = _line(_run("--mode", "sharded", "--c5-steps", "2", "--c5-values", str(1 << 22),
+        d = _line(_run("--full", "--mode", "sharded", "--c5-steps", "2", "--c5-values", str(1 << 22),
                        "--wire", wire))
         assert d["n_gpus"] == 1 and d["value"] > 0 and d["parity_spot_check"] is True, wire
         assert d["config"]["values_per_worker"] == 1 << 22
@@ -124,7 +125,7 @@ def test_bench_sharded_mode_line():
 @pytest.mark.gpu
 def test_bench_two_rank_rehearsal_on_one_gpu():
     """bench.py --gpus 2 starts two ranks itself; both on cuda:0 with gloo."""
-    d = _line(_run("--gpus", "2", "--steps", "3", "--warmup", "1", "--values", str(1 << 22),
+    d = _line(_run("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--values", str(1 << 22),
                    "--c5-values", str(1 << 22), "--c5-steps", "2",
                    env={"INA_BENCH_BACKEND": "gloo"}, timeout=400))
     assert d["n_gpus"] == 2 and d["rccl_world"] == 2 and d["backend"] == "gloo"
@@ -159,7 +160,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     assert sw["ranks"] == 2 and sw["worker_major"]["ok"] is True and sw["round_robin"]["ok"] is True
     assert d["packet_path"]["parity_spot_check"] is True
     assert sw["worker_major"]["aggregate_GBps"] > 0
-    d = _line(_run("--gpus", "2", "--mode", "sharded", "--wire", "i16", "--c5-values", "1000003",
+    d = _line(_run("--full", "--gpus", "2", "--mode", "sharded", "--wire", "i16", "--c5-values", "1000003",
                    "--c5-steps", "2", env={"INA_BENCH_BACKEND": "gloo"}, timeout=400))
     assert d["n_gpus"] == 2 and d["parity_spot_check"] is True
     assert d["layout_b"]["parity_spot_check"] is True
@@ -168,3 +169,38 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     assert d["xgmi"]["rs_send_bytes_per_rank"] == 4 * shard
     assert d["allreduce"]["parity_spot_check"] is True and d["pipelined"]["parity_spot_check"] is True
     assert d["a2a"]["parity_spot_check"] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_output(tmp_path):
+    """Without --full the line is the headline (no leg, no spot check, no `legs`), --steps sets
+    the timed steps, and --dump-outputs writes the last timed step's aggregate: the same file
+    from two runs, equal to the wrapping sum of the seeded inputs of that step."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    n, steps = 1_000_003, 3
+    lines = []
+    for run in ("a", "b"):
+        lines.append(_line(_run("--gpus", "1", "--steps", str(steps), "--warmup", "1", "--values", str(n),
+                                "--dump-outputs", str(tmp_path / run))))
+    d = lines[0]
+    assert d["metric"] == bench.METRIC and d["unit"] == "GB/s" and d["dtype"] == "int32"
+    assert d["higher_is_better"] is True and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["steps"] == steps and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert abs(d["value"] - 8 * n * 4 / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"]
+    for key in ("legs", "cpu_baseline", "c2_fused", "c4_int16", "e2e_pcie", "sharded_c5", "switch_c3",
+                "switch_c3_v32", "packet_path", "packet_path_packed", "packet_path_v32", "parity_spot_check"):
+        assert key not in d, key
+    assert d["dump_outputs"] == {"file": "aggregate.npy", "dtype": "float64", "values": n, "of": n,
+                                 "sample": None}
+    a, b = np.load(tmp_path / "a" / "aggregate.npy"), np.load(tmp_path / "b" / "aggregate.npy")
+    assert a.dtype == np.float64 and a.shape == (n,) and np.array_equal(a, b)
+    ins = bench.make_inputs(8, n, 1000 + 100 * ((steps - 1) % bench.ROTATE), "cuda:0")
+    want = np.zeros(n, np.uint32)
+    for t in ins:
+        want += t.cpu().numpy().view(np.uint32)
+    assert np.array_equal(a, want.view(np.int32).astype(np.float64))
+    del ins
+    torch.cuda.empty_cache()

@@ -52,18 +52,18 @@ for st in $STAGES; do
       timeout -k 10 900 python -u -m pytest tests/test_gpu_bench_contract.py -m gpu -v -rf --timeout 600 --timeout-method thread > "$OUT/contract.log" 2>&1
       rc=$?; tail -8 "$OUT/contract.log"; ok_or_fail contract $rc ;;
     bench)
-      # the driver's own command (BENCH_rNN.json), so the session's line and the driver's are the
-      # same measurement
-      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+      # the driver's own command (BENCH_rNN.json) with --full: the headline is the same
+      # measurement, and every leg rides in the line
+      timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
       rc=$?; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"; [ $rc -ne 0 ] && fatal bench $rc ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-        python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+        python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
       rc=$?; tail -2 "$OUT/prof.err"; [ $rc -ne 0 ] && fatal prof $rc ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
         timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_$c" -o run -- \
-          python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/pmc_$c.json" 2> "$OUT/pmc_$c.err"
+          python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/pmc_$c.json" 2> "$OUT/pmc_$c.err"
         rc=$?; tail -2 "$OUT/pmc_$c.err"; [ $rc -ne 0 ] && fatal "pmc $c" $rc
       done ;;
     swtrace:*)
@@ -109,24 +109,24 @@ for st in $STAGES; do
       rc=$?; tail -8 "$OUT/config1.log"; [ $rc -ne 0 ] && fatal config1 $rc ;;
     rehearse)
       # bench.py starts its own two ranks (no launcher); both on the box's one GPU over gloo
-      INA_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 20 --warmup 5 \
+      INA_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 20 --warmup 5 \
         --c5-values 67108864 > "$OUT/rehearse2.json" 2> "$OUT/rehearse2.err"
       rc=$?; cat "$OUT/rehearse2.json"; tail -3 "$OUT/rehearse2.err"; [ $rc -ne 0 ] && fatal rehearse $rc ;;
     rehearse8)
       # bench.py --gpus 8 the way the driver's scale run starts it, 8 ranks on one GPU over gloo
-      INA_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 8 --steps 10 --warmup 3 \
+      INA_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --full --gpus 8 --steps 10 --warmup 3 \
         --c5-values 16777216 --c5-steps 3 > "$OUT/rehearse8.json" 2> "$OUT/rehearse8.err"
       rc=$?; tail -c 600 "$OUT/rehearse8.json"; tail -3 "$OUT/rehearse8.err"; [ $rc -ne 0 ] && fatal rehearse8 $rc ;;
     sharded)
       for wire in i32 i16; do
-        timeout -k 10 400 python bench.py --mode sharded --wire $wire > "$OUT/sharded1_$wire.json" 2> "$OUT/sharded1_$wire.err"
+        timeout -k 10 400 python bench.py --full --mode sharded --wire $wire > "$OUT/sharded1_$wire.json" 2> "$OUT/sharded1_$wire.err"
         rc=$?; cat "$OUT/sharded1_$wire.json"; tail -3 "$OUT/sharded1_$wire.err"; [ $rc -ne 0 ] && fatal sharded $rc
       done ;;
     swlab)
       timeout -k 10 400 python tools/lab/switch_sort_lab.py > "$OUT/switch_sort_lab.json" 2> "$OUT/switch_sort_lab.err"
       rc=$?; cat "$OUT/switch_sort_lab.json"; [ $rc -ne 0 ] && fatal swlab $rc ;;
     extra)
-      timeout -k 10 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --extra > "$OUT/extra_bench.json" 2> "$OUT/extra.err"
+      timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --extra > "$OUT/extra_bench.json" 2> "$OUT/extra.err"
       rc=$?; tail -3 "$OUT/extra.err"; [ $rc -ne 0 ] && fatal extra $rc
       cp gpurun_out/bench_extra.json "$OUT/" ;;
   esac

@@ -1,19 +1,21 @@
 # A/B of the product library built with nt (INA_STORE_SC1=0) and sc1 (default) streaming
 # stores: bench.py legs, alternating builds twice (the product path's libina.so is swapped)
 set -u
-mkdir -p gpurun_out/store_ab
+D=${LAB_OUT:-lab_out}/store_ab     # results (LAB_OUT: where the labs write)
+export D
+mkdir -p $D
 L=distributed-training-ina_amd/ina_amd/libina.so
-cp $L gpurun_out/store_ab/libina_keep.so
+cp $L $D/libina_keep.so
 for rep in 1 2; do
   for v in nt sc1; do
     cp tools/lab/libina_$v.so $L
-    timeout -k 10 200 python bench.py --no-cpu-baseline --steps 50 --warmup 10 > gpurun_out/store_ab/bench_${v}_$rep.json 2> gpurun_out/store_ab/bench_${v}_$rep.err || { cp gpurun_out/store_ab/libina_keep.so $L; exit 1; }
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 50 --warmup 10 > $D/bench_${v}_$rep.json 2> $D/bench_${v}_$rep.err || { cp $D/libina_keep.so $L; exit 1; }
   done
 done
-cp gpurun_out/store_ab/libina_keep.so $L
+cp $D/libina_keep.so $L
 python - <<'PY'
-import json, glob
-for f in sorted(glob.glob("gpurun_out/store_ab/bench_*.json")):
+import json, glob, os
+for f in sorted(glob.glob(os.environ["D"] + "/bench_*.json")):
     d = json.loads([l for l in open(f) if l.startswith("{")][-1])
     c5 = d["sharded_c5"]["roofline"]["hbm_phases"]
     print(f.split("/")[-1], "C3", d["roofline"]["avg_launch_us"], "C2", d["c2_fused"]["roofline"]["avg_launch_us"],

@@ -53,6 +53,71 @@ def _row(name, secs, nbytes, **kw):
     return r
 
 
+def run_x16(dev, dtype=torch.bfloat16):
+    """bf16 gradient buckets (include/ina.h "bf16 / fp16 gradients") at the config-2 and config-4
+    shapes.  Each 16-bit call is timed in the same run beside (a) its fp32 sibling on an fp32
+    bucket of the same length, twice -- the two times' difference is the run-to-run spread --
+    and (b) what a user without the 16-bit entry points does: widen (into a preallocated fp32
+    buffer, no allocation in the timed region) then call the sibling.  bytes = algorithmic HBM
+    bytes of the 16-bit call; the siblings' rows carry their own."""
+    from ina_amd import ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(16)
+    n, k = 25_557_032, 16
+    name16 = {torch.bfloat16: "bf16", torch.float16: "fp16"}[dtype]
+
+    def trio(name, nb16, nb32, f16, f32, widen):
+        """rows for one op: sibling, 16-bit, widen + sibling, sibling again"""
+        t32a = _time(f32)
+        t16 = _time(f16)
+        tw = _time(lambda: (widen(), f32()))
+        t32b = _time(f32)
+        lo, hi = min(t32a, t32b), max(t32a, t32b)
+        rows.append(_row(f"{name} [{name16}]", t16, nb16, sibling_us=[round(t32a * 1e6, 2), round(t32b * 1e6, 2)],
+                         sibling_frac=round(nb32 / lo / 1e9 / HBM, 4),
+                         sibling_spread_us=round((hi - lo) * 1e6, 2), widen_then_sibling_us=round(tw * 1e6, 2),
+                         faster_than_widen_then_sibling=bool(t16 < tw),
+                         no_slower_than_sibling=bool(t16 <= hi + (hi - lo))))
+
+    # config 2: W = 4 to int32; config 4: W = 16 to int16 (V = 256)
+    W2, W4, V = 4, 16, 256
+    b32 = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(W4)]
+    b16 = [b.to(dtype) for b in b32]
+    wid = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(W4)]
+    q = torch.empty(n, dtype=torch.int32, device=dev)
+    trio("quantize_x16_i32", 6 * n, 8 * n, lambda: ops.quantize(b16[0], k, out=q),
+         lambda: ops.quantize(b32[0], k, out=q), lambda: wid[0].copy_(b16[0]))
+    trio(f"quantize_reduce_x16_i32 W={W2} (C2)", (2 * W2 + 4) * n, (4 * W2 + 4) * n,
+         lambda: ops.quantize_reduce(b16[:W2], k, out=q), lambda: ops.quantize_reduce(b32[:W2], k, out=q),
+         lambda: [w.copy_(x) for w, x in zip(wid[:W2], b16[:W2])])
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    f = torch.empty((n + V - 1) // V, dtype=torch.uint8, device=dev)
+    trio(f"quantize_reduce_x16_i16_sat W={W4} V={V} (C4)", (2 * W4 + 2) * n + f.numel(), (4 * W4 + 2) * n + f.numel(),
+         lambda: ops.quantize_reduce_i16(b16, 13, V, out=o16, overflow=f),
+         lambda: ops.quantize_reduce_i16(b32, 13, V, out=o16, overflow=f),
+         lambda: [w.copy_(x) for w, x in zip(wid, b16)])
+    # dequantise: the 16-bit call against the fp32 call, and against the fp32 call + a narrowing copy
+    ops.quantize_reduce(b32[:W2], k, out=q)
+    y32 = torch.empty(n, dtype=torch.float32, device=dev)
+    y16 = torch.empty(n, dtype=dtype, device=dev)
+    trio("dequantize_i32_x16", 6 * n, 8 * n, lambda: ops.dequantize(q, k, out=y16),
+         lambda: ops.dequantize(q, k, out=y32), lambda: y16.copy_(y32))
+    # the 8 workers' split packs in one launch, against an fp32 base
+    Wp = 8
+    base = torch.randn(n, device=dev, generator=gen) * 1e-2
+    npk = (n + V - 1) // V
+    hdrs = [torch.zeros((npk, 16), dtype=torch.uint8, device=dev) for _ in range(Wp)]
+    pays = [torch.empty((npk, 4 * V), dtype=torch.uint8, device=dev) for _ in range(Wp)]
+    args = (k, V, list(range(1, Wp + 1)), Wp, 1, 1)
+    out_b = Wp * (npk * 16 + npk * 4 * V)
+    trio(f"quantize_pack_nga_multi_split_x16 W={Wp} V={V}", (2 * Wp + 4) * n + out_b, (4 * Wp + 4) * n + out_b,
+         lambda: ops.quantize_pack_nga_multi_split(b16[:Wp], *args, base=base, hdrs=hdrs, pays=pays),
+         lambda: ops.quantize_pack_nga_multi_split(b32[:Wp], *args, base=base, hdrs=hdrs, pays=pays),
+         lambda: [w.copy_(x) for w, x in zip(wid[:Wp], b16[:Wp])])
+    return rows
+
+
 DEFAULTS = {"max_blocks": 16384, "reduce_blocks": 0, "stream_blocks": 16384, "combine_blocks": 256,
             "combine_ina_blocks": 8192, "ew_blocks": 1 << 24}
 
@@ -426,4 +491,6 @@ def run_extra(dev):
             del scratch
     ops.set_tuning(host_zero_copy=True)
     ops.set_tuning(h2d_streams=2)
+    del hosts, hout, dbuf, b3, o3
+    rows += run_x16(dev)
     return {"rows": rows, "sweep": sweep, "grid_sweeps": gsweep}

@@ -96,4 +96,107 @@ __device__ __forceinline__ void packet_store(T v, T* p) {
 #endif
 }
 
+
+// ---------------------------------------------------------------------------
+// quantiser (build-defined, see include/ina.h): sat(rne(x * 2^k)), NaN -> 0
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int32_t q32(float x, float s) {
+    float y = __builtin_rintf(x * s);
+    int32_t r = (int32_t)y;                         // in-range lanes only are selected
+    r = (y >= 2147483648.0f) ? INT32_MAX : r;
+    r = (y < -2147483648.0f) ? INT32_MIN : r;
+    return (y != y) ? 0 : r;
+}
+
+// returns the int16 value widened to int32; *sat |= clamped-or-NaN
+#ifndef INA_Q16_MED3
+#define INA_Q16_MED3 1
+#endif
+__device__ __forceinline__ int32_t q16(float x, float s, bool& sat) {
+    float y = __builtin_rintf(x * s);
+#if INA_Q16_MED3
+    // one v_med3_f32 clamps; a clamped value, +-inf or NaN differs from y
+    const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);
+    sat |= !(c == y);
+    return (y != y) ? 0 : (int32_t)c;
+#else
+    bool in = (y <= 32767.0f) && (y >= -32768.0f);  // false for NaN
+    sat |= !in;
+    int32_t r = in ? (int32_t)y : 0;
+    r = (y > 32767.0f) ? 32767 : r;
+    r = (y < -32768.0f) ? -32768 : r;
+    return r;
+#endif
+}
+
+__device__ __forceinline__ int32_t sat16(int32_t a, bool& sat) {
+    bool hi = a > 32767, lo = a < -32768;
+    sat |= hi | lo;
+    return hi ? 32767 : (lo ? -32768 : a);
+}
+
+// ---------------------------------------------------------------------------
+// per-slot overflow flags: thread t owns 8 consecutive values; a slot of V values
+// (V % 8 == 0, V/8 a power of two <= 64) is V/8 adjacent lanes of one wave.  The
+// group's first lane writes the slot flag from a wave ballot -- one writer per slot,
+// no atomics, no pre-zeroing.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void write_slot_flags8(unsigned long long m, bool active, size_t elem0,
+                                                  int V, int lanes_per_slot,
+                                                  uint8_t* __restrict__ ovf) {
+    int lane = threadIdx.x & 63;
+    int g0 = lane & ~(lanes_per_slot - 1);
+    unsigned long long gm = (lanes_per_slot == 64) ? ~0ull : (((1ull << lanes_per_slot) - 1ull) << g0);
+    if (active && (lane & (lanes_per_slot - 1)) == 0) ovf[elem0 / (size_t)V] = (m & gm) ? 1 : 0;
+}
+
+static inline bool slot_ballot_ok(int V) {
+    if (V % 8) return false;
+    int l = V / 8;
+    return l >= 1 && l <= 64 && (l & (l - 1)) == 0;
+}
+
+
+
+// ---------------------------------------------------------------------------
+// 16-bit float sources and targets (include/ina.h, INA_X16_BF16 / INA_X16_F16).  Widening is
+// exact: bf16 is the top half of an fp32 word; fp16 goes through v_cvt_f32_f16, which keeps
+// subnormals (the fp16 denormal mode is on by default).  Two values travel in one dword, the
+// lower-addressed one in the low half.
+// ---------------------------------------------------------------------------
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+template <int XT>
+__device__ __forceinline__ float widen16(uint16_t h) {
+    static_assert(XT == 1 || XT == 2, "INA_X16_BF16 or INA_X16_F16");
+    if constexpr (XT == 1) return __uint_as_float((uint32_t)h << 16);
+    else return (float)__builtin_bit_cast(_Float16, h);
+}
+template <int XT>
+__device__ __forceinline__ f32x4_t widen16x4(u32x2_t v) {
+    if constexpr (XT == 1)
+        return f32x4_t{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u),
+                       __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xFFFF0000u)};
+    else
+        return f32x4_t{widen16<XT>((uint16_t)(v.x & 0xFFFFu)), widen16<XT>((uint16_t)(v.x >> 16)),
+                       widen16<XT>((uint16_t)(v.y & 0xFFFFu)), widen16<XT>((uint16_t)(v.y >> 16))};
+}
+// fp32 -> 16-bit, one rounding to nearest even.  fp16: v_cvt_f16_f32 (overflow to +-inf,
+// subnormal results produced), never the packed round-toward-zero convert.
+template <int XT>
+__device__ __forceinline__ uint32_t rne16(float f) {
+    static_assert(XT == 1 || XT == 2, "INA_X16_BF16 or INA_X16_F16");
+    if constexpr (XT == 1) {
+        const uint32_t u = __float_as_uint(f);
+        const uint32_t r = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+        return (f != f) ? ((u >> 16) | 0x0040u) : r;
+    } else {
+        return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    }
+}
+template <int XT>
+__device__ __forceinline__ uint32_t rne16x2(float lo, float hi) {
+    return rne16<XT>(lo) | (rne16<XT>(hi) << 16);
+}
+
 }  // namespace ina

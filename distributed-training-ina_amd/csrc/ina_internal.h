@@ -30,11 +30,15 @@ int set_pre_all(int v);       // ina_switch.hip
 int set_local(int v);         // ina_switch.hip
 int set_decide_delay(int v);  // ina_switch.hip
 int ew_grid_cap();            // ina_kernels.hip: grid cap of the elementwise kernels (tuning key 14)
+int default_grid_cap();       // ina_kernels.hip: grid cap of the default-cap kernels (tuning key 0)
+int stream_grid_cap();        // ina_kernels.hip: grid cap of the flat packet kernels (tuning key 4)
+int check_x16_type(int xtype);   // ina_x16.hip: INA_OK for INA_X16_BF16 / INA_X16_F16, else INA_EINVAL
 // checked builds (INA_STORE_CHECK, ina_device.h): each source's stream_store contract
 // violations since the last read, cleared by the read
 unsigned long long store_violations_kernels();   // ina_kernels.hip
 unsigned long long store_violations_shard();     // ina_shard.hip
 unsigned long long store_violations_switch();    // ina_switch.hip
+unsigned long long store_violations_x16();       // ina_x16.hip
 
 }  // namespace ina
 

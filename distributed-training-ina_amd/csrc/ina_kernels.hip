@@ -93,6 +93,8 @@ static std::atomic<int> g_stream_blocks{16384};
 // within +-1 us of it (tools/lab/ew_grid_lab.py, profiles/r02/lab/ew_grid_lab.json)
 static std::atomic<int> g_ew_blocks{1 << 24};
 int ew_grid_cap() { return g_ew_blocks.load(); }
+int default_grid_cap() { return g_max_blocks.load(); }
+int stream_grid_cap() { return g_stream_blocks.load(); }
 // PS combine kernels (W+2 streams), measured per kernel (bench_extra grid sweeps and
 // ew_lab): the fp32 combine runs best at 256 workgroups (6.6-6.7 TB/s vs 6.0 at 512),
 // the INA combine (quantiser in the loop) with one chunk in flight at 8192
@@ -133,65 +135,14 @@ __device__ __forceinline__ void st(T* p, T v) {
 
 __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
-// ---------------------------------------------------------------------------
-// quantiser (build-defined, see include/ina.h): sat(rne(x * 2^k)), NaN -> 0
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int32_t q32(float x, float s) {
-    float y = __builtin_rintf(x * s);
-    int32_t r = (int32_t)y;                         // in-range lanes only are selected
-    r = (y >= 2147483648.0f) ? INT32_MAX : r;
-    r = (y < -2147483648.0f) ? INT32_MIN : r;
-    return (y != y) ? 0 : r;
-}
-
-// returns the int16 value widened to int32; *sat |= clamped-or-NaN
-#ifndef INA_Q16_MED3
-#define INA_Q16_MED3 1
-#endif
+// the quantiser (q32, q16, sat16) and the per-slot ballot flags (write_slot_flags8,
+// slot_ballot_ok) live in ina_device.h: ina_x16.hip runs the same ones on widened values
 // int16 kernels: a wave covers 512 values as two 256-value halves (16 B per lane per
 // load, contiguous per instruction) -- C4 fused quantise+reduce 289 -> 251 us against
 // 8 consecutive values per lane (32-B lane stride; tools/lab/ew_lab.py, lab/q16_lab.log)
 #ifndef INA_Q16_SPLIT
 #define INA_Q16_SPLIT 1
 #endif
-__device__ __forceinline__ int32_t q16(float x, float s, bool& sat) {
-    float y = __builtin_rintf(x * s);
-#if INA_Q16_MED3
-    // one v_med3_f32 clamps; a clamped value, +-inf or NaN differs from y
-    const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);
-    sat |= !(c == y);
-    return (y != y) ? 0 : (int32_t)c;
-#else
-    bool in = (y <= 32767.0f) && (y >= -32768.0f);  // false for NaN
-    sat |= !in;
-    int32_t r = in ? (int32_t)y : 0;
-    r = (y > 32767.0f) ? 32767 : r;
-    r = (y < -32768.0f) ? -32768 : r;
-    return r;
-#endif
-}
-
-__device__ __forceinline__ int32_t sat16(int32_t a, bool& sat) {
-    bool hi = a > 32767, lo = a < -32768;
-    sat |= hi | lo;
-    return hi ? 32767 : (lo ? -32768 : a);
-}
-
-// ---------------------------------------------------------------------------
-// per-slot overflow flags: thread t owns 8 consecutive values; a slot of V values
-// (V % 8 == 0, V/8 a power of two <= 64) is V/8 adjacent lanes of one wave.  The
-// group's first lane writes the slot flag from a wave ballot -- one writer per slot,
-// no atomics, no pre-zeroing.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void write_slot_flags8(unsigned long long m, bool active, size_t elem0,
-                                                  int V, int lanes_per_slot,
-                                                  uint8_t* __restrict__ ovf) {
-    int lane = threadIdx.x & 63;
-    int g0 = lane & ~(lanes_per_slot - 1);
-    unsigned long long gm = (lanes_per_slot == 64) ? ~0ull : (((1ull << lanes_per_slot) - 1ull) << g0);
-    if (active && (lane & (lanes_per_slot - 1)) == 0) ovf[elem0 / (size_t)V] = (m & gm) ? 1 : 0;
-}
-
 // the same for the split layout (a wave owns 512 values, lane l holds 4 at 4l of each
 // 256-value half): a slot is V/4 adjacent lanes of one half, or both halves at V = 512
 __device__ __forceinline__ void write_slot_flags_split(unsigned long long ma, unsigned long long mb,
@@ -203,12 +154,6 @@ __device__ __forceinline__ void write_slot_flags_split(unsigned long long ma, un
         write_slot_flags8(ma, eA < n, eA, V, V / 4, ovf);
         write_slot_flags8(mb, eB < n, eB, V, V / 4, ovf);
     }
-}
-
-static inline bool slot_ballot_ok(int V) {
-    if (V % 8) return false;
-    int l = V / 8;
-    return l >= 1 && l <= 64 && (l & (l - 1)) == 0;
 }
 
 
@@ -897,6 +842,32 @@ struct SrcQ32 {
     }
 };
 
+// a bf16 / fp16 bucket (ina.h INA_X16_*) widened in registers: the words of SrcQ32 on
+// (float)x[e], from half the bytes (one 8-byte load per 4 values); base stays fp32
+template <int XT>
+struct SrcX16 {
+    const uint16_t* __restrict__ x;
+    const float* __restrict__ base;   // may be null
+    float s;
+    SrcX16 shifted(size_t off) const { return SrcX16{x + off, base ? base + off : nullptr, s}; }
+    __device__ __forceinline__ uint32_t one(size_t e) const {
+        const float a = widen16<XT>(x[e]);
+        return (uint32_t)q32(base ? __fsub_rn(a, base[e]) : a, s);
+    }
+    __device__ __forceinline__ u32x4 four(size_t e) const {
+        f32x4 a = widen16x4<XT>(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(x + e)));
+        if (base) {                                    // shared: default policy, as in SrcQ32
+            f32x4 b = *reinterpret_cast<const f32x4*>(base + e);
+            a.x = __fsub_rn(a.x, b.x); a.y = __fsub_rn(a.y, b.y);
+            a.z = __fsub_rn(a.z, b.z); a.w = __fsub_rn(a.w, b.w);
+        }
+        return u32x4{(uint32_t)q32(a.x, s), (uint32_t)q32(a.y, s), (uint32_t)q32(a.z, s),
+                     (uint32_t)q32(a.w, s)};
+    }
+};
+// sources that quantise on the fly (the fused worker packs) against stored int32 words
+template <typename Src> constexpr bool kQuantSrc = !std::is_same_v<Src, SrcI32>;
+
 template <typename Src>
 __device__ __forceinline__ uint32_t nga_val(const Src& src, size_t n, size_t p, int V, long j) {
     // payload word j of packet p (0 outside [0, V) and past n: zero tail pad)
@@ -1302,6 +1273,63 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackSplit a, 
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 const SrcQ32 src{a.x[g], base, s};
+                u32x4 v;
+                v.x = e0 < n ? src.one(e0) : 0u;
+                v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
+                v.z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
+                v.w = e0 + 3 < n ? src.one(e0 + 3) : 0u;
+                packet_store(bswap4(v), a.pay[g] + t);
+            }
+        }
+    }
+    for (size_t p = tid; p < np; p += gs) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const u32x4 r = nga_hdr_row(a.bitmap[g], a.fcs[g], a.seq0[g] + (uint32_t)p, num_slots);
+            packet_store(r, a.hdr[g] + p);
+            if (a.desc[g]) a.desc[g][p] = u32x2{r.y, r.z};
+        }
+    }
+}
+
+// the same from bf16 / fp16 buckets (ina.h INA_X16_*): 8-byte worker loads, the fp32 base
+// chunk still read once per group
+struct QPackSplitX16 {
+    const uint16_t* x[kQpGroup];
+    u32x4* hdr[kQpGroup];
+    u32x4* pay[kQpGroup];
+    u32x2* desc[kQpGroup];          // all null or all set
+    uint32_t bitmap[kQpGroup], seq0[kQpGroup], fcs[kQpGroup];
+};
+template <int XT, int G>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_x16(QPackSplitX16 a, const float* __restrict__ base,
+                                                                      size_t n, float s, uint32_t num_slots,
+                                                                      size_t nch, size_t np) {
+    const size_t gs = (size_t)gridDim.x * kBlock;
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    for (size_t t = tid; t < nch; t += gs) {
+        const size_t e0 = 4 * t;
+        if (e0 + 4 <= n) {
+            f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
+            u32x2 x[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) x[g] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.x[g] + e0));
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                f32x4 y = widen16x4<XT>(x[g]);
+                if (base) {
+                    y.x = __fsub_rn(y.x, b.x); y.y = __fsub_rn(y.y, b.y);
+                    y.z = __fsub_rn(y.z, b.z); y.w = __fsub_rn(y.w, b.w);
+                }
+                const u32x4 q{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s),
+                              (uint32_t)q32(y.w, s)};
+                packet_store(bswap4(q), a.pay[g] + t);
+            }
+        } else {                                       // the bucket's last chunk: zero tail
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const SrcX16<XT> src{a.x[g], base, s};
                 u32x4 v;
                 v.x = e0 < n ? src.one(e0) : 0u;
                 v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
@@ -1918,7 +1946,7 @@ static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina
             // the int32 pack stays on the flat stream (36.5 -> 39.1 us with a wave per
             // packet: one 16-byte load per lane leaves too little in flight),
             // profiles/r03/lab/pack_ppw_lab.log
-            if (INA_PACK_PPW && std::is_same_v<Src, SrcQ32> && V == 256 && C <= 65 + 64) {
+            if (INA_PACK_PPW && kQuantSrc<Src> && V == 256 && C <= 65 + 64) {
                 hipLaunchKernelGGL((k_pack_nga_v256<Src>), dim3(grid_for(np * 64, 1, 1 << 20)), dim3(kBlock), 0, s,
                                    src.shifted(v0), n - v0, hp, ovf ? ovf + p0 : nullptr, pkts + p0 * pstride,
                                    (uint32_t)pstride, (uint32_t)np,
@@ -2415,6 +2443,78 @@ int ina_quantize_pack_nga_multi_split(const float* const* x, int W, const float*
     return check_launch("quantize_pack_nga_multi_split");
 }
 
+// ---- packs from bf16 / fp16 buckets (ina.h "bf16 / fp16 gradients"; the other 16-bit entry
+// points are in ina_x16.hip) ------------------------------------------------------------------
+int ina_quantize_pack_nga_x16_desc(const void* x, int xtype, const float* base, size_t n, int k,
+                                   const ina_nga_params_t* prm, uint8_t* pkts, size_t pstride,
+                                   ina_nga_desc_t* desc, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (int rc = check_k(k)) return rc;
+    if (n && !x) return set_error(INA_EINVAL, "null pointer%s", "");
+    if ((uintptr_t)x & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
+    if (desc && ((uintptr_t)desc & 7u)) return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
+    const bool al = aligned16(x) && (!base || aligned16(base));
+    const uint16_t* h = static_cast<const uint16_t*>(x);
+    const float sc = ldexpf(1.0f, k);
+    if (xtype == INA_X16_BF16)
+        return pack_nga_launch(SrcX16<INA_X16_BF16>{h, base, sc}, al, n, prm, nullptr, pkts, pstride, hs(stream), desc);
+    return pack_nga_launch(SrcX16<INA_X16_F16>{h, base, sc}, al, n, prm, nullptr, pkts, pstride, hs(stream), desc);
+}
+
+int ina_quantize_pack_nga_multi_split_x16(const void* const* x, int xtype, int W, const float* base, size_t n,
+                                          int k, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                          uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (int rc = check_k(k)) return rc;
+    if (!x || !prm || !hdr || !pay || W < 1 || W > INA_MAX_WORKERS)
+        return set_error(INA_EINVAL, "x, prm, hdr, pay non-null and W in [1, %s]", "64");
+    const int V = prm[0].V;
+    if (int rc = split_geometry(V, prm[0].num_slots)) return rc;
+    const size_t npk = (n + (size_t)V - 1) / (size_t)V;
+    if (npk == 0) return INA_OK;
+    if (base && !aligned16(base)) return set_error(INA_EINVAL, "base must be 16-byte aligned%s", "");
+    for (int w = 0; w < W; ++w) {
+        if (prm[w].V != V || prm[w].num_slots != prm[0].num_slots)
+            return set_error(INA_EINVAL, "every worker needs the same V and num_slots%s", "");
+        if (!x[w] || !hdr[w] || !pay[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
+        if (!aligned16(x[w]) || !aligned16(hdr[w]) || !aligned16(pay[w]))
+            return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
+        if (desc && (!desc[w] || ((uintptr_t)desc[w] & 7u)))
+            return set_error(INA_EINVAL, "descriptors must be non-null and 8-byte aligned%s", "");
+    }
+    const float sc = ldexpf(1.0f, k);
+    const size_t nch = npk * (size_t)V / 4;
+    const dim3 grid(grid_for(std::max(nch, npk), 1, ew_grid_cap())), blk(kBlock);
+    hipStream_t s = hs(stream);
+    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
+        const int G = std::min(kQpGroup, W - w0);
+        QPackSplitX16 a{};
+        for (int g = 0; g < G; ++g) {
+            const ina_nga_params_t& q = prm[w0 + g];
+            a.x[g] = static_cast<const uint16_t*>(x[w0 + g]);
+            a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
+            a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
+            a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
+            a.bitmap[g] = q.bitmap;
+            a.seq0[g] = q.seq0;
+            a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
+        }
+        switch (G) {
+#define INA_QPS(g_) case g_:                                                                                  \
+            if (xtype == INA_X16_BF16)                                                                        \
+                hipLaunchKernelGGL((k_qpack_nga_multi_split_x16<INA_X16_BF16, g_>), grid, blk, 0, s, a, base, n, sc, \
+                                   prm[0].num_slots, nch, npk);                                               \
+            else                                                                                              \
+                hipLaunchKernelGGL((k_qpack_nga_multi_split_x16<INA_X16_F16, g_>), grid, blk, 0, s, a, base, n, sc,  \
+                                   prm[0].num_slots, nch, npk);                                               \
+            break;
+            INA_QPS(1) INA_QPS(2) INA_QPS(3) INA_QPS(4) INA_QPS(5) INA_QPS(6) INA_QPS(7) INA_QPS(8)
+#undef INA_QPS
+        }
+    }
+    return check_launch("quantize_pack_nga_multi_split_x16");
+}
+
 int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npk, int V,
                          const ina_nga_fields_t* fields, int32_t* vals, ina_stream_t stream) {
     if (V <= 0 || V % 4 || V > 256) return set_error(INA_EINVAL, "V must be a multiple of 4 in [4, 256]%s", "");
@@ -2607,7 +2707,8 @@ unsigned long long store_violations_kernels() {
 extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (!count) return INA_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
-    *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch();
+    *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
+             ina::store_violations_x16();
     return INA_OK;
 }
 #endif

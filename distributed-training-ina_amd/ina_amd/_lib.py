@@ -27,6 +27,7 @@ ACT_DROP, ACT_FWD_AGG, ACT_FWD_COLLISION, ACT_FWD_ACK, ACT_FWD_OTHER = range(5)
 ROUTE_MAX = 256                    # ipRoute size, ngaa.p4:59
 PORT_DROP, PORT_NONE = -1, -2
 I16_WIRE_SHIFT, I16_WIRE_MAX_RANKS = 22, 64      # include/ina.h
+X16_BF16, X16_F16 = 1, 2                         # include/ina.h: 16-bit source / target types
 
 
 class InaError(RuntimeError):
@@ -114,6 +115,18 @@ SIGNATURES = {
     "ina_send_packets_fd": [_i, _vp, _sz, _sz, _sz, _u32],
     "ina_recv_packets_fd": [_i, _vp, _sz, _sz, _sz, _i, _vp],
 }
+# the bf16 / fp16 entry points (include/ina_x16.h), bound like the ones above
+SIGNATURES_X16 = {
+    "ina_quantize_x16_i32": [_vp, _i, _vp, _sz, _i, _vp],
+    "ina_quantize_x16_i16_sat": [_vp, _i, _vp, _sz, _i, _i, _vp, _vp],
+    "ina_quantize_reduce_x16_i32": [_vp, _i, _i, _vp, _sz, _i, _vp],
+    "ina_quantize_reduce_x16_i16_sat": [_vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp],
+    "ina_absmax_multi_x16": [_vp, _i, _i, _vp, _sz, _vp, _vp],
+    "ina_quantize_pack_nga_x16_desc": [_vp, _i, _vp, _sz, _i, C.POINTER(NgaParams), _vp, _sz, _vp, _vp],
+    "ina_quantize_pack_nga_multi_split_x16": [_vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp],
+    "ina_dequantize_i32_x16": [_vp, _vp, _i, _sz, _i, _vp],
+    "ina_dequantize_i16_x16": [_vp, _vp, _i, _sz, _i, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -128,7 +141,7 @@ def open_library(path: str) -> C.CDLL:
     if not os.path.exists(path):
         raise InaError(f"libina.so not built at {path}; run `make -C {CSRC}` or __graft_entry__.build()")
     lib = C.CDLL(path)
-    for name, args in SIGNATURES.items():
+    for name, args in {**SIGNATURES, **SIGNATURES_X16}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

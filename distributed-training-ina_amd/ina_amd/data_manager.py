@@ -49,7 +49,11 @@ class DataManager:
 
     # DataManager.py:167-168
     def update_data(self, new_data):
-        x = torch.as_tensor(new_data, dtype=torch.float32)
+        # a bf16 / fp16 tensor is quantised as it is (no fp32 copy); anything else as float32
+        if isinstance(new_data, torch.Tensor) and new_data.dtype in (torch.bfloat16, torch.float16):
+            x = new_data
+        else:
+            x = torch.as_tensor(new_data, dtype=torch.float32)
         x = x.reshape(-1).to(self.device, non_blocking=True).contiguous()
         self.data = ops.quantize(x, self.k)
 

@@ -41,6 +41,38 @@ def _req(t: torch.Tensor, dtype, name: str):
         raise ValueError(f"{name} must be contiguous")
 
 
+# 16-bit gradient dtypes -> the C ABI's type code (include/ina.h INA_X16_*)
+_X16 = {torch.bfloat16: _lib.X16_BF16, torch.float16: _lib.X16_F16}
+
+
+def _req_grad(t: torch.Tensor, name: str):
+    """A gradient input: float32, bfloat16 or float16.  Returns 0 for float32 (the fp32 entry
+    points), else the 16-bit type code."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype in _X16:
+        _req(t, t.dtype, name)
+        return _X16[t.dtype]
+    _req(t, torch.float32, name)
+    return 0
+
+
+def _grad_bufs(bufs, name="bufs"):
+    """Worker buckets of ONE gradient dtype (float32, bfloat16 or float16): (bufs, n, type code)."""
+    if isinstance(bufs, torch.Tensor):
+        bufs = list(bufs.unbind(0)) if bufs.dim() > 1 else [bufs]
+    bufs = list(bufs)
+    dt = bufs[0].dtype if bufs and isinstance(bufs[0], torch.Tensor) else torch.float32
+    if dt not in _X16:
+        dt = torch.float32
+    for i, b in enumerate(bufs):
+        if isinstance(b, torch.Tensor) and b.dtype != dt and (b.dtype in _X16 or b.dtype == torch.float32):
+            raise TypeError(f"all workers of one call share one dtype: {name}[0] is {dt}, "
+                            f"{name}[{i}] is {b.dtype}")
+    bufs, n = _bufs(bufs, dt, name)
+    return bufs, n, _X16.get(dt, 0)
+
+
 def _fits(out: torch.Tensor, numel: int, name: str = "out"):
     """A caller-supplied output must hold what the kernel writes (the C ABI sees only a
     pointer, so a short buffer would be an out-of-bounds device write)."""
@@ -64,17 +96,20 @@ def nga_stride(V: int) -> int:
 
 # -- quantise / dequantise -------------------------------------------------------------
 def quantize(x: torch.Tensor, k: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    _req(x, torch.float32, "x")
+    xt = _req_grad(x, "x")
     out = torch.empty(x.shape, dtype=torch.int32, device=x.device) if out is None else out
     _fits(out, x.numel())
     _req(out, torch.int32, "out")
-    check(load().ina_quantize_f32_i32(x.data_ptr(), out.data_ptr(), x.numel(), k, _stream(x)),
-          "quantize")
+    if xt:      # bf16 / fp16: widened in registers, the fp32 result bit for bit
+        rc = load().ina_quantize_x16_i32(x.data_ptr(), xt, out.data_ptr(), x.numel(), k, _stream(x))
+    else:
+        rc = load().ina_quantize_f32_i32(x.data_ptr(), out.data_ptr(), x.numel(), k, _stream(x))
+    check(rc, "quantize")
     return out
 
 
 def quantize_i16(x: torch.Tensor, k: int, V: int, out=None, overflow=None):
-    _req(x, torch.float32, "x")
+    xt = _req_grad(x, "x")
     out = torch.empty(x.shape, dtype=torch.int16, device=x.device) if out is None else out
     _fits(out, x.numel())
     nslot = (x.numel() + V - 1) // V
@@ -82,15 +117,23 @@ def quantize_i16(x: torch.Tensor, k: int, V: int, out=None, overflow=None):
     _fits(overflow, nslot, "overflow")
     _req(out, torch.int16, "out")
     _req(overflow, torch.uint8, "overflow")
-    check(load().ina_quantize_f32_i16_sat(x.data_ptr(), out.data_ptr(), x.numel(), k, V,
-                                          overflow.data_ptr(), _stream(x)), "quantize_i16")
+    if xt:
+        rc = load().ina_quantize_x16_i16_sat(x.data_ptr(), xt, out.data_ptr(), x.numel(), k, V,
+                                             overflow.data_ptr(), _stream(x))
+    else:
+        rc = load().ina_quantize_f32_i16_sat(x.data_ptr(), out.data_ptr(), x.numel(), k, V,
+                                             overflow.data_ptr(), _stream(x))
+    check(rc, "quantize_i16")
     return out, overflow
 
 
 def quantize_i16_wire(x: torch.Tensor, k: int, out: torch.Tensor | None = None) -> torch.Tensor:
     """fp32 -> int32 wire words q16(x) + (saturated << 22) (include/ina.h): the int16
     quantisation widened so an int32 SUM collective carries the sum and the saturation
-    count together (the sharded int16 path, dist.ShardedAggregator(wire="i16"))."""
+    count together (the sharded int16 path, dist.ShardedAggregator(wire="i16")).  fp32 only."""
+    if isinstance(x, torch.Tensor) and x.dtype in _X16:
+        raise TypeError(f"quantize_i16_wire takes float32 only (the sharded int16 wire has no 16-bit "
+                        f"source path), got {x.dtype}")
     _req(x, torch.float32, "x")
     out = torch.empty(x.shape, dtype=torch.int32, device=x.device) if out is None else out
     _fits(out, x.numel())
@@ -128,16 +171,29 @@ def i16_wire_finish(wire_sum: torch.Tensor, k: int, V: int, out16=None, y=None, 
     return out16, y, overflow
 
 
-def dequantize(s: torch.Tensor, k: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    out = torch.empty(s.shape, dtype=torch.float32, device=s.device) if out is None else out
+def dequantize(s: torch.Tensor, k: int, out: torch.Tensor | None = None,
+               dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """y = float(s) * 2^-k as float32, or rounded once (to nearest even) to bfloat16 / float16:
+    the dtype of `out` decides, `dtype` only when out is None."""
+    if out is None:
+        if dtype != torch.float32 and dtype not in _X16:
+            raise TypeError(f"dtype must be float32, bfloat16 or float16, got {dtype}")
+        out = torch.empty(s.shape, dtype=dtype, device=s.device)
     _fits(out, s.numel())
-    _req(out, torch.float32, "out")
+    yt = _req_grad(out, "out")
+    lib = load()
     if s.dtype == torch.int16:
         _req(s, torch.int16, "s")
-        rc = load().ina_dequantize_i16_f32(s.data_ptr(), out.data_ptr(), s.numel(), k, _stream(s))
+        if yt:
+            rc = lib.ina_dequantize_i16_x16(s.data_ptr(), out.data_ptr(), yt, s.numel(), k, _stream(s))
+        else:
+            rc = lib.ina_dequantize_i16_f32(s.data_ptr(), out.data_ptr(), s.numel(), k, _stream(s))
     else:
         _req(s, torch.int32, "s")
-        rc = load().ina_dequantize_i32_f32(s.data_ptr(), out.data_ptr(), s.numel(), k, _stream(s))
+        if yt:
+            rc = lib.ina_dequantize_i32_x16(s.data_ptr(), out.data_ptr(), yt, s.numel(), k, _stream(s))
+        else:
+            rc = lib.ina_dequantize_i32_f32(s.data_ptr(), out.data_ptr(), s.numel(), k, _stream(s))
     check(rc, "dequantize")
     return out
 
@@ -219,18 +275,21 @@ def sum_reduce_i16(bufs, V: int, out=None, overflow=None):
 
 
 def quantize_reduce(bufs, k: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    bufs, n = _bufs(bufs, torch.float32)
+    bufs, n, xt = _grad_bufs(bufs)
     out = torch.empty(n, dtype=torch.int32, device=bufs[0].device) if out is None else out
     _fits(out, n)
     _req(out, torch.int32, "out")
     arr = ptr_array([b.data_ptr() for b in bufs])
-    check(load().ina_quantize_reduce_f32_i32(arr, len(bufs), out.data_ptr(), n, k, _stream(out)),
-          "quantize_reduce")
+    if xt:
+        rc = load().ina_quantize_reduce_x16_i32(arr, xt, len(bufs), out.data_ptr(), n, k, _stream(out))
+    else:
+        rc = load().ina_quantize_reduce_f32_i32(arr, len(bufs), out.data_ptr(), n, k, _stream(out))
+    check(rc, "quantize_reduce")
     return out
 
 
 def quantize_reduce_i16(bufs, k: int, V: int, out=None, overflow=None):
-    bufs, n = _bufs(bufs, torch.float32)
+    bufs, n, xt = _grad_bufs(bufs)
     dev = bufs[0].device
     out = torch.empty(n, dtype=torch.int16, device=dev) if out is None else out
     _fits(out, n)
@@ -240,9 +299,13 @@ def quantize_reduce_i16(bufs, k: int, V: int, out=None, overflow=None):
     _req(overflow, torch.uint8, "overflow")
     _fits(overflow, (n + V - 1) // V, "overflow")
     arr = ptr_array([b.data_ptr() for b in bufs])
-    check(load().ina_quantize_reduce_f32_i16_sat(arr, len(bufs), out.data_ptr(), n, k, V,
-                                                 overflow.data_ptr(), _stream(out)),
-          "quantize_reduce_i16")
+    if xt:
+        rc = load().ina_quantize_reduce_x16_i16_sat(arr, xt, len(bufs), out.data_ptr(), n, k, V,
+                                                    overflow.data_ptr(), _stream(out))
+    else:
+        rc = load().ina_quantize_reduce_f32_i16_sat(arr, len(bufs), out.data_ptr(), n, k, V,
+                                                    overflow.data_ptr(), _stream(out))
+    check(rc, "quantize_reduce_i16")
     return out, overflow
 
 
@@ -341,8 +404,9 @@ def quantize_pack_nga(x: torch.Tensor, k: int, V: int, bitmap: int, count: int, 
                       num_slots: int = NUM_REGISTER, stride: int | None = None,
                       out: torch.Tensor | None = None, desc=None):
     """Fused worker side: NGA-V packets of quantize(x - base, k) in one pass (same bytes as
-    quantize() then pack_nga()); desc as in pack_nga."""
-    _req(x, torch.float32, "x")
+    quantize() then pack_nga()); desc as in pack_nga.  x: float32, bfloat16 or float16 (base
+    stays float32)."""
+    xt = _req_grad(x, "x")
     if base is not None:
         _req(base, torch.float32, "base")
         if base.numel() != x.numel():
@@ -355,10 +419,14 @@ def quantize_pack_nga(x: torch.Tensor, k: int, V: int, bitmap: int, count: int, 
     prm = _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
                          seq0 & 0xFFFFFFFF, num_slots, V)
     d = _desc_arg(desc, npk, x.device)
-    check(load().ina_quantize_pack_nga_desc(x.data_ptr(), base.data_ptr() if base is not None else None,
-                                            x.numel(), k, C.byref(prm), out.data_ptr(), stride,
-                                            d.data_ptr() if d is not None else None, _stream(x)),
-          "quantize_pack_nga")
+    bp, dp = base.data_ptr() if base is not None else None, d.data_ptr() if d is not None else None
+    if xt:
+        rc = load().ina_quantize_pack_nga_x16_desc(x.data_ptr(), xt, bp, x.numel(), k, C.byref(prm),
+                                                   out.data_ptr(), stride, dp, _stream(x))
+    else:
+        rc = load().ina_quantize_pack_nga_desc(x.data_ptr(), bp, x.numel(), k, C.byref(prm), out.data_ptr(),
+                                               stride, dp, _stream(x))
+    check(rc, "quantize_pack_nga")
     return (out, d) if d is not None else out
 
 
@@ -370,7 +438,11 @@ def quantize_pack_nga_multi(xs, k: int, V: int, bitmaps, count: int, switch_id: 
     packets of quantize(xs[w] - base, k) with header word bitmaps[w] and sequence start
     seq0 (an int for all workers or one per worker); the shared base is read once for
     every 8 workers.  Same bytes as W quantize_pack_nga calls.  outs / descs: W tensors
-    each (descs=True allocates them); returns outs, or (outs, descs)."""
+    each (descs=True allocates them); returns outs, or (outs, descs).  fp32 only: 16-bit
+    buckets go through quantize_pack_nga_multi_split."""
+    if any(isinstance(x, torch.Tensor) and x.dtype in _X16 for x in (xs if not isinstance(xs, torch.Tensor) else [xs])):
+        raise TypeError("quantize_pack_nga_multi takes float32 only; bfloat16 / float16 buckets go "
+                        "through quantize_pack_nga_multi_split")
     xs, n = _bufs(xs, torch.float32, "xs")
     W, dev = len(xs), xs[0].device
     if base is not None:
@@ -452,8 +524,9 @@ def quantize_pack_nga_multi_split(xs, k: int, V: int, bitmaps, count: int, switc
                                   num_slots: int = NUM_REGISTER, hdrs=None, pays=None, descs=None):
     """quantize_pack_nga_multi into split rows (ina_quantize_pack_nga_multi_split): W
     workers' quantize(xs[w] - base, k) as header rows hdrs[w] + payload rows pays[w], the
-    base read once per 8 workers.  Returns (hdrs, pays) or (hdrs, pays, descs)."""
-    xs, n = _bufs(xs, torch.float32, "xs")
+    base read once per 8 workers.  Returns (hdrs, pays) or (hdrs, pays, descs).  xs: float32,
+    bfloat16 or float16, one dtype for all workers (base stays float32)."""
+    xs, n, xt = _grad_bufs(xs, "xs")
     W, dev = len(xs), xs[0].device
     if base is not None:
         _req(base, torch.float32, "base")
@@ -479,11 +552,14 @@ def quantize_pack_nga_multi_split(xs, k: int, V: int, bitmaps, count: int, switc
     prm = (_lib.NgaParams * W)(*[_lib.NgaParams(bitmaps[w] & 0xFFFFFFFF, count & 0xFF, flags & 0xFF,
                                                 switch_id & 0xFF, 0, seqs[w] & 0xFFFFFFFF, num_slots, V)
                                  for w in range(W)])
-    check(load().ina_quantize_pack_nga_multi_split(
-        ptr_array([x.data_ptr() for x in xs]), W, base.data_ptr() if base is not None else None, n, k,
-        prm, ptr_array([h.data_ptr() for h in hdrs]), ptr_array([p.data_ptr() for p in pays]),
-        ptr_array([d.data_ptr() for d in ds]) if ds is not None else None, _stream(xs[0])),
-        "quantize_pack_nga_multi_split")
+    xa, bp = ptr_array([x.data_ptr() for x in xs]), base.data_ptr() if base is not None else None
+    ha, pa = ptr_array([h.data_ptr() for h in hdrs]), ptr_array([p.data_ptr() for p in pays])
+    da = ptr_array([d.data_ptr() for d in ds]) if ds is not None else None
+    if xt:
+        rc = load().ina_quantize_pack_nga_multi_split_x16(xa, xt, W, bp, n, k, prm, ha, pa, da, _stream(xs[0]))
+    else:
+        rc = load().ina_quantize_pack_nga_multi_split(xa, W, bp, n, k, prm, ha, pa, da, _stream(xs[0]))
+    check(rc, "quantize_pack_nga_multi_split")
     return (hdrs, pays, ds) if ds is not None else (hdrs, pays)
 
 
@@ -625,8 +701,9 @@ def checksum(x: torch.Tensor) -> torch.Tensor:
 
 # -- dynamic scale ---------------------------------------------------------------------------
 def absmax(x: torch.Tensor, base: torch.Tensor | None = None, out: torch.Tensor | None = None):
-    """Device float32 [1] = max_i |x[i] - base[i]| (base optional; NaN ignored)."""
-    _req(x, torch.float32, "x")
+    """Device float32 [1] = max_i |x[i] - base[i]| (base optional; NaN ignored).  x: float32,
+    bfloat16 or float16; base and the result stay float32."""
+    xt = _req_grad(x, "x")
     if base is not None:
         _req(base, torch.float32, "base")
         if base.numel() != x.numel():
@@ -635,8 +712,12 @@ def absmax(x: torch.Tensor, base: torch.Tensor | None = None, out: torch.Tensor 
     out = torch.empty(1, dtype=torch.float32, device=x.device) if out is None else out
     _fits(out, 1)
     _req(out, torch.float32, "out")
-    check(load().ina_absmax_f32(x.data_ptr(), base.data_ptr() if base is not None else None,
-                                x.numel(), out.data_ptr(), _stream(x)), "absmax")
+    bp = base.data_ptr() if base is not None else None
+    if xt:      # the single-bucket form of the multi-bucket pass
+        rc = load().ina_absmax_multi_x16(ptr_array([x.data_ptr()]), xt, 1, bp, x.numel(), out.data_ptr(), _stream(x))
+    else:
+        rc = load().ina_absmax_f32(x.data_ptr(), bp, x.numel(), out.data_ptr(), _stream(x))
+    check(rc, "absmax")
     return out
 
 
@@ -650,8 +731,9 @@ def scale_for(amax: float, W: int, bits: int = 32) -> int:
 
 def absmax_multi(xs, base: torch.Tensor | None = None, out: torch.Tensor | None = None):
     """Device float32 [1] = max_w,i |xs[w][i] - base[i]| over W buckets in ONE pass
-    (ina_absmax_multi_f32: each base chunk is read once for all W workers)."""
-    xs, n = _bufs(xs, torch.float32, "xs")
+    (ina_absmax_multi_f32: each base chunk is read once for all W workers).  xs: float32,
+    bfloat16 or float16, one dtype for all workers."""
+    xs, n, xt = _grad_bufs(xs, "xs")
     if base is not None:
         _req(base, torch.float32, "base")
         if base.numel() != n:
@@ -661,8 +743,12 @@ def absmax_multi(xs, base: torch.Tensor | None = None, out: torch.Tensor | None 
     _fits(out, 1)
     _req(out, torch.float32, "out")
     arr = ptr_array([x.data_ptr() for x in xs])
-    check(load().ina_absmax_multi_f32(arr, len(xs), base.data_ptr() if base is not None else None,
-                                      n, out.data_ptr(), _stream(xs[0])), "absmax_multi")
+    bp = base.data_ptr() if base is not None else None
+    if xt:
+        rc = load().ina_absmax_multi_x16(arr, xt, len(xs), bp, n, out.data_ptr(), _stream(xs[0]))
+    else:
+        rc = load().ina_absmax_multi_f32(arr, len(xs), bp, n, out.data_ptr(), _stream(xs[0]))
+    check(rc, "absmax_multi")
     return out
 
 

@@ -271,6 +271,25 @@ int ina_quantize_pack_nga_multi_split(const float* const* x, int W, const float*
                                       ina_stream_t stream);
 int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npkts, int V,
                          const ina_nga_fields_t* fields, int32_t* vals, ina_stream_t stream);
+/* ---- bf16 / fp16 gradients -------------------------------------------------------
+ * The reference's data path is "16bit float -> 32bit integer" (types.p4:10); a bucket that
+ * is already bf16 or fp16 goes through the quantiser, the fused reduce and the packs as it
+ * is, with no fp32 copy.  x / bufs / xs point at 16-bit values of type `xtype` (2-byte
+ * aligned at least; the vector paths need every source and output 16-byte aligned, any
+ * other alignment takes a scalar path with identical results).  Any other xtype / ytype is
+ * INA_EINVAL before any device work.  Argument order, return codes, the n == 0 no-op and the
+ * null checks are those of the fp32 sibling named in each comment.
+ *   Quantise side: the result is exactly the fp32 sibling's on (float)x[i].  Widening is
+ *     exact, fp16 subnormals included (2^-24 at k = 24 quantises to 1); +-inf saturates, NaN
+ *     gives 0 (and sets the slot flag on the int16 paths).
+ *   base stays fp32 (the PS's global parameter vector): the delta is the fp32 subtraction
+ *     (float)x[i] - base[i], rounded once, as in the fp32 packs.
+ *   Dequantise side: y[i] = rne16((float)s[i] * 2^-k), the fp32 result rounded once to the
+ *     target type, round-to-nearest-even: fp16 overflows to +-inf and fp16 subnormals are
+ *     produced, not flushed.
+ * The declarations are in ina_x16.h, included here (it needs the packet types above). */
+#include "ina_x16.h"   /* INA_X16_BF16 / INA_X16_F16 and the ina_*_x16_* entry points */
+
 /* C-128 pack (communicator.cc:23-37): npkts x 524-byte packet_t, all words htonl. */
 int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,
                   uint32_t aggregator_index, int tensor_index, uint8_t* pkts,

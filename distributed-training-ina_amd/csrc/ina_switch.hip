@@ -248,6 +248,7 @@ struct KeySrc {
         return slot | ((ack_hint && ((d.x >> 14) & 1u)) ? kAckBit : 0u);
     }
 };
+constexpr int kLocEpochWord = 133;            // = kLocEpoch (the control block, below; asserted there)
 template <int R, bool kDesc, int NW = kRsWaves>
 __global__ __launch_bounds__(NW * 64) void k_switch_keys(const uint8_t* __restrict__ pkts,
                                                           const uint2* __restrict__ desc,
@@ -265,6 +266,7 @@ __global__ __launch_bounds__(NW * 64) void k_switch_keys(const uint8_t* __restri
         ctl[0] = epoch;
         ctl[1] = epoch;
         ctl[2] = 0u;
+        ctl[kLocEpochWord] = 0u;                               // (no stale "near-sorted" tag either)
     }
     const int lane = threadIdx.x & 63, wv = wave_in_block();
     const size_t c = blockIdx.x;
@@ -763,6 +765,7 @@ constexpr int kLocVerdict = kLocEpoch + 6;            // 2 words: the decision, 
 static_assert((kCtlEpochs + kLocVerdict) % 2 == 0, "the verdict is 8-byte aligned in the control block");
 constexpr int kCtlWords = kCtlLocal + 8;
 static_assert(kCtlWords * 4 <= 1024, "control block fits its 1 KiB");
+static_assert(kLocEpochWord == kLocEpoch, "k_switch_keys clears the near-sorted epoch");
 
 // the run table from the chunks' break records (a structured batch, total <= kRunsMax breaks),
 // by one block of kBkThr threads: thread t takes chunks 2t and 2t+1 (nch <= 2 x kBkThr), so the
@@ -1519,7 +1522,15 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     // the identity permutation).  Tagged with the call's epoch, so nothing needs clearing.
     if constexpr (kMode != 2) {
         if (__ballot(down) && lane == 0) unsorted[0] = epoch;
-        if (c == 0 && threadIdx.x == 0) unsorted[1] = epoch;     // this call's epoch, for the run kernel
+        if (c == 0 && threadIdx.x == 0) {
+            unsorted[1] = epoch;                                 // this call's epoch, for the run kernel
+            // the words a LATER launch of this call tags when it chooses a path: cleared here, so
+            // a word the scratch held on entry never passes for this call's tag (no epoch is 0)
+            unsorted[2] = 0u;
+            unsorted[kLocEpoch] = 0u;
+            unsorted[kLocVerdict] = 0u;
+            unsorted[kLocVerdict + 1] = 0u;
+        }
     }
     uint32_t nbw = 0;                                         // this wave's breaks
 #pragma unroll
@@ -1538,12 +1549,17 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         // (kflags) only a wave the near-sorted lists may read stores its keys: one with a descent
         // (a wave in slot order is read from the descriptors) whose slots span at most
         // kKeysSpanMax (a shuffled batch's waves span the pool and take the sort, which reads the
-        // descriptors itself)
-        if (kflags && __ballot(down) && kmx >= kmn && kmx - kmn <= kKeysSpanMax && kmx - kmn > kKeysSpanMin) {
+        // descriptors itself).  Every wave writes its flag on every call -- the epoch if it
+        // stored, else 0 (no epoch is 0): the scratch is not cleared and the flags' offset moves
+        // with npk, so a word an earlier, larger batch left there may equal this call's epoch
+        if (kflags) {
+            const bool st = __ballot(down) && kmx >= kmn && kmx - kmn <= kKeysSpanMax && kmx - kmn > kKeysSpanMin;
+            if (st) {
 #pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (i0 + (size_t)r * 64 < npk) kout[i0 + (size_t)r * 64] = k[r];
-            if (lane == 0) kflags[c * kBkWaves + wv] = epoch;
+                for (int r = 0; r < R; ++r)
+                    if (i0 + (size_t)r * 64 < npk) kout[i0 + (size_t)r * 64] = k[r];
+            }
+            if (lane == 0) kflags[c * kBkWaves + wv] = st ? epoch : 0u;
         }
     }
     __syncthreads();
@@ -3617,7 +3633,14 @@ __global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? 
             return;
         }
         if (unsorted[2] == ep) {
-            // a batch of dense ascending runs: the decision wrote the run table, not a sort
+            // a batch of dense ascending runs: the decision wrote the run table, not a sort.
+            // Precedence: the lists, then the run table, then the in-order test -- a run table
+            // tagged with this call's epoch wins over the in-order windows.  Both deciders
+            // (k_sort_chunks mode 2, k_sort_buckets) build the table only after a descent was
+            // found, so a batch that is in slot order AND dense runs (one sender, worker-major)
+            // has no table of this call and falls through to the in-order test; were one built,
+            // switch_runs_body would take it, with the same results -- both walk a slot's packets
+            // in arrival order (test_whole_segments_vs_oracle, order "one_sender")
             switch_runs_body<kPs, kNarrow, kSplit>(st, pkts, stride, pay, actions, kmask, ps,
                                                    unsorted + (kCtlRuns - kCtlEpochs), wave, nwaves,
                                                    drop_prefill != 0);

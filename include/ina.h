@@ -302,7 +302,14 @@ int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,
  * packets are rewritten in place (slot sum, collision bit; dropped ones too when
  * write_dropped) and actions[p] gets INA_ACT_*.
  * scratch: device buffer of ina_switch_scratch_bytes(npkts, num_slots) bytes; the size
- * is monotonic in npkts, so one buffer sized for the largest batch serves them all. */
+ * is monotonic in npkts, so one buffer sized for the largest batch serves them all.
+ * The scratch's contents on entry are arbitrary: nothing need be zeroed, a buffer may come
+ * straight from the allocator or from a call over another batch size, pool or switch, and
+ * results (actions, rewritten rows, registers, the PS step) never depend on them.  Every
+ * word a call reads it has written itself, or it is tagged with the call's epoch (never 0)
+ * after the call cleared the tag.  Only which sort path a batch takes may: a batch in slot
+ * order is sorted needlessly if the one "descent found" word held this call's epoch on
+ * entry (ina_switch_batch_path then says so). */
 typedef struct ina_switch_state {
     uint32_t num_slots;
     int32_t V;

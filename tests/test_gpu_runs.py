@@ -635,7 +635,7 @@ def _check_split_vs_oracle(o, V, batches, want_paths, write_dropped, num_slots=P
 
 
 @pytest.mark.parametrize("write_dropped", [False, True])
-@pytest.mark.parametrize("order", ["worker_major", "round_robin", "jitter", "shuffled"])
+@pytest.mark.parametrize("order", ["worker_major", "round_robin", "jitter", "shuffled", "one_sender"])
 @pytest.mark.parametrize("case", ["clean", "collide", "count_open", "ack_inside", "degree4", "small_V"])
 def test_whole_segments_vs_oracle(case, order, write_dropped):
     """Round 6 (seg8_fast): split-row narrow batches whose slots hold exactly 8 packets of
@@ -644,8 +644,12 @@ def test_whole_segments_vs_oracle(case, order, write_dropped):
     (shuffled).  Any other segment in a wave sends that wave back to the packet-by-packet walk:
     a frag-id collision, a slot whose count is not 0 when the batch arrives (its first 4 packets
     came in the previous batch), a PS ack among the 8, degree 4 (two completions per segment).
-    V = 8 leaves 6 of a group's 8 lanes without payload.  Bit-exact against the P4 restatement
-    with registers after every batch, with and without write_dropped."""
+    V = 8 leaves 6 of a group's 8 lanes without payload.  Order "one_sender": one sender's
+    packets alone, worker-major -- a batch both in slot order and one dense run.  No descent, so
+    no run table is built and the in-order windows take it (k_switch_run2 tests the run table's
+    epoch before the in-order test); the same sender's run is what the run-table kernel walks
+    when the other seven senders follow it (order "worker_major").  Bit-exact against the P4
+    restatement with registers after every batch, with and without write_dropped."""
     o = ops()
     V = 8 if case == "small_V" else 32
     W, per = 8, 2000
@@ -655,7 +659,7 @@ def test_whole_segments_vs_oracle(case, order, write_dropped):
 
     def arrive(b, k):
         n = len(b)
-        if order == "worker_major":
+        if order in ("worker_major", "one_sender"):
             return b
         rr = b.reshape(k, n // k, stride).transpose(1, 0, 2).reshape(n, stride)
         if order == "round_robin":
@@ -666,7 +670,9 @@ def test_whole_segments_vs_oracle(case, order, write_dropped):
 
     batches = []
     for bi in range(2):
-        if case == "count_open" and bi == 0:
+        if order == "one_sender":
+            specs = [(5, per // 2 if case == "count_open" and bi == 0 else per, bi)]
+        elif case == "count_open" and bi == 0:
             specs = [(5, per // 2, w) for w in range(4)]           # half the slots: 4 of 8 packets
         else:
             specs = [(5, per, w) for w in range(W)]
@@ -679,7 +685,7 @@ def test_whole_segments_vs_oracle(case, order, write_dropped):
                 b[i, 5] |= orc.FLAG_ACK                            # a PS ack among a slot's packets
         batches.append(arrive(b, k))
     want = {"worker_major": ("runs",), "round_robin": ("in_order",), "jitter": ("local",),
-            "shuffled": ("sorted", "local")}[order]
+            "shuffled": ("sorted", "local"), "one_sender": ("in_order",)}[order]
     if case == "count_open" and order == "worker_major":
         want = ("runs",)
     _check_split_vs_oracle(o, V, batches, want, write_dropped)

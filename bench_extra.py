@@ -118,6 +118,107 @@ def run_x16(dev, dtype=torch.bfloat16):
     return rows
 
 
+def _wall(fn, reps=20, warm=3):
+    """Median wall time of fn() from an idle device to an idle device (for paths with a host read)."""
+    import time
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        _flush()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts)
+
+
+def run_blk(dev):
+    """Per-block scales (include/ina_blk.h) at the ResNet-50 size, cold caches, median of 20, the
+    whole set twice in this process (run 1 / run 2).  GIVEN calls and ps_apply_blk beside their
+    global-k sibling timed twice (the two times' difference is the spread); the bar is sibling time
+    x bytes ratio + spread.  AUTO calls and the block-scaled PS combine beside the composition a
+    caller would otherwise write (block_scales, then the GIVEN call) -- they must beat it -- and
+    beside the global-k sibling (ratio reported).  The PS combine also against today's k="auto"
+    path (absmax_multi, the host read, ina_ps_combine_ina_f32), both as wall time."""
+    from ina_amd import ops, ps
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(17)
+    n, k = 25_557_032, 16
+    Wmax = 16
+    b = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(Wmax)]
+    local = torch.randn(n, device=dev, generator=gen) * 1e-2
+    q = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+
+    def given(run, name, V, nb_sib, f_blk, f_sib):
+        nblk = (n + V - 1) // V
+        ta, tb, tc = _time(f_sib), _time(f_blk), _time(f_sib)
+        lo, hi = min(ta, tc), max(ta, tc)
+        bar = hi * (nb_sib + nblk) / nb_sib + (hi - lo)
+        rows.append(_row(f"{name} V={V} [blk given, run {run}]", tb, nb_sib + nblk,
+                         sibling_us=[round(ta * 1e6, 2), round(tc * 1e6, 2)], sibling_spread_us=round((hi - lo) * 1e6, 2),
+                         bar_us=round(bar * 1e6, 2), bar_met=bool(tb <= bar)))
+
+    def auto(run, name, V, nb_sib, f_auto, f_scales, f_given, f_sib):
+        nblk = (n + V - 1) // V
+        ts, ta, tc = _time(f_sib), _time(f_auto), _time(lambda: (f_scales(), f_given()))
+        rows.append(_row(f"{name} V={V} [blk auto, run {run}]", ta, nb_sib + nblk,
+                         scales_then_given_us=round(tc * 1e6, 2), beats_scales_then_given=bool(ta < tc),
+                         sibling_us=round(ts * 1e6, 2), ratio_to_sibling=round(ta / ts, 3)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = (n + V - 1) // V
+            f = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kb32 = ops.block_scales(b[:8], V, bits=32)
+            kb16 = ops.block_scales(b, V, bits=16)
+            kb = torch.empty(nblk, dtype=torch.int8, device=dev)
+            given(run, "quantize", V, 8 * n, lambda: ops.quantize_blk(b[0], kb32, V, out=q),
+                  lambda: ops.quantize(b[0], k, out=q))
+            given(run, "quantize_i16", V, 6 * n + nblk, lambda: ops.quantize_i16_blk(b[0], kb16, V, out=o16, overflow=f),
+                  lambda: ops.quantize_i16(b[0], 13, V, out=o16, overflow=f))
+            given(run, "quantize_reduce W=8", V, 36 * n, lambda: ops.quantize_reduce_blk(b[:8], V, kblk=kb32, out=q),
+                  lambda: ops.quantize_reduce(b[:8], k, out=q))
+            for W in (4, 16):
+                given(run, f"quantize_reduce_i16 W={W}", V, (4 * W + 2) * n + nblk,
+                      lambda: ops.quantize_reduce_i16_blk(b[:W], V, kblk=kb16, out=o16, overflow=f),
+                      lambda: ops.quantize_reduce_i16(b[:W], 13, V, out=o16, overflow=f))
+            ops.quantize_reduce(b[:8], k, out=q)
+            given(run, "dequantize_i32", V, 8 * n, lambda: ops.dequantize_blk(q, kb32, V, out=y),
+                  lambda: ops.dequantize(q, k, out=y))
+            given(run, "dequantize_i16", V, 6 * n, lambda: ops.dequantize_blk(o16, kb16, V, out=y),
+                  lambda: ops.dequantize(o16, 13, out=y))
+            given(run, "ps_apply", V, 12 * n, lambda: ops.ps_apply_blk(local, q, kb32, V, 0.1, out=y),
+                  lambda: ops.ps_apply(local, q, k, 0.1, out=y))
+            for W in (4, 16):
+                auto(run, f"quantize_reduce_i16 W={W}", V, (4 * W + 2) * n + nblk,
+                     lambda: ops.quantize_reduce_i16_blk(b[:W], V, out=o16, overflow=f, kblk_out=kb),
+                     lambda: ops.block_scales(b[:W], V, bits=16, out=kb),
+                     lambda: ops.quantize_reduce_i16_blk(b[:W], V, kblk=kb, out=o16, overflow=f),
+                     lambda: ops.quantize_reduce_i16(b[:W], 13, V, out=o16, overflow=f))
+            auto(run, "quantize_reduce W=8", V, 36 * n,
+                 lambda: ops.quantize_reduce_blk(b[:8], V, out=q, kblk_out=kb),
+                 lambda: ops.block_scales(b[:8], V, bits=32, out=kb),
+                 lambda: ops.quantize_reduce_blk(b[:8], V, kblk=kb, out=q),
+                 lambda: ops.quantize_reduce(b[:8], k, out=q))
+            # the PS combine's composition: scales of the deltas, the fused reduce cannot take a base, so
+            # the caller's second pass is the global-k combine's bytes again (timed as block_scales + sibling)
+            auto(run, "ps_combine_ina W=8", V, 40 * n,
+                 lambda: ops.ps_combine_ina_blk(local, b[:8], V, 0.1, out=y, kblk_out=kb),
+                 lambda: ops.block_scales(b[:8], V, bits=32, base=local, out=kb),
+                 lambda: ps.combine_ina(local, b[:8], k, 0.1, out=y),
+                 lambda: ps.combine_ina(local, b[:8], k, 0.1, out=y))
+            t_auto = _wall(lambda: ps.combine_ina(local, b[:8], "auto", 0.1, out=y))
+            t_blk = _wall(lambda: ps.combine_ina(local, b[:8], "block", 0.1, out=y, block=V))
+            rows.append(_row(f"ps.combine_ina k=block V={V} W=8 [wall, run {run}]", t_blk, 40 * n + nblk,
+                             k_auto_wall_us=round(t_auto * 1e6, 2), ratio_to_k_auto=round(t_blk / t_auto, 3)))
+    return rows
+
+
 DEFAULTS = {"max_blocks": 16384, "reduce_blocks": 0, "stream_blocks": 16384, "combine_blocks": 256,
             "combine_ina_blocks": 8192, "ew_blocks": 1 << 24}
 
@@ -493,4 +594,5 @@ def run_extra(dev):
     ops.set_tuning(h2d_streams=2)
     del hosts, hout, dbuf, b3, o3
     rows += run_x16(dev)
+    rows += run_blk(dev)
     return {"rows": rows, "sweep": sweep, "grid_sweeps": gsweep}

@@ -1,0 +1,764 @@
+// ina_blk.hip -- per-block scales (block floating point) for the quantiser, the fused reduces
+// and the PS update (include/ina_blk.h states the contract).
+//
+// One int8 exponent per block of V values.  Every kernel here runs the quantiser of the global-k
+// entry points (q32 / q16 / sat16, ina_device.h) with the block's own 2^k, so a block's result is
+// bit for bit the sibling's on that block alone.
+//
+// Lane layout (vector path: V a power of two in [8, 256], 16-byte aligned buffers, 256-thread
+// workgroups, non-temporal loads, write-through stores, like the siblings).  A lane always holds
+// 16-byte chunks of 4 fp32 / int32 values, so a block is V/4 adjacent lanes of one wave:
+//   32-bit side (quantise / reduce to int32, both dequantises, PS apply, PS combine, scales):
+//     lane l of a wave owns values 4l..4l+3 of the wave's 256 -- the siblings' layout.
+//   int16 out (quantise / reduce to int16): a wave owns 512 values as two 256-value halves, lane l
+//     the 4 at 4l of each half (16 B per lane per load, 1 KiB contiguous per instruction: the
+//     layout k_quant_reduce_i16 measured 13 % faster than 8 consecutive values per lane), one
+//     8-byte store per half.  Each half has its own group and its own scale.
+// kblk[s] is one byte load per lane of the group (the same address across the group), and the slot
+// flag comes from the one-writer ballot (write_slot_flags8) with V/4 lanes per slot.
+//
+// AUTO (scales computed in the pass): the block's max |value| is a cross-lane unsigned max of the
+// fp32 bit patterns over the group (non-negative floats order as their bits; NaN mapped to 0
+// first), butterfly over lane ^ 1, 2, ... < V/4.  It runs wave-convergent: every loop has a
+// wave-uniform trip count, lanes past n contribute 0 and take part.  Compile-time W (1, 2, 4, 8,
+// 16) keeps the lane's W chunks in registers between the max and the quantiser (one read of the
+// inputs); any other W reads them a second time in the same launch (the lane's own chunks, so the
+// second read is the one the first brought in).  A lane reads all of its chunks before it writes
+// any, so out may alias an input of the same width.
+//
+// Scalar path (any other V or alignment): one wave per block, lanes striding over the block,
+// the same helpers, identical results.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "ina.h"
+#include "ina_internal.h"
+#include "ina_device.h"
+
+namespace ina {
+namespace {
+
+using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
+using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
+using f32x4 = float __attribute__((ext_vector_type(4)));
+
+constexpr int kBlk = 256;
+constexpr int kCombineGrid = 8192;   // the INA combine's grid cap (ina_ps_combine_ina_f32)
+
+// ---------------------------------------------------------------------------
+// scales
+// ---------------------------------------------------------------------------
+// a given scale: -127 / -128 read as -126
+__device__ __forceinline__ int rd_k(const int8_t* __restrict__ kblk, size_t s) {
+    const int k = kblk[s];
+    return k < -126 ? -126 : k;
+}
+// 2^k for k in [-127, 127], built from its bits: 2^-127 is the subnormal 0x00400000 (ldexpf(1, -127)),
+// which an exp2 / division would flush or round
+__device__ __forceinline__ float pow2f(int k) {
+    return __uint_as_float(k >= -126 ? (uint32_t)(k + 127) << 23 : 0x00400000u);
+}
+// |d| as its bit pattern, NaN -> 0
+__device__ __forceinline__ uint32_t absbits(float d) {
+    const uint32_t u = __float_as_uint(d) & 0x7FFFFFFFu;
+    return u > 0x7F800000u ? 0u : u;
+}
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t fold4(uint32_t m, f32x4 a) {
+    return umax(umax(m, absbits(a.x)), umax(umax(absbits(a.y), absbits(a.z)), absbits(a.w)));
+}
+__device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
+    return f32x4{__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z), __fsub_rn(a.w, b.w)};
+}
+
+// ina_scale_for(amax, degree, bits) for amax given as its bits and lim = (2^(bits-1) - 1) / degree
+// - 1/2 as the host computed it: the largest k in [-126, 127] with amax * 2^k <= lim (-126 if
+// none).  amax = ma * 2^ea, lim = ml * 2^el with ma, ml in [1, 2): k = el - ea when ma <= ml, else
+// el - ea - 1 -- exponents and mantissas compared as integers, so the answer is the host's exact
+// double comparison for every fp32 amax (an fp32 mantissa, subnormal ones included, converts to
+// double exactly).
+__device__ __forceinline__ int scale_of(uint32_t u, double lim) {
+    if (u == 0u) return 127;
+    if (u >= 0x7F800000u) return -126;
+    const uint32_t e = u >> 23, m = u & 0x7FFFFFu;
+    const uint64_t d = (uint64_t)__double_as_longlong((double)(e ? (m | 0x800000u) : m));   // exact
+    const int ea = (int)(d >> 52) - 1023 + (int)(e ? e : 1u) - 150;
+    const uint64_t l = (uint64_t)__double_as_longlong(lim);
+    const int el = (int)(l >> 52) - 1023;
+    const uint64_t mant = (1ull << 52) - 1ull;
+    int k = el - ea - ((d & mant) > (l & mant) ? 1 : 0);
+    return k < -126 ? -126 : (k > 127 ? 127 : k);
+}
+
+// max over the `lanes` (a power of two <= 64, wave-uniform) adjacent lanes of a group; every
+// lane of the wave must reach it
+__device__ __forceinline__ uint32_t group_max(uint32_t m, int lanes) {
+    for (int off = 1; off < lanes; off <<= 1) m = umax(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    return m;
+}
+
+// ---------------------------------------------------------------------------
+// a lane's chunk of 4 values at element e; a chunk that crosses n is read and written value by
+// value (values past n read as 0)
+// ---------------------------------------------------------------------------
+template <bool NT = true>
+__device__ __forceinline__ f32x4 ld4(const float* p, size_t e, size_t n) {
+    if (e + 4 <= n) {
+        if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + e));
+        else return *reinterpret_cast<const f32x4*>(p + e);
+    }
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (e < n) v.x = p[e];
+    if (e + 1 < n) v.y = p[e + 1];
+    if (e + 2 < n) v.z = p[e + 2];
+    return v;
+}
+__device__ __forceinline__ u32x4 ld4i(const int32_t* p, size_t e, size_t n) {
+    if (e + 4 <= n) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + e));
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (e < n) v.x = (uint32_t)p[e];
+    if (e + 1 < n) v.y = (uint32_t)p[e + 1];
+    if (e + 2 < n) v.z = (uint32_t)p[e + 2];
+    return v;
+}
+// 4 int16 values, sign-extended
+__device__ __forceinline__ u32x4 ld4h(const int16_t* p, size_t e, size_t n) {
+    if (e + 4 <= n) {
+        const u32x2 h = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + e));
+        return u32x4{(uint32_t)(int32_t)(int16_t)(h.x & 0xFFFFu), (uint32_t)((int32_t)h.x >> 16),
+                     (uint32_t)(int32_t)(int16_t)(h.y & 0xFFFFu), (uint32_t)((int32_t)h.y >> 16)};
+    }
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (e < n) v.x = (uint32_t)(int32_t)p[e];
+    if (e + 1 < n) v.y = (uint32_t)(int32_t)p[e + 1];
+    if (e + 2 < n) v.z = (uint32_t)(int32_t)p[e + 2];
+    return v;
+}
+// (the element is passed by value: __builtin_bit_cast applied to a vector element itself reads
+// element 0 whichever is named)
+template <typename T, typename S>
+__device__ __forceinline__ T bits_as(S s) {
+    return __builtin_bit_cast(T, s);
+}
+template <typename V4, typename T>
+__device__ __forceinline__ void st4(V4 v, T* p, size_t e, size_t n) {
+    static_assert(sizeof(V4) == 4 * sizeof(T), "4 values");
+    if (e + 4 <= n) {
+        stream_store(v, reinterpret_cast<V4*>(p + e));
+    } else {
+        if (e < n) p[e] = bits_as<T>(v.x);
+        if (e + 1 < n) p[e + 1] = bits_as<T>(v.y);
+        if (e + 2 < n) p[e + 2] = bits_as<T>(v.z);
+    }
+}
+// 4 int16 (held widened) as one 8-byte store
+__device__ __forceinline__ void st4h(const int32_t* a, int16_t* p, size_t e, size_t n) {
+    if (e + 4 <= n) {
+        u32x2 o;
+        o.x = (uint32_t)(uint16_t)a[0] | ((uint32_t)a[1] << 16);
+        o.y = (uint32_t)(uint16_t)a[2] | ((uint32_t)a[3] << 16);
+        stream_store(o, reinterpret_cast<u32x2*>(p + e));
+    } else {
+        for (int j = 0; j < 3; ++j)
+            if (e + j < n) p[e + j] = (int16_t)a[j];
+    }
+}
+
+__device__ __forceinline__ u32x4 q32x4(f32x4 v, float s) {
+    return u32x4{(uint32_t)q32(v.x, s), (uint32_t)q32(v.y, s), (uint32_t)q32(v.z, s), (uint32_t)q32(v.w, s)};
+}
+__device__ __forceinline__ void q16x4_add(f32x4 v, float s, int32_t* a, bool& sat) {
+    a[0] += q16(v.x, s, sat); a[1] += q16(v.y, s, sat); a[2] += q16(v.z, s, sat); a[3] += q16(v.w, s, sat);
+}
+__device__ __forceinline__ f32x4 deq4(u32x4 q, float inv) {
+    return f32x4{__fmul_rn((float)(int32_t)q.x, inv), __fmul_rn((float)(int32_t)q.y, inv),
+                 __fmul_rn((float)(int32_t)q.z, inv), __fmul_rn((float)(int32_t)q.w, inv)};
+}
+// local + ws * y, the PS update's unfused fp32 sequence
+__device__ __forceinline__ f32x4 upd4(f32x4 l, f32x4 y, float ws) {
+    return f32x4{__fadd_rn(l.x, __fmul_rn(y.x, ws)), __fadd_rn(l.y, __fmul_rn(y.y, ws)),
+                 __fadd_rn(l.z, __fmul_rn(y.z, ws)), __fadd_rn(l.w, __fmul_rn(y.w, ws))};
+}
+
+// ---------------------------------------------------------------------------
+// vector path, 32-bit side: chunk i = values 4i..4i+3, block of chunk i = i >> shift
+// (shift = log2(V) - 2, a group is 1 << shift lanes).  Every loop below has a wave-uniform trip
+// count.
+// ---------------------------------------------------------------------------
+#define INA_BLK_QUAD_LOOP(nq)                                                      \
+    const size_t tid_ = (size_t)blockIdx.x * kBlk + threadIdx.x;                   \
+    const size_t stride_ = (size_t)gridDim.x * kBlk;                               \
+    for (size_t base_ = tid_ & ~(size_t)63; base_ < (nq); base_ += stride_)
+
+// scales alone: W + 1 streams, 4 workers' loads in flight (k_absmax_multi_f32's loop)
+__global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<float> xs, int W, const float* __restrict__ base,
+                                                     size_t n, int shift, double lim,
+                                                     int8_t* __restrict__ kblk) {
+    const size_t nq = (n + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    INA_BLK_QUAD_LOOP(nq) {
+        const size_t i = base_ + lane, e = 4 * i;
+        uint32_t m = 0u;
+        if (e < n) {
+            const f32x4 b = base ? ld4(base, e, n) : f32x4{0.f, 0.f, 0.f, 0.f};
+            int w = 0;
+            for (; w + 4 <= W; w += 4) {
+                f32x4 a[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) a[u] = ld4(xs.p[w + u], e, n);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) m = fold4(m, sub4(a[u], b));
+            }
+            for (; w < W; ++w) m = fold4(m, sub4(ld4(xs.p[w], e, n), b));
+        }
+        m = group_max(m, 1 << shift);
+        if (e < n && (lane & ((1 << shift) - 1)) == 0) kblk[i >> shift] = (int8_t)scale_of(m, lim);
+    }
+}
+
+// fused quantise + W-way reduce to int32 (W = 1: the plain quantiser).  W > 0: compile-time worker
+// count, chunks held in registers; W = 0: runtime count, re-read under AUTO.
+template <int W, bool AUTO>
+__global__ __launch_bounds__(kBlk) void k_qr_blk_i32(PtrPack<float> in, int Wd, int8_t* __restrict__ kblk,
+                                                     double lim, int32_t* out, size_t n, int shift) {
+    const int nw = W > 0 ? W : Wd;
+    constexpr bool HOLD = AUTO && W > 0;      // given scales: a chunk is quantised as it arrives
+    constexpr int UNR = W > 0 ? W : 1;
+    const size_t nq = (n + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    INA_BLK_QUAD_LOOP(nq) {
+        const size_t i = base_ + lane, e = 4 * i;
+        [[maybe_unused]] f32x4 v[HOLD ? W : 1];
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) v[w] = ld4(in.p[w], e, n);
+        }
+        int k = 0;
+        if constexpr (AUTO) {
+            uint32_t m = 0u;
+            if constexpr (HOLD) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) m = fold4(m, v[w]);
+            } else {
+                for (int w = 0; w < nw; ++w) m = fold4(m, ld4(in.p[w], e, n));
+            }
+            m = group_max(m, 1 << shift);
+            k = scale_of(m, lim);
+            if (e < n && (lane & ((1 << shift) - 1)) == 0) kblk[i >> shift] = (int8_t)k;
+        } else {
+            if (e < n) k = rd_k(kblk, i >> shift);
+        }
+        const float s = pow2f(k);
+        u32x4 acc = {0u, 0u, 0u, 0u};
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) acc += q32x4(v[w], s);
+        } else {
+#pragma unroll UNR
+            for (int w = 0; w < nw; ++w) acc += q32x4(ld4(in.p[w], e, n), s);
+        }
+        if (e < n) st4(acc, out, e, n);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlk) void k_dq_blk(const T* __restrict__ sv, const int8_t* __restrict__ kblk,
+                                                 float* __restrict__ y, size_t n, int shift) {
+    const size_t nq = (n + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    INA_BLK_QUAD_LOOP(nq) {
+        const size_t i = base_ + lane, e = 4 * i;
+        if (e >= n) continue;
+        u32x4 q;
+        if constexpr (sizeof(T) == 4) q = ld4i(sv, e, n);
+        else q = ld4h(sv, e, n);
+        st4(deq4(q, pow2f(-rd_k(kblk, i >> shift))), y, e, n);
+    }
+}
+
+__global__ __launch_bounds__(kBlk) void k_ps_apply_blk(const float* local, const int32_t* __restrict__ sum,
+                                                       const int8_t* __restrict__ kblk, float ws, float* out,
+                                                       size_t n, int shift) {
+    const size_t nq = (n + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    INA_BLK_QUAD_LOOP(nq) {
+        const size_t i = base_ + lane, e = 4 * i;
+        if (e >= n) continue;
+        const f32x4 l = ld4<false>(local, e, n);
+        const u32x4 q = ld4i(sum, e, n);
+        st4(upd4(l, deq4(q, pow2f(-rd_k(kblk, i >> shift))), ws), out, e, n);
+    }
+}
+
+// INA update in one pass, scales on the fly from the W deltas (degree = W, bits = 32)
+template <int W>
+__global__ __launch_bounds__(kBlk) void k_ps_combine_ina_blk(const float* local, PtrPack<float> paras, int Wd,
+                                                             double lim, float ws, float* out, size_t n,
+                                                             int shift, int8_t* __restrict__ kblk) {
+    const int nw = W > 0 ? W : Wd;
+    const size_t nq = (n + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    INA_BLK_QUAD_LOOP(nq) {
+        const size_t i = base_ + lane, e = 4 * i;
+        const f32x4 l = ld4<false>(local, e, n);
+        [[maybe_unused]] f32x4 d[W > 0 ? W : 1];
+        uint32_t m = 0u;
+        if constexpr (W > 0) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) d[w] = ld4(paras.p[w], e, n);
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                d[w] = sub4(d[w], l);
+                m = fold4(m, d[w]);
+            }
+        } else {
+            for (int w = 0; w < nw; ++w) m = fold4(m, sub4(ld4(paras.p[w], e, n), l));
+        }
+        m = group_max(m, 1 << shift);
+        const int k = scale_of(m, lim);
+        if (kblk && e < n && (lane & ((1 << shift) - 1)) == 0) kblk[i >> shift] = (int8_t)k;
+        const float s = pow2f(k);
+        u32x4 acc = {0u, 0u, 0u, 0u};
+        if constexpr (W > 0) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) acc += q32x4(d[w], s);
+        } else {
+            for (int w = 0; w < nw; ++w) acc += q32x4(sub4(ld4(paras.p[w], e, n), l), s);
+        }
+        if (e < n) st4(upd4(l, deq4(acc, pow2f(-k)), ws), out, e, n);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// vector path, int16 out: a wave owns 512 values, lane l the 4 at 4l of each 256-value half
+// ---------------------------------------------------------------------------
+template <int W, bool AUTO>
+__global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<float> in, int Wd, int8_t* __restrict__ kblk,
+                                                     double lim, int16_t* __restrict__ out, size_t n, int shift,
+                                                     int V, uint8_t* __restrict__ ovf) {
+    const int nw = W > 0 ? W : Wd;
+    constexpr bool HOLD = AUTO && W > 0;
+    constexpr int UNR = W > 0 ? W : 1;
+    const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
+    const size_t nwaves = ((size_t)gridDim.x * kBlk) >> 6;
+    const int lane = (int)(tid & 63), lanes = 1 << shift;
+    const size_t nreg = (n + 511) / 512;
+    for (size_t r = tid >> 6; r < nreg; r += nwaves) {          // wave-uniform
+        const size_t eA = r * 512 + 4 * (size_t)lane, eB = eA + 256;
+        [[maybe_unused]] f32x4 u[HOLD ? W : 1], v[HOLD ? W : 1];
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                u[w] = ld4(in.p[w], eA, n);
+                v[w] = ld4(in.p[w], eB, n);
+            }
+        }
+        int kA = 0, kB = 0;
+        if constexpr (AUTO) {
+            uint32_t mA = 0u, mB = 0u;
+            if constexpr (HOLD) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    mA = fold4(mA, u[w]);
+                    mB = fold4(mB, v[w]);
+                }
+            } else {
+                for (int w = 0; w < nw; ++w) {
+                    mA = fold4(mA, ld4(in.p[w], eA, n));
+                    mB = fold4(mB, ld4(in.p[w], eB, n));
+                }
+            }
+            mA = group_max(mA, lanes);
+            mB = group_max(mB, lanes);
+            kA = scale_of(mA, lim);
+            kB = scale_of(mB, lim);
+            if ((lane & (lanes - 1)) == 0) {
+                if (eA < n) kblk[eA >> (shift + 2)] = (int8_t)kA;
+                if (eB < n) kblk[eB >> (shift + 2)] = (int8_t)kB;
+            }
+        } else {
+            if (eA < n) kA = rd_k(kblk, eA >> (shift + 2));
+            if (eB < n) kB = rd_k(kblk, eB >> (shift + 2));
+        }
+        const float sA = pow2f(kA), sB = pow2f(kB);
+        bool sa = false, sb = false;
+        int32_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                q16x4_add(u[w], sA, a, sa);
+                q16x4_add(v[w], sB, b, sb);
+            }
+        } else {
+#pragma unroll UNR
+            for (int w = 0; w < nw; ++w) {
+                q16x4_add(ld4(in.p[w], eA, n), sA, a, sa);
+                q16x4_add(ld4(in.p[w], eB, n), sB, b, sb);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            a[j] = sat16(a[j], sa);
+            b[j] = sat16(b[j], sb);
+        }
+        if (eA < n) st4h(a, out, eA, n);
+        if (eB < n) st4h(b, out, eB, n);
+        const unsigned long long ma = __ballot(sa), mb = __ballot(sb);   // wave-convergent
+        if (ovf) {
+            write_slot_flags8(ma, eA < n, eA, V, lanes, ovf);
+            write_slot_flags8(mb, eB < n, eB, V, lanes, ovf);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// scalar path: any V, any alignment.  One wave per block (wave-uniform block loop), lanes
+// striding over the block's values; one kernel for every entry point.
+// ---------------------------------------------------------------------------
+enum { S_SCALES, S_Q32, S_Q16, S_DQ32, S_DQ16, S_APPLY, S_COMB };
+struct ScalarArgs {
+    PtrPack<float> in;     // worker buffers (S_SCALES, S_Q32, S_Q16, S_COMB)
+    int W;
+    const float* base;     // S_SCALES: base or null; S_APPLY, S_COMB: local
+    const void* src;       // S_DQ32, S_DQ16, S_APPLY: the integers
+    int8_t* kblk;          // read (GIVEN) or written (AUTO; may be null for S_COMB)
+    double lim;
+    void* out;
+    size_t n;
+    size_t V;
+    uint8_t* ovf;
+    float ws;
+};
+
+template <int MODE, bool AUTO>
+__global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs a) {
+    const size_t wave = ((size_t)blockIdx.x * kBlk + threadIdx.x) >> 6;
+    const size_t nwaves = ((size_t)gridDim.x * kBlk) >> 6;
+    const int lane = threadIdx.x & 63;
+    const size_t nblk = (a.n + a.V - 1) / a.V;
+    constexpr bool kDelta = MODE == S_SCALES || MODE == S_COMB;     // values are in[w][j] - base[j]
+    for (size_t s = wave; s < nblk; s += nwaves) {                  // wave-uniform
+        const size_t j0 = s * a.V, j1 = (j0 + a.V < a.n) ? j0 + a.V : a.n;
+        int k;
+        if constexpr (AUTO) {
+            uint32_t m = 0u;
+            for (size_t j = j0 + lane; j < j1; j += 64)
+                for (int w = 0; w < a.W; ++w) {
+                    const float x = a.in.p[w][j];
+                    m = umax(m, absbits((kDelta && a.base) ? __fsub_rn(x, a.base[j]) : x));
+                }
+            m = group_max(m, 64);
+            k = scale_of(m, a.lim);
+            if (lane == 0 && a.kblk) a.kblk[s] = (int8_t)k;
+        } else {
+            k = rd_k(a.kblk, s);
+        }
+        if constexpr (MODE == S_SCALES) continue;
+        [[maybe_unused]] const float sc = pow2f(k), inv = pow2f(-k);
+        [[maybe_unused]] bool sat = false;
+        for (size_t j = j0 + lane; j < j1; j += 64) {
+            if constexpr (MODE == S_Q32) {
+                uint32_t acc = 0u;
+                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(a.in.p[w][j], sc);
+                static_cast<int32_t*>(a.out)[j] = (int32_t)acc;
+            } else if constexpr (MODE == S_Q16) {
+                int32_t acc = 0;
+                for (int w = 0; w < a.W; ++w) acc += q16(a.in.p[w][j], sc, sat);
+                static_cast<int16_t*>(a.out)[j] = (int16_t)sat16(acc, sat);
+            } else if constexpr (MODE == S_DQ32) {
+                static_cast<float*>(a.out)[j] = __fmul_rn((float)static_cast<const int32_t*>(a.src)[j], inv);
+            } else if constexpr (MODE == S_DQ16) {
+                static_cast<float*>(a.out)[j] = __fmul_rn((float)static_cast<const int16_t*>(a.src)[j], inv);
+            } else if constexpr (MODE == S_APPLY) {
+                const float y = __fmul_rn((float)static_cast<const int32_t*>(a.src)[j], inv);
+                static_cast<float*>(a.out)[j] = __fadd_rn(a.base[j], __fmul_rn(y, a.ws));
+            } else {
+                const float l = a.base[j];
+                uint32_t acc = 0u;
+                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(__fsub_rn(a.in.p[w][j], l), sc);
+                const float y = __fmul_rn((float)(int32_t)acc, inv);
+                static_cast<float*>(a.out)[j] = __fadd_rn(l, __fmul_rn(y, a.ws));
+            }
+        }
+        if constexpr (MODE == S_Q16) {
+            const unsigned long long m = __ballot(sat);               // wave-convergent
+            if (a.ovf && lane == 0) a.ovf[s] = m ? 1 : 0;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+inline unsigned grid_of(size_t items, int cap) {
+    size_t g = (items + kBlk - 1) / kBlk;
+    if (g > (size_t)cap) g = (size_t)cap;             // grid-stride beyond
+    return g ? (unsigned)g : 1u;
+}
+inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline hipStream_t hs(ina_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// the vector path's block sizes; shift = log2(V) - 2
+inline bool vec_v(int V, int& shift) {
+    if (V < 8 || V > 256 || (V & (V - 1))) return false;
+    shift = 0;
+    while ((4 << shift) < V) ++shift;
+    return true;
+}
+int check_v(int V) { return V < 1 ? set_error(INA_EINVAL, "V must be >= 1%s", "") : INA_OK; }
+// ina_scale_for's rule for the number of summands
+int scale_lim(int degree, int bits, double& lim) {
+    if (bits != 16 && bits != 32) return set_error(INA_EINVAL, "bits must be 16 or 32%s", "");
+    if (degree < 1) return set_error(INA_EINVAL, "degree must be >= 1%s", "");
+    lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)degree - 0.5;
+    if (lim <= 0.0) return set_error(INA_EINVAL, "too many summands (degree) for this width%s", "");
+    return INA_OK;
+}
+int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) {
+    lim = 1.0;
+    if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
+        return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
+    if (mode == INA_BLK_AUTO) {
+        if (int rc = scale_lim(degree, bits, lim)) return rc;
+    }
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    return INA_OK;
+}
+int fill(PtrPack<float>& pk, const float* const* bufs, int W, bool& all_aligned) {
+    if (!bufs || W < 1 || W > INA_MAX_WORKERS) return set_error(INA_EINVAL, "W must be in [1, %s]", "64");
+    all_aligned = true;
+    for (int w = 0; w < W; ++w) {
+        if (!bufs[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
+        pk.p[w] = bufs[w];
+        all_aligned &= al16(bufs[w]);
+    }
+    for (int w = W; w < INA_MAX_WORKERS; ++w) pk.p[w] = nullptr;
+    return INA_OK;
+}
+int launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? INA_OK : set_error(INA_EHIP, "block-scale kernel launch: %s", hipGetErrorString(e));
+}
+
+template <int MODE, bool AUTO>
+void launch_scalar(const ScalarArgs& a, hipStream_t s) {
+    const size_t nblk = (a.n + a.V - 1) / a.V;
+    hipLaunchKernelGGL((k_blk_scalar<MODE, AUTO>), dim3(grid_of(nblk * 64, default_grid_cap())), dim3(kBlk), 0, s, a);
+}
+
+// compile-time worker counts of the fused kernels (others: the runtime-W instance)
+#define INA_BLK_W_SWITCH(W, LAUNCH) \
+    switch (W) {                    \
+        case 1: LAUNCH(1); break;   \
+        case 2: LAUNCH(2); break;   \
+        case 4: LAUNCH(4); break;   \
+        case 8: LAUNCH(8); break;   \
+        case 16: LAUNCH(16); break; \
+        default: LAUNCH(0);         \
+    }
+
+int reduce_i32(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int32_t* out, size_t n,
+               ina_stream_t stream) {
+    double lim;
+    if (int rc = check_v(V)) return rc;
+    if (int rc = check_mode(mode, kblk, degree, 32, lim)) return rc;
+    if (n == 0) return INA_OK;
+    PtrPack<float> pk;
+    bool al;
+    if (int rc = fill(pk, bufs, W, al)) return rc;
+    if (!out) return set_error(INA_EINVAL, "null out%s", "");
+    hipStream_t s = hs(stream);
+    const bool autok = mode == INA_BLK_AUTO;
+    int shift;
+    if (vec_v(V, shift) && al && al16(out)) {
+        // the sibling's grids: covering for W <= 8, the streaming cap beyond
+        const dim3 g(grid_of((n + 3) / 4, W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
+#define L(WW)                                                                                              \
+    do {                                                                                                   \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<WW, true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift); \
+        else hipLaunchKernelGGL((k_qr_blk_i32<WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift);   \
+    } while (0)
+        INA_BLK_W_SWITCH(W, L)
+#undef L
+    } else {
+        ScalarArgs a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
+        if (autok) launch_scalar<S_Q32, true>(a, s);
+        else launch_scalar<S_Q32, false>(a, s);
+    }
+    return launched();
+}
+
+int reduce_i16(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int16_t* out, size_t n,
+               uint8_t* ovf, ina_stream_t stream) {
+    double lim;
+    if (int rc = check_v(V)) return rc;
+    if (int rc = check_mode(mode, kblk, degree, 16, lim)) return rc;
+    if (n == 0) return INA_OK;
+    PtrPack<float> pk;
+    bool al;
+    if (int rc = fill(pk, bufs, W, al)) return rc;
+    if (!out) return set_error(INA_EINVAL, "null out%s", "");
+    hipStream_t s = hs(stream);
+    const bool autok = mode == INA_BLK_AUTO;
+    int shift;
+    if (vec_v(V, shift) && al && al16(out)) {
+        const dim3 g(grid_of((n + 511) / 512 * 64, default_grid_cap())), b(kBlk);
+#define L(WW)                                                                                                       \
+    do {                                                                                                            \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<(WW <= 8 ? WW : 0), true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf); \
+        else hipLaunchKernelGGL((k_qr_blk_i16<WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf);    \
+    } while (0)
+        INA_BLK_W_SWITCH(W, L)
+#undef L
+    } else {
+        ScalarArgs a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
+        if (autok) launch_scalar<S_Q16, true>(a, s);
+        else launch_scalar<S_Q16, false>(a, s);
+    }
+    return launched();
+}
+
+}  // namespace
+}  // namespace ina
+
+using namespace ina;
+
+extern "C" {
+
+int ina_block_scales_f32(const float* const* xs, int W, const float* base, size_t n, int V, int degree, int bits,
+                         int8_t* kblk, ina_stream_t stream) {
+    double lim;
+    if (int rc = check_v(V)) return rc;
+    if (int rc = scale_lim(degree, bits, lim)) return rc;
+    if (n == 0) return INA_OK;
+    PtrPack<float> pk;
+    bool al;
+    if (int rc = fill(pk, xs, W, al)) return rc;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    hipStream_t s = hs(stream);
+    int shift;
+    if (vec_v(V, shift) && al && (!base || al16(base))) {
+        hipLaunchKernelGGL(k_blk_scales, dim3(grid_of((n + 3) / 4, stream_grid_cap())), dim3(kBlk), 0, s, pk, W, base,
+                           n, shift, lim, kblk);
+    } else {
+        ScalarArgs a{pk, W, base, nullptr, kblk, lim, nullptr, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_SCALES, true>(a, s);
+    }
+    return launched();
+}
+
+int ina_quantize_blk_f32_i32(const float* x, const int8_t* kblk, int V, int32_t* q, size_t n, ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    const float* one[1] = {x};
+    return reduce_i32(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, stream);
+}
+
+int ina_quantize_blk_f32_i16_sat(const float* x, const int8_t* kblk, int V, int16_t* q, size_t n, uint8_t* ovf,
+                                 ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    const float* one[1] = {x};
+    return reduce_i16(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, ovf, stream);
+}
+
+int ina_quantize_reduce_blk_f32_i32(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V,
+                                    int32_t* out, size_t n, ina_stream_t stream) {
+    return reduce_i32(bufs, W, kblk, mode, degree, V, out, n, stream);
+}
+
+int ina_quantize_reduce_blk_f32_i16_sat(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V,
+                                        int16_t* out, size_t n, uint8_t* ovf, ina_stream_t stream) {
+    return reduce_i16(bufs, W, kblk, mode, degree, V, out, n, ovf, stream);
+}
+
+int ina_dequantize_blk_i32_f32(const int32_t* sv, const int8_t* kblk, int V, float* y, size_t n,
+                               ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    int shift;
+    if (vec_v(V, shift) && al16(sv) && al16(y)) {
+        hipLaunchKernelGGL(k_dq_blk<int32_t>, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
+                           kblk, y, n, shift);
+    } else {
+        ScalarArgs a{{}, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_DQ32, false>(a, hs(stream));
+    }
+    return launched();
+}
+
+int ina_dequantize_blk_i16_f32(const int16_t* sv, const int8_t* kblk, int V, float* y, size_t n,
+                               ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    int shift;
+    if (vec_v(V, shift) && ((uintptr_t)sv % 8 == 0) && al16(y)) {
+        hipLaunchKernelGGL(k_dq_blk<int16_t>, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
+                           kblk, y, n, shift);
+    } else {
+        ScalarArgs a{{}, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_DQ16, false>(a, hs(stream));
+    }
+    return launched();
+}
+
+int ina_ps_apply_blk_i32(const float* local, const int32_t* sum_int, const int8_t* kblk, int V, double weight_step,
+                         float* out, size_t n, ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!local || !sum_int || !out || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    int shift;
+    if (vec_v(V, shift) && al16(local) && al16(sum_int) && al16(out)) {
+        hipLaunchKernelGGL(k_ps_apply_blk, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), local,
+                           sum_int, kblk, (float)weight_step, out, n, shift);
+    } else {
+        ScalarArgs a{{}, 0, local, sum_int, const_cast<int8_t*>(kblk), 1.0, out, n, (size_t)V, nullptr,
+                     (float)weight_step};
+        launch_scalar<S_APPLY, false>(a, hs(stream));
+    }
+    return launched();
+}
+
+int ina_ps_combine_ina_blk_f32(const float* local, const float* const* paras, int W, int V, double weight_step,
+                               float* out, size_t n, int8_t* kblk_out, ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    PtrPack<float> pk;
+    bool al;
+    if (int rc = fill(pk, paras, W, al)) return rc;
+    if (!local || !out) return set_error(INA_EINVAL, "null pointer%s", "");
+    double lim;
+    if (int rc = scale_lim(W, 32, lim)) return rc;
+    hipStream_t s = hs(stream);
+    const float ws = (float)weight_step;
+    int shift;
+    if (vec_v(V, shift) && al && al16(local) && al16(out)) {
+        const dim3 g(grid_of((n + 3) / 4, kCombineGrid)), b(kBlk);
+#define L(WW) hipLaunchKernelGGL(k_ps_combine_ina_blk<WW>, g, b, 0, s, local, pk, W, lim, ws, out, n, shift, kblk_out)
+        INA_BLK_W_SWITCH(W, L)
+#undef L
+    } else {
+        ScalarArgs a{pk, W, local, nullptr, kblk_out, lim, out, n, (size_t)V, nullptr, ws};
+        launch_scalar<S_COMB, true>(a, s);
+    }
+    return launched();
+}
+
+}  // extern "C"
+
+#if INA_STORE_CHECK
+namespace ina {
+unsigned long long store_violations_blk() {
+    unsigned long long v = 0, z = 0;
+    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
+        return ~0ull;                                  // unreadable: report as a violation
+    return v;
+}
+}  // namespace ina
+#endif

@@ -39,6 +39,7 @@ unsigned long long store_violations_kernels();   // ina_kernels.hip
 unsigned long long store_violations_shard();     // ina_shard.hip
 unsigned long long store_violations_switch();    // ina_switch.hip
 unsigned long long store_violations_x16();       // ina_x16.hip
+unsigned long long store_violations_blk();       // ina_blk.hip
 
 }  // namespace ina
 

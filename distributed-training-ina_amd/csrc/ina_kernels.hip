@@ -2708,7 +2708,7 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (!count) return INA_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
-             ina::store_violations_x16();
+             ina::store_violations_x16() + ina::store_violations_blk();
     return INA_OK;
 }
 #endif

@@ -127,6 +127,19 @@ SIGNATURES_X16 = {
     "ina_dequantize_i32_x16": [_vp, _vp, _i, _sz, _i, _vp],
     "ina_dequantize_i16_x16": [_vp, _vp, _i, _sz, _i, _vp],
 }
+# the per-block-scale entry points (include/ina_blk.h), bound like the ones above
+BLK_GIVEN, BLK_AUTO = 0, 1
+SIGNATURES_BLK = {
+    "ina_block_scales_f32": [_vp, _i, _vp, _sz, _i, _i, _i, _vp, _vp],
+    "ina_quantize_blk_f32_i32": [_vp, _vp, _i, _vp, _sz, _vp],
+    "ina_quantize_blk_f32_i16_sat": [_vp, _vp, _i, _vp, _sz, _vp, _vp],
+    "ina_quantize_reduce_blk_f32_i32": [_vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp],
+    "ina_quantize_reduce_blk_f32_i16_sat": [_vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp],
+    "ina_dequantize_blk_i32_f32": [_vp, _vp, _i, _vp, _sz, _vp],
+    "ina_dequantize_blk_i16_f32": [_vp, _vp, _i, _vp, _sz, _vp],
+    "ina_ps_apply_blk_i32": [_vp, _vp, _vp, _i, _d, _vp, _sz, _vp],
+    "ina_ps_combine_ina_blk_f32": [_vp, _vp, _i, _i, _d, _vp, _sz, _vp, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -141,7 +154,7 @@ def open_library(path: str) -> C.CDLL:
     if not os.path.exists(path):
         raise InaError(f"libina.so not built at {path}; run `make -C {CSRC}` or __graft_entry__.build()")
     lib = C.CDLL(path)
-    for name, args in {**SIGNATURES, **SIGNATURES_X16}.items():
+    for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -14,6 +14,7 @@ These are the kernels that replace the reference's CPU / switch arithmetic:
   pack_c128                  send_gradients' packet loop (communicator.cc:23-37)
   ps_combine                 aggregate() (launch.py:42-52)
   absmax / scale_for         per-bucket dynamic scale for the quantiser (build-defined)
+  block_scales / *_blk       one scale per block of V values instead (include/ina_blk.h)
 """
 from __future__ import annotations
 
@@ -758,6 +759,204 @@ def scale_for_workers(xs, base: torch.Tensor | None = None, bits: int = 32) -> i
     xs = list(xs)
     m = absmax_multi(xs, base)
     return scale_for(float(m.item()), len(xs), bits)
+
+
+# -- per-block scales (include/ina_blk.h) -------------------------------------------------------
+def _blk_v(V) -> int:
+    V = int(V)
+    if V < 1:
+        raise ValueError("V must be >= 1")
+    return V
+
+
+def _blk_f32(t, name: str):
+    """Block scales take fp32 buckets: a bf16 / fp16 tensor is refused as such."""
+    if isinstance(t, torch.Tensor) and t.dtype in _X16:
+        raise ValueError(f"block scales take fp32 buckets: {name} is {t.dtype}")
+    _req(t, torch.float32, name)
+
+
+def _blk_bufs(bufs, name="bufs"):
+    if isinstance(bufs, torch.Tensor):
+        bufs = list(bufs.unbind(0)) if bufs.dim() > 1 else [bufs]
+    bufs = list(bufs)
+    for i, b in enumerate(bufs):
+        if isinstance(b, torch.Tensor) and b.dtype in _X16:
+            raise ValueError(f"block scales take fp32 buckets: {name}[{i}] is {b.dtype}")
+    return _bufs(bufs, torch.float32, name)
+
+
+def _blk_scales_arg(kblk, nblk: int, ref: torch.Tensor, name: str = "kblk", given: bool = False):
+    """A scale array: int8, one entry per block, on ref's device (None: a new one, unless the
+    call reads it)."""
+    if kblk is None and not given:
+        return torch.empty(nblk, dtype=torch.int8, device=ref.device)
+    _req(kblk, torch.int8, name)
+    _fits(kblk, nblk, name)
+    _same_device(ref, kblk)
+    return kblk
+
+
+def _blk_degree(degree, W: int, bits: int) -> int:
+    degree = W if degree is None else int(degree)
+    if bits not in (16, 32):
+        raise ValueError("bits must be 16 or 32")
+    if degree < 1 or ((1 << (bits - 1)) - 1) / degree - 0.5 <= 0:
+        raise ValueError(f"degree {degree} cannot be summed at {bits} bits")
+    return degree
+
+
+def block_scales(xs, V: int, bits: int = 32, degree: int | None = None, base: torch.Tensor | None = None,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """int8 [ceil(n / V)]: for each block of V values the k that ina_scale_for gives for the
+    block's max |xs[w][i] - base[i]| over the given buckets, `degree` summands (default: the
+    number of buckets) and `bits`.  All zero / all NaN: 127; a block holding inf: -126.  Ranks
+    of one job agree on a block's scale by taking the MIN of theirs."""
+    V = _blk_v(V)
+    if degree is not None:
+        _blk_degree(degree, 0, bits)
+    xs, n = _blk_bufs(xs, "xs")
+    degree = _blk_degree(degree, len(xs), bits)
+    if base is not None:
+        _blk_f32(base, "base")
+        if base.numel() != n:
+            raise ValueError("base and xs differ in length")
+        _same_device(xs[0], base)
+    out = _blk_scales_arg(out, (n + V - 1) // V, xs[0], "out")
+    check(load().ina_block_scales_f32(ptr_array([x.data_ptr() for x in xs]), len(xs),
+                                      base.data_ptr() if base is not None else None, n, V, degree, bits,
+                                      out.data_ptr(), _stream(xs[0])), "block_scales")
+    return out
+
+
+def quantize_blk(x: torch.Tensor, kblk: torch.Tensor, V: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """quantize() with block s scaled by 2^kblk[s]."""
+    V = _blk_v(V)
+    _blk_f32(x, "x")
+    kblk = _blk_scales_arg(kblk, (x.numel() + V - 1) // V, x, given=True)
+    out = torch.empty(x.shape, dtype=torch.int32, device=x.device) if out is None else out
+    _fits(out, x.numel())
+    _req(out, torch.int32, "out")
+    check(load().ina_quantize_blk_f32_i32(x.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), x.numel(), _stream(x)),
+          "quantize_blk")
+    return out
+
+
+def quantize_i16_blk(x: torch.Tensor, kblk: torch.Tensor, V: int, out=None, overflow=None):
+    """quantize_i16() with block s scaled by 2^kblk[s]; the overflow flags are per block."""
+    V = _blk_v(V)
+    _blk_f32(x, "x")
+    nblk = (x.numel() + V - 1) // V
+    kblk = _blk_scales_arg(kblk, nblk, x, given=True)
+    out = torch.empty(x.shape, dtype=torch.int16, device=x.device) if out is None else out
+    _fits(out, x.numel())
+    overflow = torch.empty(nblk, dtype=torch.uint8, device=x.device) if overflow is None else overflow
+    _fits(overflow, nblk, "overflow")
+    _req(out, torch.int16, "out")
+    _req(overflow, torch.uint8, "overflow")
+    check(load().ina_quantize_blk_f32_i16_sat(x.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), x.numel(),
+                                              overflow.data_ptr(), _stream(x)), "quantize_i16_blk")
+    return out, overflow
+
+
+def quantize_reduce_blk(bufs, V: int, kblk: torch.Tensor | None = None, degree: int | None = None,
+                        out: torch.Tensor | None = None, kblk_out: torch.Tensor | None = None):
+    """quantize_reduce() with per-block scales: returns (out, kblk).  kblk=None computes the
+    scales in the same pass from these buckets for `degree` summands (default: their number)
+    and returns them (in kblk_out when given); a given kblk is read."""
+    V = _blk_v(V)
+    bufs, n = _blk_bufs(bufs)
+    nblk = (n + V - 1) // V
+    mode = _lib.BLK_AUTO if kblk is None else _lib.BLK_GIVEN
+    degree = _blk_degree(degree, len(bufs), 32) if kblk is None else 1
+    kblk = _blk_scales_arg(kblk if kblk is not None else kblk_out, nblk, bufs[0])
+    out = torch.empty(n, dtype=torch.int32, device=bufs[0].device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int32, "out")
+    arr = ptr_array([b.data_ptr() for b in bufs])
+    check(load().ina_quantize_reduce_blk_f32_i32(arr, len(bufs), kblk.data_ptr(), mode, degree, V, out.data_ptr(), n,
+                                                 _stream(out)), "quantize_reduce_blk")
+    return out, kblk
+
+
+def quantize_reduce_i16_blk(bufs, V: int, kblk: torch.Tensor | None = None, degree: int | None = None,
+                            out=None, overflow=None, kblk_out: torch.Tensor | None = None):
+    """quantize_reduce_i16() with per-block scales: returns (out, overflow, kblk); kblk as in
+    quantize_reduce_blk (computed for the int16 width)."""
+    V = _blk_v(V)
+    bufs, n = _blk_bufs(bufs)
+    nblk, dev = (n + V - 1) // V, bufs[0].device
+    mode = _lib.BLK_AUTO if kblk is None else _lib.BLK_GIVEN
+    degree = _blk_degree(degree, len(bufs), 16) if kblk is None else 1
+    kblk = _blk_scales_arg(kblk if kblk is not None else kblk_out, nblk, bufs[0])
+    out = torch.empty(n, dtype=torch.int16, device=dev) if out is None else out
+    _fits(out, n)
+    overflow = torch.empty(nblk, dtype=torch.uint8, device=dev) if overflow is None else overflow
+    _req(out, torch.int16, "out")
+    _req(overflow, torch.uint8, "overflow")
+    _fits(overflow, nblk, "overflow")
+    arr = ptr_array([b.data_ptr() for b in bufs])
+    check(load().ina_quantize_reduce_blk_f32_i16_sat(arr, len(bufs), kblk.data_ptr(), mode, degree, V,
+                                                     out.data_ptr(), n, overflow.data_ptr(), _stream(out)),
+          "quantize_reduce_i16_blk")
+    return out, overflow, kblk
+
+
+def dequantize_blk(s: torch.Tensor, kblk: torch.Tensor, V: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """y = float(s) * 2^-kblk[block] as float32; s: int32 or int16."""
+    V = _blk_v(V)
+    if not isinstance(s, torch.Tensor) or s.dtype not in (torch.int32, torch.int16):
+        raise TypeError("s must be an int32 or int16 tensor")
+    if out is not None and isinstance(out, torch.Tensor) and out.dtype in _X16:
+        raise ValueError(f"block scales take fp32 buckets: out is {out.dtype}")
+    _req(s, s.dtype, "s")
+    kblk = _blk_scales_arg(kblk, (s.numel() + V - 1) // V, s, given=True)
+    out = torch.empty(s.shape, dtype=torch.float32, device=s.device) if out is None else out
+    _fits(out, s.numel())
+    _req(out, torch.float32, "out")
+    fn = load().ina_dequantize_blk_i16_f32 if s.dtype == torch.int16 else load().ina_dequantize_blk_i32_f32
+    check(fn(s.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), s.numel(), _stream(s)), "dequantize_blk")
+    return out
+
+
+def ps_apply_blk(local: torch.Tensor, sum_int: torch.Tensor, kblk: torch.Tensor, V: int, weight_step: float,
+                 out=None):
+    """ps_apply() with per-block scales: local + float(weight_step) * dequantize_blk(sum_int)."""
+    V = _blk_v(V)
+    _blk_f32(local, "local")
+    _req(sum_int, torch.int32, "sum_int")
+    if sum_int.numel() != local.numel():
+        raise ValueError("local and sum_int differ in length")
+    kblk = _blk_scales_arg(kblk, (local.numel() + V - 1) // V, local, given=True)
+    out = torch.empty_like(local) if out is None else out
+    _fits(out, local.numel())
+    _req(out, torch.float32, "out")
+    check(load().ina_ps_apply_blk_i32(local.data_ptr(), sum_int.data_ptr(), kblk.data_ptr(), V, float(weight_step),
+                                      out.data_ptr(), local.numel(), _stream(local)), "ps_apply_blk")
+    return out
+
+
+def ps_combine_ina_blk(local: torch.Tensor, paras, V: int, weight_step: float, out=None,
+                       kblk_out: torch.Tensor | None = None):
+    """The INA update with per-block scales computed on the device in the same pass
+    (ina_ps_combine_ina_blk_f32): no host read.  kblk_out (int8, one per block) receives the
+    scales when given."""
+    V = _blk_v(V)
+    _blk_f32(local, "local")
+    paras, n = _blk_bufs(paras, "paras")
+    if n != local.numel():
+        raise ValueError("local and paras differ in length")
+    _same_device(local, paras[0])
+    out = torch.empty_like(local) if out is None else out
+    _fits(out, n)
+    _req(out, torch.float32, "out")
+    if kblk_out is not None:
+        kblk_out = _blk_scales_arg(kblk_out, (n + V - 1) // V, local, "kblk_out")
+    arr = ptr_array([p.data_ptr() for p in paras])
+    check(load().ina_ps_combine_ina_blk_f32(local.data_ptr(), arr, len(paras), V, float(weight_step),
+                                            out.data_ptr(), n, kblk_out.data_ptr() if kblk_out is not None else None,
+                                            _stream(local)), "ps_combine_ina_blk")
+    return out
 
 
 # -- device packet-stream switch ---------------------------------------------------------------

@@ -11,7 +11,9 @@ and meaning of launch.py:42-52 (sync: weight 1/(W+1)) and launch_async.py:42-57
                          the switch's Processor add -- and dequantised into the
                          update (ina_ps_combine_ina_f32), one pass over HBM;
                          k="auto" picks the largest non-saturating scale from the
-                         deltas' absmax (ops.scale_for_workers).
+                         deltas' absmax (ops.scale_for_workers); k="block" picks it
+                         per block of `block` values on the device, in the same pass
+                         (no host read).
 
 Worker.updated_paras may be CPU tensors (unpickled from the worker socket,
 worker.py:78) or device tensors; CPU ones are staged through pinned memory.  The global
@@ -52,7 +54,8 @@ def _staged(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
 
 
 def aggregate(global_model, worker_list, step_size, worker_num: int | None = None,
-              mode: str = "fp32", k: int | str = 16, device: str | torch.device | None = None):
+              mode: str = "fp32", k: int | str = 16, device: str | torch.device | None = None,
+              block: int = 256):
     home = _device_of(global_model)
     if home.type == "cuda":
         dev = home
@@ -73,7 +76,7 @@ def aggregate(global_model, worker_list, step_size, worker_num: int | None = Non
     if mode == "fp32":
         out = ops.ps_combine(local, paras, ws)
     elif mode == "ina":
-        out = combine_ina(local, paras, k, ws)
+        out = combine_ina(local, paras, k, ws, block=block)
     else:
         raise ValueError(f"unknown mode {mode!r}")
     if home.type != "cuda":                          # back into the CPU parameters
@@ -84,11 +87,17 @@ def aggregate(global_model, worker_list, step_size, worker_num: int | None = Non
     return out
 
 
-def combine_ina(local: torch.Tensor, paras, k, weight_step: float, out=None):
+def combine_ina(local: torch.Tensor, paras, k, weight_step: float, out=None, block: int = 256):
     """local + float(weight_step) * dequant(sum_w q(paras[w] - local)) on the GPU.
     k="auto": the largest scale at which no delta and no W-way sum saturates
-    (ops.scale_for_workers over the deltas; one host read)."""
+    (ops.scale_for_workers over the deltas; one host read).
+    k="block": that scale per block of `block` values, computed on the device in the same
+    pass (ina_ps_combine_ina_blk_f32): one enqueue, no host read."""
     from . import _lib
+    if isinstance(k, str) and k not in ("auto", "block"):
+        raise ValueError(f"unknown k {k!r}: an int, \"auto\" or \"block\"")
+    if k == "block":
+        return ops.ps_combine_ina_blk(local, paras, block, weight_step, out=out)
     ops._req(local, torch.float32, "local")
     paras, n = ops._bufs(paras, torch.float32, "paras")
     if k == "auto":

@@ -289,6 +289,10 @@ int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npkts, i
  *     produced, not flushed.
  * The declarations are in ina_x16.h, included here (it needs the packet types above). */
 #include "ina_x16.h"   /* INA_X16_BF16 / INA_X16_F16 and the ina_*_x16_* entry points */
+/* ---- per-block scales -----------------------------------------------------------
+ * One exponent per block of V values (block floating point) for the quantiser, the fused
+ * reduces and the PS update; the contract is stated in ina_blk.h. */
+#include "ina_blk.h"   /* INA_BLK_GIVEN / INA_BLK_AUTO and the ina_*_blk_* entry points */
 
 /* C-128 pack (communicator.cc:23-37): npkts x 524-byte packet_t, all words htonl. */
 int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,

@@ -44,7 +44,6 @@ using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
 using f32x4 = float __attribute__((ext_vector_type(4)));
 
 constexpr int kBlk = 256;
-constexpr int kCombineGrid = 8192;   // the INA combine's grid cap (ina_ps_combine_ina_f32)
 
 // ---------------------------------------------------------------------------
 // scales
@@ -738,7 +737,7 @@ int ina_ps_combine_ina_blk_f32(const float* local, const float* const* paras, in
     const float ws = (float)weight_step;
     int shift;
     if (vec_v(V, shift) && al && al16(local) && al16(out)) {
-        const dim3 g(grid_of((n + 3) / 4, kCombineGrid)), b(kBlk);
+        const dim3 g(grid_of((n + 3) / 4, combine_ina_grid_cap())), b(kBlk);
 #define L(WW) hipLaunchKernelGGL(k_ps_combine_ina_blk<WW>, g, b, 0, s, local, pk, W, lim, ws, out, n, shift, kblk_out)
         INA_BLK_W_SWITCH(W, L)
 #undef L

@@ -32,6 +32,7 @@ int set_decide_delay(int v);  // ina_switch.hip
 int ew_grid_cap();            // ina_kernels.hip: grid cap of the elementwise kernels (tuning key 14)
 int default_grid_cap();       // ina_kernels.hip: grid cap of the default-cap kernels (tuning key 0)
 int stream_grid_cap();        // ina_kernels.hip: grid cap of the flat packet kernels (tuning key 4)
+int combine_ina_grid_cap();   // ina_kernels.hip: grid cap of the INA combines, blk one included (tuning key 6)
 int check_x16_type(int xtype);   // ina_x16.hip: INA_OK for INA_X16_BF16 / INA_X16_F16, else INA_EINVAL
 // checked builds (INA_STORE_CHECK, ina_device.h): each source's stream_store contract
 // violations since the last read, cleared by the read

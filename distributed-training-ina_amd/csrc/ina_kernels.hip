@@ -100,6 +100,7 @@ int stream_grid_cap() { return g_stream_blocks.load(); }
 // the INA combine (quantiser in the loop) with one chunk in flight at 8192
 static std::atomic<int> g_combine_blocks{256};
 static std::atomic<int> g_combine_ina_blocks{8192};
+int combine_ina_grid_cap() { return g_combine_ina_blocks.load(); }
 static std::atomic<int> g_nontemporal{1};
 // flat packet kernels index 16-byte chunks in 32 bits: a launch covers at most this many
 // chunks and longer batches go in packet ranges (tunable so tests reach the split path)

@@ -39,9 +39,9 @@
 namespace ina {
 namespace {
 
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using u32x4 = u32x4_t;
+using u32x2 = u32x2_t;
+using f32x4 = f32x4_t;
 
 constexpr int kBlk = 256;
 
@@ -490,14 +490,6 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-inline unsigned grid_of(size_t items, int cap) {
-    size_t g = (items + kBlk - 1) / kBlk;
-    if (g > (size_t)cap) g = (size_t)cap;             // grid-stride beyond
-    return g ? (unsigned)g : 1u;
-}
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-inline hipStream_t hs(ina_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
 // the vector path's block sizes; shift = log2(V) - 2
 inline bool vec_v(int V, int& shift) {
     if (V < 8 || V > 256 || (V & (V - 1))) return false;
@@ -524,21 +516,7 @@ int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) 
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     return INA_OK;
 }
-int fill(PtrPack<float>& pk, const float* const* bufs, int W, bool& all_aligned) {
-    if (!bufs || W < 1 || W > INA_MAX_WORKERS) return set_error(INA_EINVAL, "W must be in [1, %s]", "64");
-    all_aligned = true;
-    for (int w = 0; w < W; ++w) {
-        if (!bufs[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
-        pk.p[w] = bufs[w];
-        all_aligned &= al16(bufs[w]);
-    }
-    for (int w = W; w < INA_MAX_WORKERS; ++w) pk.p[w] = nullptr;
-    return INA_OK;
-}
-int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? INA_OK : set_error(INA_EHIP, "block-scale kernel launch: %s", hipGetErrorString(e));
-}
+int launched() { return check_launch("block-scale kernel launch"); }
 
 template <int MODE, bool AUTO>
 void launch_scalar(const ScalarArgs& a, hipStream_t s) {
@@ -565,12 +543,12 @@ int reduce_i32(const float* const* bufs, int W, int8_t* kblk, int mode, int degr
     if (n == 0) return INA_OK;
     PtrPack<float> pk;
     bool al;
-    if (int rc = fill(pk, bufs, W, al)) return rc;
+    if (int rc = fill_pack(pk, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
-    if (vec_v(V, shift) && al && al16(out)) {
+    if (vec_v(V, shift) && al && aligned16(out)) {
         // the sibling's grids: covering for W <= 8, the streaming cap beyond
         const dim3 g(grid_of((n + 3) / 4, W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
 #define L(WW)                                                                                              \
@@ -596,12 +574,12 @@ int reduce_i16(const float* const* bufs, int W, int8_t* kblk, int mode, int degr
     if (n == 0) return INA_OK;
     PtrPack<float> pk;
     bool al;
-    if (int rc = fill(pk, bufs, W, al)) return rc;
+    if (int rc = fill_pack(pk, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
-    if (vec_v(V, shift) && al && al16(out)) {
+    if (vec_v(V, shift) && al && aligned16(out)) {
         const dim3 g(grid_of((n + 511) / 512 * 64, default_grid_cap())), b(kBlk);
 #define L(WW)                                                                                                       \
     do {                                                                                                            \
@@ -633,11 +611,11 @@ int ina_block_scales_f32(const float* const* xs, int W, const float* base, size_
     if (n == 0) return INA_OK;
     PtrPack<float> pk;
     bool al;
-    if (int rc = fill(pk, xs, W, al)) return rc;
+    if (int rc = fill_pack(pk, xs, W, al)) return rc;
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     hipStream_t s = hs(stream);
     int shift;
-    if (vec_v(V, shift) && al && (!base || al16(base))) {
+    if (vec_v(V, shift) && al && (!base || aligned16(base))) {
         hipLaunchKernelGGL(k_blk_scales, dim3(grid_of((n + 3) / 4, stream_grid_cap())), dim3(kBlk), 0, s, pk, W, base,
                            n, shift, lim, kblk);
     } else {
@@ -680,7 +658,7 @@ int ina_dequantize_blk_i32_f32(const int32_t* sv, const int8_t* kblk, int V, flo
     if (n == 0) return INA_OK;
     if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
     int shift;
-    if (vec_v(V, shift) && al16(sv) && al16(y)) {
+    if (vec_v(V, shift) && aligned16(sv) && aligned16(y)) {
         hipLaunchKernelGGL(k_dq_blk<int32_t>, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
                            kblk, y, n, shift);
     } else {
@@ -696,7 +674,7 @@ int ina_dequantize_blk_i16_f32(const int16_t* sv, const int8_t* kblk, int V, flo
     if (n == 0) return INA_OK;
     if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
     int shift;
-    if (vec_v(V, shift) && ((uintptr_t)sv % 8 == 0) && al16(y)) {
+    if (vec_v(V, shift) && ((uintptr_t)sv % 8 == 0) && aligned16(y)) {
         hipLaunchKernelGGL(k_dq_blk<int16_t>, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
                            kblk, y, n, shift);
     } else {
@@ -712,7 +690,7 @@ int ina_ps_apply_blk_i32(const float* local, const int32_t* sum_int, const int8_
     if (n == 0) return INA_OK;
     if (!local || !sum_int || !out || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
     int shift;
-    if (vec_v(V, shift) && al16(local) && al16(sum_int) && al16(out)) {
+    if (vec_v(V, shift) && aligned16(local) && aligned16(sum_int) && aligned16(out)) {
         hipLaunchKernelGGL(k_ps_apply_blk, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), local,
                            sum_int, kblk, (float)weight_step, out, n, shift);
     } else {
@@ -729,14 +707,14 @@ int ina_ps_combine_ina_blk_f32(const float* local, const float* const* paras, in
     if (n == 0) return INA_OK;
     PtrPack<float> pk;
     bool al;
-    if (int rc = fill(pk, paras, W, al)) return rc;
+    if (int rc = fill_pack(pk, paras, W, al)) return rc;
     if (!local || !out) return set_error(INA_EINVAL, "null pointer%s", "");
     double lim;
     if (int rc = scale_lim(W, 32, lim)) return rc;
     hipStream_t s = hs(stream);
     const float ws = (float)weight_step;
     int shift;
-    if (vec_v(V, shift) && al && al16(local) && al16(out)) {
+    if (vec_v(V, shift) && al && aligned16(local) && aligned16(out)) {
         const dim3 g(grid_of((n + 3) / 4, combine_ina_grid_cap())), b(kBlk);
 #define L(WW) hipLaunchKernelGGL(k_ps_combine_ina_blk<WW>, g, b, 0, s, local, pk, W, lim, ws, out, n, shift, kblk_out)
         INA_BLK_W_SWITCH(W, L)
@@ -751,13 +729,5 @@ int ina_ps_combine_ina_blk_f32(const float* local, const float* const* paras, in
 }  // extern "C"
 
 #if INA_STORE_CHECK
-namespace ina {
-unsigned long long store_violations_blk() {
-    unsigned long long v = 0, z = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
-        return ~0ull;                                  // unreadable: report as a violation
-    return v;
-}
-}  // namespace ina
+unsigned long long ina::store_violations_blk() { return take_store_violations(); }
 #endif

@@ -49,6 +49,14 @@ constexpr int kAuxSC1 = 16;
 #endif
 #if INA_STORE_CHECK
 static __device__ unsigned long long g_store_violations;   // one per source file
+// host: this source's count since the last read, cleared by the read
+static inline unsigned long long take_store_violations() {
+    unsigned long long v = 0, z = 0;
+    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
+        return ~0ull;                                  // unreadable: report as a violation
+    return v;
+}
 #endif
 template <typename T>
 __device__ __forceinline__ void stream_store(T v, T* p) {

@@ -1,7 +1,13 @@
-// ina_internal.h -- shared between the libina.so translation units (not installed).
+// ina_internal.h -- shared between the libina.so translation units (not installed): the
+// cross-source declarations, then the one copy of the small host helpers every entry point
+// uses (stream cast, alignment and scale checks, grids, worker-pointer packs, launch check).
 #pragma once
+#include <hip/hip_runtime_api.h>
+
 #include <cstddef>
 #include <cstdint>
+#include <string>
+#include <type_traits>
 
 #include "ina.h"
 
@@ -18,17 +24,9 @@ int set_h2d_streams(int v);   // ina_host.cpp
 int set_zero_copy(int v);     // ina_host.cpp
 int sum_reduce_i32_impl(const int32_t* const* bufs, int W, int32_t* out, size_t n, ina_stream_t stream,
                         bool host);   // ina_kernels.hip
-int set_small_sort(int v);    // ina_switch.hip
-int set_switch_win(int v);    // ina_switch.hip
-int set_ack_fast(int v);      // ina_switch.hip
-int set_sort_mode(int v);     // ina_switch.hip
-int set_os_rounds(int v);     // ina_switch.hip
-int set_tiny_max(int v);      // ina_switch.hip
-int set_bucket_tile(int v);   // ina_switch.hip
-int set_runs(int v);          // ina_switch.hip
-int set_pre_all(int v);       // ina_switch.hip
-int set_local(int v);         // ina_switch.hip
-int set_decide_delay(int v);  // ina_switch.hip
+// ina_switch.hip: the switch keys of ina_set_tuning (9-13, 15, 17-21; the table g_switch_keys);
+// INA_EINVAL for a key that is not the switch's or a value the key refuses
+int set_switch_tuning(int key, int value);
 int ew_grid_cap();            // ina_kernels.hip: grid cap of the elementwise kernels (tuning key 14)
 int default_grid_cap();       // ina_kernels.hip: grid cap of the default-cap kernels (tuning key 0)
 int stream_grid_cap();        // ina_kernels.hip: grid cap of the flat packet kernels (tuning key 4)
@@ -41,6 +39,60 @@ unsigned long long store_violations_shard();     // ina_shard.hip
 unsigned long long store_violations_switch();    // ina_switch.hip
 unsigned long long store_violations_x16();       // ina_x16.hip
 unsigned long long store_violations_blk();       // ina_blk.hip
+
+// ---------------------------------------------------------------------------
+// host helpers
+// ---------------------------------------------------------------------------
+constexpr int kHostBlock = 256;   // threads per workgroup of every kernel these grids are for
+
+inline hipStream_t hs(ina_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// 256-thread workgroups covering `items`, at most `cap` (the kernels grid-stride beyond), at least 1
+inline unsigned grid_of(size_t items, int cap) {
+    size_t g = (items + kHostBlock - 1) / kHostBlock;
+    if (g > (size_t)cap) g = (size_t)cap;
+    return g ? (unsigned)g : 1u;
+}
+// the same with `per_thread` items a thread, under the default cap (tuning key 0) unless overridden
+inline unsigned grid_for(size_t work_items, int per_thread, int cap_override = 0) {
+    size_t per_block = (size_t)kHostBlock * (size_t)per_thread;
+    size_t blocks = (work_items + per_block - 1) / per_block;
+    size_t cap = (size_t)(cap_override > 0 ? cap_override : default_grid_cap());
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    return (unsigned)blocks;
+}
+
+inline int check_k(int k) {
+    if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
+    return INA_OK;
+}
+
+// after a launch: INA_OK, or INA_EHIP with "<what>: <the runtime's error string>"
+inline int check_launch(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return INA_OK;
+    return set_error(INA_EHIP, "%s", (std::string(what) + ": " + hipGetErrorString(e)).c_str());
+}
+
+// the W worker pointers into a pack; B = void: untyped 16-bit buffers (include/ina_x16.h), refused
+// unless 2-byte aligned
+template <typename T, typename B>
+int fill_pack(PtrPack<T>& pk, const B* const* bufs, int W, bool& all_aligned) {
+    if (!bufs || W < 1 || W > INA_MAX_WORKERS) return set_error(INA_EINVAL, "W must be in [1, %s]", "64");
+    all_aligned = true;
+    for (int w = 0; w < W; ++w) {
+        if (!bufs[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
+        if constexpr (std::is_void_v<B>) {
+            if ((uintptr_t)bufs[w] & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
+        }
+        pk.p[w] = static_cast<const T*>(bufs[w]);
+        all_aligned &= aligned16(bufs[w]);
+    }
+    for (int w = W; w < INA_MAX_WORKERS; ++w) pk.p[w] = nullptr;
+    return INA_OK;
+}
 
 }  // namespace ina
 

@@ -29,11 +29,11 @@
 
 namespace ina {
 
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using u32x4 = u32x4_t;
+using u32x2 = u32x2_t;
+using f32x4 = f32x4_t;
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kHostBlock;
 
 // ---------------------------------------------------------------------------
 // error reporting
@@ -43,15 +43,6 @@ static thread_local char g_err[256] = "";
 int set_error(int code, const char* fmt, const char* detail) {
     snprintf(g_err, sizeof g_err, fmt, detail ? detail : "");
     return code;
-}
-
-static int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-        return INA_EHIP;
-    }
-    return INA_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -105,17 +96,6 @@ static std::atomic<int> g_nontemporal{1};
 // flat packet kernels index 16-byte chunks in 32 bits: a launch covers at most this many
 // chunks and longer batches go in packet ranges (tunable so tests reach the split path)
 static std::atomic<int64_t> g_launch_chunks{0x7FFFFFFF};
-
-static inline unsigned grid_for(size_t work_items, int per_thread, int cap_override = 0) {
-    size_t per_block = (size_t)kBlock * (size_t)per_thread;
-    size_t blocks = (work_items + per_block - 1) / per_block;
-    size_t cap = (size_t)(cap_override > 0 ? cap_override : g_max_blocks.load());
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    return (unsigned)blocks;
-}
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // grid cap of the reductions that finish with one atomic per workgroup on one word
 constexpr int kFaninBlocks = 256;
@@ -1899,27 +1879,6 @@ __global__ __launch_bounds__(kBlock) void k_absmax_multi_f32(PtrPack<float> xs, 
 // ===========================================================================
 using namespace ina;
 
-static inline hipStream_t hs(ina_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-static int check_k(int k) {
-    if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
-    return INA_OK;
-}
-
-template <typename T>
-static int fill_pack(PtrPack<T>& pk, const T* const* bufs, int W, bool& all_aligned) {
-    if (!bufs || W < 1 || W > INA_MAX_WORKERS)
-        return set_error(INA_EINVAL, "W must be in [1, %s]", "64");
-    all_aligned = true;
-    for (int w = 0; w < W; ++w) {
-        if (!bufs[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
-        pk.p[w] = bufs[w];
-        all_aligned &= aligned16(bufs[w]);
-    }
-    for (int w = W; w < INA_MAX_WORKERS; ++w) pk.p[w] = nullptr;
-    return INA_OK;
-}
-
 template <typename Src>
 static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina_nga_params_t* prm,
                            const uint8_t* ovf, uint8_t* pkts, size_t pstride, hipStream_t s,
@@ -1990,22 +1949,13 @@ int ina_set_tuning(int key, int value) {
         case 14: if (value < 1) return INA_EINVAL; g_ew_blocks = value; return INA_OK;
         case 5: if (value < 1) return INA_EINVAL; g_combine_blocks = value; return INA_OK;
         case 6: if (value < 1) return INA_EINVAL; g_combine_ina_blocks = value; return INA_OK;
-        case 10: return set_switch_win(value);
+#else
+        case 10: return INA_EINVAL;
 #endif
         case 7: return set_h2d_streams(value);
         case 8: if (value < 1) return INA_EINVAL; g_launch_chunks = value; return INA_OK;
-        case 9: return set_small_sort(value);
-        case 11: return set_ack_fast(value);
-        case 12: return set_sort_mode(value);
-        case 13: return set_os_rounds(value);
-        case 15: return set_tiny_max(value);
         case 16: return set_zero_copy(value);
-        case 17: return set_bucket_tile(value);
-        case 18: return set_runs(value);
-        case 19: return set_pre_all(value);
-        case 20: return set_local(value);
-        case 21: return set_decide_delay(value);
-        default: return INA_EINVAL;
+        default: return set_switch_tuning(key, value);   // the switch keys (ina_switch.hip), else INA_EINVAL
     }
 }
 
@@ -2691,15 +2641,7 @@ int ina_checksum_i32(const int32_t* x, size_t n, uint32_t* out_dev, ina_stream_t
 }  // extern "C"
 
 #if INA_STORE_CHECK
-namespace ina {
-unsigned long long store_violations_kernels() {
-    unsigned long long v = 0, z = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
-        return ~0ull;                                  // unreadable: report as a violation
-    return v;
-}
-}  // namespace ina
+unsigned long long ina::store_violations_kernels() { return take_store_violations(); }
 #endif
 
 #if INA_STORE_CHECK

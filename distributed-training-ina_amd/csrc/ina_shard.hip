@@ -31,11 +31,11 @@
 namespace ina {
 namespace {
 
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using u32x4 = u32x4_t;
+using u32x2 = u32x2_t;
+using f32x4 = f32x4_t;
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kHostBlock;
 constexpr int kWireShift = INA_I16_WIRE_SHIFT;   // 22
 constexpr int32_t kWireHalf = 1 << (kWireShift - 1);
 
@@ -142,12 +142,6 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_scalar(const int32_t* 
     }
 }
 
-inline unsigned grid_of(size_t items) {
-    size_t g = (items + kBlk - 1) / kBlk;
-    const size_t cap = (size_t)ew_grid_cap();       // the elementwise kernels' cap (tuning key 14)
-    if (g > cap) g = cap;                           // grid-stride beyond
-    return g ? (unsigned)g : 1u;
-}
 inline bool al(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
@@ -158,51 +152,41 @@ using namespace ina;
 extern "C" {
 
 int ina_quantize_f32_i16_wire(const float* x, int32_t* wire, size_t n, int k, ina_stream_t stream) {
-    if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
+    if (int rc = check_k(k)) return rc;
     if (n == 0) return INA_OK;
     if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
     const int vec = al(x, 16) && al(wire, 16);
-    hipLaunchKernelGGL(k_quantize_i16_wire, dim3(grid_of(vec ? n / 4 + 1 : n)), dim3(kBlk), 0,
-                       reinterpret_cast<hipStream_t>(stream), x, wire, n, ldexpf(1.0f, k), vec);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? INA_OK : set_error(INA_EHIP, "quantize_i16_wire: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(k_quantize_i16_wire, dim3(grid_of(vec ? n / 4 + 1 : n, ew_grid_cap())), dim3(kBlk), 0,
+                       hs(stream), x, wire, n, ldexpf(1.0f, k), vec);
+    return check_launch("quantize_i16_wire");
 }
 
 int ina_i16_wire_finish(const int32_t* wire_sum, size_t n, int k, int V, int16_t* out16, float* y,
                         uint8_t* overflow_per_slot, ina_stream_t stream) {
-    if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
+    if (int rc = check_k(k)) return rc;
     if (V <= 0) return set_error(INA_EINVAL, "V must be > 0%s", "");
     if (n == 0) return INA_OK;
     if (!wire_sum) return set_error(INA_EINVAL, "null pointer%s", "");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = hs(stream);
     const float inv = ldexpf(1.0f, -k);
     const int l = V / 4;
     const bool ballot = V % 4 == 0 && l >= 1 && l <= 64 && (l & (l - 1)) == 0;
     const bool vec = al(wire_sum, 16) && (!out16 || al(out16, 8)) && (!y || al(y, 16));
     if (vec && (ballot || !overflow_per_slot)) {
-        hipLaunchKernelGGL(k_i16_wire_finish_vec, dim3(grid_of((n + 3) / 4)), dim3(kBlk), 0, s,
+        hipLaunchKernelGGL(k_i16_wire_finish_vec, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, s,
                            wire_sum, n, inv, ballot ? l : 1, V, out16, y, overflow_per_slot);
     } else {
         if (overflow_per_slot &&
             hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
             return set_error(INA_EHIP, "memset overflow flags%s", "");
-        hipLaunchKernelGGL(k_i16_wire_finish_scalar, dim3(grid_of(n)), dim3(kBlk), 0, s, wire_sum, n,
+        hipLaunchKernelGGL(k_i16_wire_finish_scalar, dim3(grid_of(n, ew_grid_cap())), dim3(kBlk), 0, s, wire_sum, n,
                            inv, V, out16, y, overflow_per_slot);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? INA_OK : set_error(INA_EHIP, "i16_wire_finish: %s", hipGetErrorString(e));
+    return check_launch("i16_wire_finish");
 }
 
 }  // extern "C"
 
 #if INA_STORE_CHECK
-namespace ina {
-unsigned long long store_violations_shard() {
-    unsigned long long v = 0, z = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
-        return ~0ull;                                  // unreadable: report as a violation
-    return v;
-}
-}  // namespace ina
+unsigned long long ina::store_violations_shard() { return take_store_violations(); }
 #endif

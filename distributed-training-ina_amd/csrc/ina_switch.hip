@@ -28,8 +28,8 @@
 
 namespace ina {
 
-using u32x4s = uint32_t __attribute__((ext_vector_type(4)));
-using f32x4s = float __attribute__((ext_vector_type(4)));
+using u32x4s = u32x4_t;
+using f32x4s = f32x4_t;
 
 constexpr int kSwBlock = 256;               // 4 waves, one slot segment each
 constexpr int kMaxV = 256;                  // 4 payload words per lane
@@ -334,88 +334,17 @@ constexpr int kSmallBatch = 4096;                 // LDS capacity of the one-wor
 #endif
 static_assert(INA_SWITCH_SMALL_MAX <= kSmallBatch, "small path limited by its LDS");
 constexpr int kSmallBlock = 1024;
-// ina_set_tuning key 9: the largest batch the one-workgroup sort takes (0: never; 1: the
-// default, INA_SWITCH_SMALL_DEFAULT; 2..INA_SWITCH_SMALL_MAX: that many packets).  Above
-// ~700 packets the bucket sort is faster (tiny_lab: 1,024 packets 26.6 vs 25.2 us, 2,048
-// 37.5 vs 25.3; 512: 23.1 vs 24.0 -- profiles/r02/lab/tiny_lab.log)
+// the largest batch the one-workgroup sort takes by default (ina_set_tuning key 9, g_switch_keys)
 #ifndef INA_SWITCH_SMALL_DEFAULT
 #define INA_SWITCH_SMALL_DEFAULT 768
 #endif
-static std::atomic<int> g_small_sort{INA_SWITCH_SMALL_DEFAULT};
 #ifndef INA_SWITCH_TINY_MAX
 #define INA_SWITCH_TINY_MAX 128                // one-launch path (k_switch_tiny) up to this many packets (tiny_lab: break-even ~150)
 #endif
-static std::atomic<int> g_switch_win{0};   // ina_set_tuning key 10: run-kernel window (0: auto)
-static std::atomic<int> g_ack_fast{1};     // ina_set_tuning key 11: lone-ack lane path (0: off)
-// ina_set_tuning key 12, the slot sort: 0 auto (chunk + bucket sort for keys of one or two
-// digits, else the LSD digit passes), 3 the digit passes for every batch (the cross-check the
-// tests run both ways).  The one-sweep and round-2 bucket + local variants moved to tools/lab
-// (DESIGN.md section 4).
-static std::atomic<int> g_sort_mode{0};
-static std::atomic<int> g_os_rounds{0};    // ina_set_tuning key 13: sort chunk rounds (0 auto, 4/8/16)
-static std::atomic<uint32_t> g_sort_epoch{0};   // per-call tag of the chunk sort's "unsorted" flag
-static std::atomic<int> g_runs{1};         // ina_set_tuning key 18: dense-run batches skip the sort (0: off)
-int set_runs(int v) {
-    g_runs = v ? 1 : 0;
-    return INA_OK;
-}
-static std::atomic<int> g_local{1};        // ina_set_tuning key 20: near-sorted batches skip the sort (0: off)
-int set_local(int v) {
-    g_local = v ? 1 : 0;
-    return INA_OK;
-}
-// ina_set_tuning key 21 (tests): block 0 of the decision pass waits this many microseconds
-// before it decides, so every other block's bounded wait for the near-sorted verdict runs out
-// and it sorts its chunk anyway -- the shape of a block 0 dispatched late (0: off, the default)
-static std::atomic<int> g_decide_delay{0};
-int set_decide_delay(int v) {
-    if (v < 0 || v > 100000) return INA_EINVAL;
-    g_decide_delay = v;
-    return INA_OK;
-}
-// ina_set_tuning key 19: the split chunk pass (detection, decision, then digits) for every key
-// width (1, default) or for keys of 19-22 bits only (0).  Interleaved over packed and split
-// rows at 819,200 NGA-256 packets (tools/lab/switch_pre_lab.py, profiles/r04/lab): worker-
-// major -3.8 / -3.2 us, round-robin -6.1 / -5.4 us, a shuffled batch +5.6 / +4.9 us (it pays
-// the detection pass and one launch more); NIC arrival is structured, so split by default
 #ifndef INA_SWITCH_PRE_ALL
-#define INA_SWITCH_PRE_ALL 1
+#define INA_SWITCH_PRE_ALL 1                   // ina_set_tuning key 19's default (g_switch_keys)
 #endif
-static std::atomic<int> g_pre_all{INA_SWITCH_PRE_ALL};
-int set_pre_all(int v) {
-    g_pre_all = v ? 1 : 0;
-    return INA_OK;
-}
-int set_sort_mode(int v) {
-    if (v != 0 && v != 3) return INA_EINVAL;
-    g_sort_mode = v;
-    return INA_OK;
-}
-int set_os_rounds(int v) {
-    if (v != 0 && v != 4 && v != 8 && v != 16) return INA_EINVAL;
-    g_os_rounds = v;
-    return INA_OK;
-}
-int set_ack_fast(int v) {
-    g_ack_fast = v ? 1 : 0;
-    return INA_OK;
-}
-int set_switch_win(int v) {
-    if (v < 0 || v > 64) return INA_EINVAL;
-    g_switch_win = v;
-    return INA_OK;
-}
-static std::atomic<int> g_tiny_max{INA_SWITCH_TINY_MAX};   // ina_set_tuning key 15 (0: off)
-int set_tiny_max(int v) {
-    if (v < 0 || v > INA_SWITCH_SMALL_MAX) return INA_EINVAL;
-    g_tiny_max = v;
-    return INA_OK;
-}
-int set_small_sort(int v) {
-    if (v < 0 || v > INA_SWITCH_SMALL_MAX) return INA_EINVAL;
-    g_small_sort = v == 1 ? INA_SWITCH_SMALL_DEFAULT : v;
-    return INA_OK;
-}
+static std::atomic<uint32_t> g_sort_epoch{0};   // per-call tag of the chunk sort's "unsorted" flag
 
 // T = uint32_t packs (slot << 12 | id) when num_slots + 1 <= 2^20, else uint64_t (slot << 32
 // | id).  Compare-exchange stages with j < 64 pair elements inside one wave's 64-element
@@ -634,13 +563,6 @@ constexpr int kBkMaxChunks = 2048;                  // B's LDS rows: up to 2048 
 constexpr int kLcRounds = 4;
 constexpr int kLcRoundsBig = 8;
 constexpr size_t kBigTileAvg = (size_t)kBkWaves * 64 * kLcRounds * 7 / 8;   // 3,584 items
-static std::atomic<int> g_bucket_tile{0};   // ina_set_tuning key 17: 0 auto, 4 or 8 rounds
-int set_bucket_tile(int v) {
-    if (v != 0 && v != kLcRounds && v != kLcRoundsBig) return INA_EINVAL;
-    g_bucket_tile = v;
-    return INA_OK;
-}
-
 // The switch keys one batch runs under, read ONCE per call.  A sort-only call (phase 1)
 // records its snapshot with the scratch it filled (g_sorts), and the run over that scratch
 // (phase 2) follows the record, never the live keys: a thread that tunes between another
@@ -650,10 +572,80 @@ struct SwitchTuning {
     int small_sort, tiny_max, sort_mode, os_rounds, runs, local, pre_all, ack_fast, win, bucket_tile,
         decide_delay;
 };
+
+// what a key stores for a value, -1: refused
+template <int LO, int HI>
+static int key_range(int v) { return v < LO || v > HI ? -1 : v; }
+template <int... A>
+static int key_one_of(int v) { return ((v == A) || ...) ? v : -1; }
+static int key_flag(int v) { return v ? 1 : 0; }
+
+// The switch's ina_set_tuning keys: the key, its field of the snapshot, what it stores for a value
+// and its live value (the default until set).  set_switch_tuning and switch_tuning() both walk
+// this table and nothing else lists the keys.
+struct SwitchKey {
+    int key;
+    int SwitchTuning::*field;
+    int (*stored)(int);
+    std::atomic<int> value;
+};
+static SwitchKey g_switch_keys[] = {
+    // key 9: the largest batch the one-workgroup sort takes (0: never; 1: the
+    // default, INA_SWITCH_SMALL_DEFAULT; 2..INA_SWITCH_SMALL_MAX: that many packets).  Above
+    // ~700 packets the bucket sort is faster (tiny_lab: 1,024 packets 26.6 vs 25.2 us, 2,048
+    // 37.5 vs 25.3; 512: 23.1 vs 24.0 -- profiles/r02/lab/tiny_lab.log)
+    {9, &SwitchTuning::small_sort,
+     [](int v) { return v == 1 ? INA_SWITCH_SMALL_DEFAULT : key_range<0, INA_SWITCH_SMALL_MAX>(v); },
+     INA_SWITCH_SMALL_DEFAULT},
+    // key 10 (lab builds only, gated in ina_set_tuning): run-kernel window (0: auto)
+    {10, &SwitchTuning::win, key_range<0, 64>, 0},
+    // key 11: lone-ack lane path (0: off)
+    {11, &SwitchTuning::ack_fast, key_flag, 1},
+    // key 12, the slot sort: 0 auto (chunk + bucket sort for keys of one or two
+    // digits, else the LSD digit passes), 3 the digit passes for every batch (the cross-check the
+    // tests run both ways).  The one-sweep and round-2 bucket + local variants moved to tools/lab
+    // (DESIGN.md section 4).
+    {12, &SwitchTuning::sort_mode, key_one_of<0, 3>, 0},
+    // key 13: sort chunk rounds (0 auto, 4/8/16)
+    {13, &SwitchTuning::os_rounds, key_one_of<0, 4, 8, 16>, 0},
+    // key 15: the one-launch path (k_switch_tiny) up to this many packets (0: off)
+    {15, &SwitchTuning::tiny_max, key_range<0, INA_SWITCH_SMALL_MAX>, INA_SWITCH_TINY_MAX},
+    // key 17: the bucket pass's tile, 0 auto, 4 or 8 rounds
+    {17, &SwitchTuning::bucket_tile, key_one_of<0, kLcRounds, kLcRoundsBig>, 0},
+    // key 18: dense-run batches skip the sort (0: off)
+    {18, &SwitchTuning::runs, key_flag, 1},
+    // key 19: the split chunk pass (detection, decision, then digits) for every key
+    // width (1, default) or for keys of 19-22 bits only (0).  Interleaved over packed and split
+    // rows at 819,200 NGA-256 packets (tools/lab/switch_pre_lab.py, profiles/r04/lab): worker-
+    // major -3.8 / -3.2 us, round-robin -6.1 / -5.4 us, a shuffled batch +5.6 / +4.9 us (it pays
+    // the detection pass and one launch more); NIC arrival is structured, so split by default
+    {19, &SwitchTuning::pre_all, key_flag, INA_SWITCH_PRE_ALL},
+    // key 20: near-sorted batches skip the sort (0: off)
+    {20, &SwitchTuning::local, key_flag, 1},
+    // key 21 (tests): block 0 of the decision pass waits this many microseconds
+    // before it decides, so every other block's bounded wait for the near-sorted verdict runs out
+    // and it sorts its chunk anyway -- the shape of a block 0 dispatched late (0: off, the default)
+    {21, &SwitchTuning::decide_delay, key_range<0, 100000>, 0},
+};
+
+static_assert(sizeof(g_switch_keys) / sizeof(g_switch_keys[0]) == sizeof(SwitchTuning) / sizeof(int),
+              "one key per field of the snapshot");
+
+int set_switch_tuning(int key, int value) {
+    for (SwitchKey& k : g_switch_keys) {
+        if (k.key != key) continue;
+        const int v = k.stored(value);
+        if (v < 0) return INA_EINVAL;
+        k.value = v;
+        return INA_OK;
+    }
+    return INA_EINVAL;
+}
+
 static SwitchTuning switch_tuning() {
-    return SwitchTuning{g_small_sort.load(), g_tiny_max.load(), g_sort_mode.load(), g_os_rounds.load(),
-                        g_runs.load(),       g_local.load(),    g_pre_all.load(),   g_ack_fast.load(),
-                        g_switch_win.load(), g_bucket_tile.load(), g_decide_delay.load()};
+    SwitchTuning t{};
+    for (const SwitchKey& k : g_switch_keys) t.*k.field = k.value.load();
+    return t;
 }
 
 // key fields of R rounds of 64 packets (all loads issued first): slot index, switch id and
@@ -3741,13 +3733,15 @@ static SortPlan sort_plan(size_t npk, uint32_t num_slots, const SwitchTuning& t)
     return p;
 }
 
-// sort scratch after the four key / id arrays, sized for the SMALLEST chunk whatever tier
-// npk falls in (so the size is monotonic in npk: a buffer sized for a batch serves every
+// The switch scratch, in the order it is carved (switch_scratch, the ONE place that order is
+// written): the four key / id arrays, then the sort scratch, sized for the SMALLEST chunk whatever
+// tier npk falls in (so the size is monotonic in npk: a buffer sized for a batch serves every
 // smaller batch): per (digit, chunk) counts -- the digit passes' histogram, or A's run
 // lengths -- and A's run starts, the digit passes' digit totals, the control block (the
 // size of the foreign-only bucket B leaves out, the epochs, the run table) and A's per-chunk
 // breaks of the dense runs (count + kRunsMax entries per chunk)
-struct SortAux {
+struct SwitchScratch {
+    uint32_t *k_in, *k_out, *v_in, *v_out;   // [npk] each: keys and packet ids, ping and pong
     uint32_t* hist;               // [2^bits][nch]
     uint32_t* rst;                // [2^bits][nch]
     uint32_t* totals;             // [512]
@@ -3761,6 +3755,7 @@ struct SortAux {
     LocUnit* units;               // near-sorted path: per unit (>= 2 granules) its slot range and window
     uint2* tab;                   // near-sorted path: per slot (first list entry, length)
     uint32_t* kflags;             // per detection wave: the epoch of the call whose keys it stored
+    size_t end;                   // bytes from the aligned base to the end of the last array
 };
 
 static size_t sort_nch_cap(size_t npk) {
@@ -3773,32 +3768,41 @@ static size_t sort_hist_cap(size_t npk, uint32_t num_slots) {
     return ((size_t)1 << std::max(p.bits, p.hbits)) * sort_nch_cap(npk);
 }
 
-static size_t sort_temp_bytes(size_t npk, uint32_t num_slots) {
-    const size_t hist = align_up(sort_hist_cap(npk, num_slots) * 4, 256);
-    const size_t nc = sort_nch_cap(npk);
-    return 2 * hist + align_up((size_t)kRsBins * 4, 256) + 1024 + align_up(nc * 4, 256) +
-           align_up(nc * (size_t)kRunsMax * 8, 256) + align_up(2 * nc * kGranPerChunk * 4, 256) +
-           align_up(nc * (kGranPerChunk / 2) * sizeof(LocUnit), 256) + align_up((size_t)num_slots * 8, 256) +
-           nc * kBkWaves * 4;
-}
+// Bump carver over the caller's scratch: the base rounded up to 256 bytes, every array but the last
+// padded to a multiple of 256.  A null scratch carves nothing real and serves for sizing (`end`).
+struct Carver {
+    uintptr_t base;
+    size_t off = 0;
+    template <typename T>
+    T* take(size_t bytes, bool pad = true) {
+        T* p = reinterpret_cast<T*>(base + off);
+        off += pad ? align_up(bytes, 256) : bytes;
+        return p;
+    }
+};
 
-static SortAux sort_aux(uint8_t* aux, size_t npk, uint32_t num_slots) {
-    const size_t hist = align_up(sort_hist_cap(npk, num_slots) * 4, 256);
-    const size_t nc = sort_nch_cap(npk);
-    SortAux a;
-    a.hist = reinterpret_cast<uint32_t*>(aux);
-    a.rst = reinterpret_cast<uint32_t*>(aux + hist);
-    a.totals = reinterpret_cast<uint32_t*>(aux + 2 * hist);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(aux + 2 * hist + align_up((size_t)kRsBins * 4, 256));
-    a.nforeign = ctl + kCtlForeign;
-    a.unsorted = ctl + kCtlEpochs;
-    a.brk_cnt = ctl + 256;
-    a.brk_ent = reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(a.brk_cnt) + align_up(nc * 4, 256));
-    a.gstat = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.brk_ent) + align_up(nc * (size_t)kRunsMax * 8, 256));
-    a.units = reinterpret_cast<LocUnit*>(reinterpret_cast<uint8_t*>(a.gstat) + align_up(2 * nc * kGranPerChunk * 4, 256));
-    a.tab = reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(a.units) + align_up(nc * (kGranPerChunk / 2) * sizeof(LocUnit), 256));
-    a.kflags = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.tab) + align_up((size_t)num_slots * 8, 256));
-    return a;
+static SwitchScratch switch_scratch(const void* scratch, size_t npk, uint32_t num_slots) {
+    const size_t hist = sort_hist_cap(npk, num_slots) * 4, nc = sort_nch_cap(npk);
+    Carver c{align_up((uintptr_t)scratch, 256)};
+    SwitchScratch s;
+    s.k_in = c.take<uint32_t>(npk * 4);
+    s.k_out = c.take<uint32_t>(npk * 4);
+    s.v_in = c.take<uint32_t>(npk * 4);
+    s.v_out = c.take<uint32_t>(npk * 4);
+    s.hist = c.take<uint32_t>(hist);
+    s.rst = c.take<uint32_t>(hist);
+    s.totals = c.take<uint32_t>((size_t)kRsBins * 4);
+    uint32_t* ctl = c.take<uint32_t>(1024);                     // the control block: 256 words
+    s.nforeign = ctl + kCtlForeign;
+    s.unsorted = ctl + kCtlEpochs;
+    s.brk_cnt = c.take<uint32_t>(nc * 4);
+    s.brk_ent = c.take<uint2>(nc * (size_t)kRunsMax * 8);
+    s.gstat = c.take<uint32_t>(2 * nc * kGranPerChunk * 4);
+    s.units = c.take<LocUnit>(nc * (kGranPerChunk / 2) * sizeof(LocUnit));
+    s.tab = c.take<uint2>((size_t)num_slots * 8);
+    s.kflags = c.take<uint32_t>(nc * kBkWaves * 4, false);      // the last array: its size as it is
+    s.end = c.off;
+    return s;
 }
 
 // The sorts queued alone (phase 1), by scratch: the switch keys they ran under and the batch
@@ -3840,6 +3844,394 @@ static bool sort_record_find(const void* scratch, const SortRecord& want, Switch
         return false;
     *t = r.t;
     return true;
+}
+
+// ---------------------------------------------------------------------------
+// ina_switch on the host: a plan (every decision, no HIP call), one launch function per stage,
+// and the driver (switch_process_impl)
+// ---------------------------------------------------------------------------
+// sort chunk geometry (sort_plan): one instantiation per rounds-per-wave choice
+constexpr int kR0 = INA_RS_ROUNDS_SMALL, kR1 = INA_RS_ROUNDS_MID, kR2 = kRsRounds, kR3 = INA_RS_ROUNDS_BIG;
+static_assert(kR0 % 4 == 0 && kR1 % 4 == 0 && kR2 % 4 == 0 && kR3 % 4 == 0, "chunk sort: 16 waves x rounds/4");
+
+// f(integral_constant<int, rounds / 4>) for the plan's rounds tier: the chunk pass's instantiations
+template <typename F>
+static void with_chunk_rounds(int ri, F&& f) {
+    if (ri == 3) f(std::integral_constant<int, kR3 / 4>{});
+    else if (ri == 2) f(std::integral_constant<int, kR2 / 4>{});
+    else if (ri == 1) f(std::integral_constant<int, kR1 / 4>{});
+    else f(std::integral_constant<int, kR0 / 4>{});
+}
+
+enum SwitchPath {
+    kPathTiny,     // sort and run in ONE launch of one workgroup (k_switch_tiny)
+    kPathSmall,    // the one-workgroup sort (k_switch_sort_small), then the run
+    kPathBucket,   // chunk pass (A), bucket pass (B), the near-sorted lists, then the run
+    kPathDigits,   // LSD digit passes, then the run
+};
+
+struct SwitchPlan {
+    SortPlan sp;
+    SwitchPath path;
+    int ri;                      // rounds tier: sp.rounds == kR<ri>
+    bool fast;                   // the register-resident run kernels take the layout
+    bool ack_hint, small, bucket;
+    bool key32;                  // the one-workgroup sorts pack (slot << 12 | id) in 32 bits
+    // the bucket path's (false / 0 on every other path)
+    bool runs_on, loc, pre, drop_prefill, keys_from_desc, plain, big;
+    uint32_t loc_gsize;          // the near-sorted path's granule: 1/8 of a sort chunk
+    uint32_t delay_ticks, skip, CH;
+    // the run's
+    bool narrow;
+    uint32_t win;
+    // grids: chunk and digit passes, bucket pass, column scan, local lists, run
+    unsigned gc, gb, gd, gl, gr;
+    uint32_t nb;
+};
+
+// rows16: the rows are 16-byte aligned; desc / split / ps_on: the batch has descriptors, payload
+// rows, a PS step
+static SwitchPlan switch_plan(const ina_switch_state_t& st, size_t npk, size_t stride, bool rows16, bool desc,
+                              bool split, bool ps_on, int phase, const SwitchTuning& t) {
+    SwitchPlan p{};
+    const SortPlan& sp = p.sp = sort_plan(npk, st.num_slots, t);
+    p.ri = sp.rounds == kR0 ? 0 : sp.rounds == kR1 ? 1 : sp.rounds == kR2 ? 2 : 3;
+    p.gc = (unsigned)sp.nch;
+    p.nb = 1u << sp.bits;
+    p.gd = (p.nb + kRsWaves - 1) / kRsWaves;
+    p.fast = stride % 16 == 0 && rows16 && st.V % 4 == 0 && st.V <= kMaxV && aligned16(st.regs);
+    // keys carry the PS-ack bit for the run kernel when bit 31 is outside every digit
+    p.ack_hint = p.fast && sp.passes * sp.bits <= 31 && t.ack_fast;
+    p.small = npk <= (size_t)t.small_sort;
+    // chunk + bucket sort: keys of one or two digits (the low digit is one workgroup's LDS
+    // bins) and at most kBkMaxChunks chunks (B's LDS rows); else the digit passes (keys of three
+    // digits, batches beyond B's rows, or key 12 = 3)
+    p.bucket = !p.small && t.sort_mode == 0 && sp.bucket_ok && sp.nch <= (size_t)kBkMaxChunks;
+    p.path = p.small && p.fast && npk <= (size_t)t.tiny_max ? kPathTiny
+           : p.small                                        ? kPathSmall
+           : p.bucket                                       ? kPathBucket
+                                                            : kPathDigits;
+    p.key32 = (uint64_t)st.num_slots + 1 <= (1u << 20);
+    p.skip = 0xFFFFFFFFu;
+    if (p.path == kPathBucket) {
+        const int lb = sp.lbits;                           // low digit bits (0: one-digit keys)
+        // dense ascending runs skip the sort (run table, switch_runs_body): the register-
+        // resident run kernel only (ina_set_tuning key 18 = 0 turns it off)
+        p.runs_on = p.fast && t.runs != 0;
+        // near-sorted batches (local disorder) skip the sort and run from per-slot lists: the
+        // narrow run (V <= 32) after the split chunk pass, <= kLocMaxGran granules
+        // (the decision keeps PM and SM in the digit pass's count array: G <= 8,192 granules for the
+        // 2,048-bin pass, <= 4,096 for the 512-bin one)
+        p.loc = p.fast && st.V <= kNarrowMaxV && (sp.wide || t.pre_all) && t.local != 0 &&
+                sp.nch * kGranPerChunk <= (size_t)(sp.wide ? kLocMaxGran : kLocMaxGran / 2);
+        p.loc_gsize = (uint32_t)((size_t)kRsWaves * 64u * (size_t)sp.rounds / kGranPerChunk);
+        p.gl = (unsigned)std::min<size_t>(sp.nch * kGranPerChunk / kLocU, 2048);
+        // keys of 19-22 bits (2,048-bin digits) with the register-resident run kernel: the
+        // chunk pass split in two (detection, then decision + digits), so structured batches skip the digits
+        p.pre = (sp.wide || t.pre_all) && p.fast;
+        p.drop_prefill = p.pre;             // the detection pass (mode 1) stores every packet's drop
+        p.delay_ticks = (uint32_t)t.decide_delay * 100u;
+        // the detection pass's arrival-order keys are read only by the in-order narrow run and the
+        // near-sorted lists; with descriptors the pass stores only the waves that found a descent
+        // (a batch in slot order or of dense runs: none of its 26 MB at NGA-32 C3 size), the lists
+        // read those and make the rest from the descriptors, the in-order run makes all (KeySrc).
+        // A sort queued alone still writes every key (its run may come without the descriptors).
+        // (narrow + descriptors, one call: no arrival-order key array)
+        p.keys_from_desc = INA_KEYS_FROM_DESC && p.pre && desc && phase == 0 && st.V <= kNarrowMaxV;
+        // plain packets (kPlainBit): the digit pass of a narrow split-row batch reads its header rows
+        // and marks them, so the sorted run reads no header row for them.  One call only (a sort
+        // queued alone reads nothing but the descriptors), no PS step, and the ack hint on (both
+        // hint bits outside the digits, masked out of the slot by the run)
+        p.plain = INA_SWITCH_PLAIN && p.pre && split && phase == 0 && !ps_on && p.ack_hint && st.V <= kNarrowMaxV &&
+                  sp.passes * sp.bits <= 30 && st.num_slots < kPlainBit;
+        // the bucket of foreign packets only (a pool of a multiple of 2^lb slots) is left out
+        // when the register-resident run kernel takes the batch (it stops before them); the
+        // generic run kernel reads every position, so then it is gathered like the others
+        if (p.fast && (st.num_slots & ((1u << lb) - 1u)) == 0u) p.skip = st.num_slots >> lb;
+        p.CH = (uint32_t)kRsWaves * 64u * (uint32_t)sp.rounds;
+        // buckets past the sentinel's (num_slots >> lb) are always empty: no block for them,
+        // so at 2^17 slots 257 blocks (one per CU, one generation) instead of 512
+        p.gb = std::min<unsigned>(1u << sp.hbits, (st.num_slots >> lb) + 1u);
+        const int tile = t.bucket_tile;
+        p.big = tile == kLcRoundsBig || (tile == 0 && npk > (size_t)p.gb * kBigTileAvg);
+    }
+    if (p.path == kPathTiny) {
+        p.win = (uint32_t)INA_SWITCH_WIN_SMALL;
+        if (const int wv = t.win) p.win = (uint32_t)wv;
+    } else if (p.fast) {
+        // a wave runs the segments that start in its window of `win` sorted positions: a
+        // segment is a chain of dependent round trips, so small windows (more waves) win
+        // at every size -- tools/lab/switch_lab.py, profiles/r01/lab/switch_lab_win.log:
+        // 1,024 packets 52.9 -> 27.7 us (64 -> 8 positions), 819,200 packets 277 -> 266 us
+        // (64 -> 16 positions, one pass of the grid)
+        // V <= 32 (NGA-32, the P4 program's format): 8 packets of a segment side by side per
+        // wave (run_segment_narrow); wider packets: a packet per wave instruction
+        p.narrow = st.V <= kNarrowMaxV;
+        p.win = npk <= 65536 ? (uint32_t)INA_SWITCH_WIN_SMALL : (uint32_t)INA_SWITCH_WIN_LARGE;
+        // a narrow wave moves a whole segment per batch: a window of 64 sorted positions
+        // (about 8 segments) keeps the grid at npk / 256 workgroups
+        if (p.narrow && (INA_SWITCH_NARROW_SLOTS || npk > 65536)) p.win = INA_SWITCH_WIN_NARROW;   // 8 lane groups: ~8 segments
+        if (const int wv = t.win) p.win = (uint32_t)wv;
+        const size_t per_block = (size_t)p.win * (kSwBlock / 64);
+        p.gr = (unsigned)std::min<size_t>((npk + per_block - 1) / per_block, INA_SWITCH_GRID);
+    } else {
+        p.gr = (unsigned)((npk + (kSwBlock / 64) - 1) / (kSwBlock / 64));
+    }
+    return p;
+}
+
+// the batch as ina_switch was given it
+struct SwitchBatch {
+    const ina_switch_state_t* st;
+    uint8_t *pkts, *pay;
+    size_t npk, stride;
+    const uint64_t* desc;
+    uint8_t* actions;
+    const PsFuse& ps;
+    hipStream_t s;
+};
+
+// never 0 (fresh scratch reads as "unsorted": the safe side); a stale epoch equal to
+// this one (2^32 calls later) also only costs the full sort
+static uint32_t draw_sort_epoch() {
+    uint32_t epoch = g_sort_epoch.fetch_add(1u) + 1u;
+    if (epoch == 0u) epoch = g_sort_epoch.fetch_add(1u) + 1u;
+    return epoch;
+}
+
+static void launch_tiny(const SwitchBatch& b, const SwitchPlan& p) {
+    const bool split = b.pay != nullptr;
+    auto* tiny = b.ps.on
+        ? (p.key32 ? (split ? &k_switch_tiny<true, uint32_t, 12, true> : &k_switch_tiny<true, uint32_t, 12, false>)
+                   : (split ? &k_switch_tiny<true, unsigned long long, 32, true> : &k_switch_tiny<true, unsigned long long, 32, false>))
+        : (p.key32 ? (split ? &k_switch_tiny<false, uint32_t, 12, true> : &k_switch_tiny<false, uint32_t, 12, false>)
+                   : (split ? &k_switch_tiny<false, unsigned long long, 32, true> : &k_switch_tiny<false, unsigned long long, 32, false>));
+    hipLaunchKernelGGL(tiny, dim3(1), dim3(kSmallBlock), 0, b.s, *b.st, b.pkts, b.pay, (uint32_t)b.npk, b.stride,
+                       b.actions, p.win, b.ps);
+}
+
+static void launch_sort_small(const SwitchBatch& b, const SwitchPlan& p, const SwitchScratch& sc) {
+    hipLaunchKernelGGL((p.key32 ? &k_switch_sort_small<uint32_t, 12> : &k_switch_sort_small<unsigned long long, 32>),
+                       dim3(1), dim3(kSmallBlock), 0, b.s, b.pkts, (uint32_t)b.npk, b.stride, b.st->num_slots,
+                       b.st->switch_id, b.actions, sc.k_in, sc.v_in);
+}
+
+// A: keys + each chunk sorted by the high digit (bits lb..eb-1) -> (k_out, v_out) and the
+// per (digit, chunk) run lengths / starts.  Split (pre): the detection pass first (the
+// arrival-order keys -> (k_in, v_in)), then the decision + digits
+static void launch_chunk_pass(const SwitchBatch& b, const SwitchPlan& p, const SwitchScratch& sc, uint32_t epoch) {
+    const SortPlan& sp = p.sp;
+    const uint2* dsc = reinterpret_cast<const uint2*>(b.desc);
+    with_chunk_rounds(p.ri, [&](auto rr) {
+        constexpr int RR = decltype(rr)::value;
+        auto pass = [&](auto* kernel, uint32_t* kout, uint32_t* vout, uint32_t delay_ticks, uint32_t* kflags,
+                        const uint32_t* plain_hdr) {
+            hipLaunchKernelGGL(kernel, dim3(p.gc), dim3(kBkThr), 0, b.s, b.pkts, dsc, b.npk, b.stride,
+                               b.st->num_slots, b.st->switch_id, b.actions, sp.hbits, sp.lbits, sc.hist, sc.rst,
+                               sp.nch, kout, vout, p.ack_hint ? 1 : 0, sc.unsorted, epoch,
+                               p.runs_on ? sc.brk_cnt : nullptr, sc.brk_ent, p.loc ? sc.gstat : nullptr, sc.units,
+                               delay_ticks, kflags, plain_hdr);
+        };
+        if (p.pre) {
+            pass(dsc ? &k_sort_chunks<RR, true, 64, 1> : &k_sort_chunks<RR, false, 64, 1>, sc.k_in, sc.v_in, 0u,
+                 p.keys_from_desc ? sc.kflags : nullptr, nullptr);
+            pass(sp.wide ? (dsc ? &k_sort_chunks<RR, true, kBinsBig, 2> : &k_sort_chunks<RR, false, kBinsBig, 2>)
+                         : (dsc ? &k_sort_chunks<RR, true, kRsBins, 2> : &k_sort_chunks<RR, false, kRsBins, 2>),
+                 sc.k_out, sc.v_out, p.delay_ticks, nullptr,
+                 p.plain ? reinterpret_cast<const uint32_t*>(b.pkts) : nullptr);
+        } else {
+            pass(sp.wide ? (dsc ? &k_sort_chunks<RR, true, kBinsBig> : &k_sort_chunks<RR, false, kBinsBig>)
+                         : (dsc ? &k_sort_chunks<RR, true, kRsBins> : &k_sort_chunks<RR, false, kRsBins>),
+                 sc.k_out, sc.v_out, 0u, nullptr, nullptr);
+        }
+    });
+}
+
+// B: each bucket gathered in chunk order and sorted on its low digit -> (k_in, v_in)
+static void launch_bucket_pass(const SwitchBatch& b, const SwitchPlan& p, const SwitchScratch& sc, uint32_t epoch) {
+    const SortPlan& sp = p.sp;
+    const int lb = sp.lbits;
+    // the bucket pass's bins follow the low digit: 1,024 for keys of 19-21 bits (three
+    // blocks per CU with the packed counts), 2,048 for 22 bits
+    hipLaunchKernelGGL((sp.wide ? (lb <= 10 ? (p.big ? &k_sort_buckets<kLcRoundsBig, 1024> : &k_sort_buckets<kLcRounds, 1024>)
+                                            : (p.big ? &k_sort_buckets<kLcRoundsBig, kBinsBig> : &k_sort_buckets<kLcRounds, kBinsBig>))
+                                : (p.big ? &k_sort_buckets<kLcRoundsBig, kRsBins> : &k_sort_buckets<kLcRounds, kRsBins>)),
+                       dim3(p.gb), dim3(kBkThr), 0, b.s, sc.k_out, sc.v_out, sc.k_in, sc.v_in, sc.hist, sc.rst,
+                       (uint32_t)sp.nch, p.CH, lb, sc.nforeign, p.skip, sc.unsorted, epoch, p.fast ? 0 : 1,
+                       (p.runs_on && !p.pre) ? sc.brk_cnt : nullptr, sc.brk_ent, (uint32_t)b.npk, p.pre ? 1 : 0);
+}
+
+// the near-sorted path's per-slot lists into the idle k_out (exits at once unless the
+// decision chose the path)
+static void launch_local_lists(const SwitchBatch& b, const SwitchPlan& p, const SwitchScratch& sc) {
+    hipLaunchKernelGGL(k_local_lists, dim3(p.gl), dim3(kLlWaves * 64), 0, b.s,
+                       KeySrc{sc.k_in, p.keys_from_desc ? reinterpret_cast<const uint2*>(b.desc) : nullptr,
+                              b.st->num_slots, b.st->switch_id, p.ack_hint, sc.kflags, 0u,
+                              6u + (uint32_t)__builtin_ctz((unsigned)(p.sp.rounds / 4))},
+                       b.npk, b.st->num_slots, p.ack_hint ? ~kAckBit : 0xFFFFFFFFu, sc.unsorted, sc.units,
+                       p.loc_gsize, sc.k_out, sc.tab);
+}
+
+// LSD digit passes: keys + pass-0 histogram, then per pass a column scan and a scatter,
+// (k_in, ids) -> (k_out, v_out) -> (k_in, v_in) -> ...
+static int launch_digit_passes(const SwitchBatch& b, const SwitchPlan& p, const SwitchScratch& sc, uint32_t epoch) {
+    const SortPlan& sp = p.sp;
+    const int ri = p.ri;
+    auto* k_keys = b.desc ? (ri == 0 ? &k_switch_keys<kR0, true> : ri == 1 ? &k_switch_keys<kR1, true>
+                                                                  : &k_switch_keys<kR2, true>)
+                          : (ri == 0 ? &k_switch_keys<kR0, false> : ri == 1 ? &k_switch_keys<kR1, false>
+                                                                   : &k_switch_keys<kR2, false>);
+    auto* k_hist = ri == 0 ? &k_rs_hist<kR0> : ri == 1 ? &k_rs_hist<kR1> : &k_rs_hist<kR2>;
+    auto* k_sc0 = ri == 0 ? &k_rs_scatter<false, kR0>
+                : ri == 1 ? &k_rs_scatter<false, kR1> : &k_rs_scatter<false, kR2>;
+    auto* k_sc1 = ri == 0 ? &k_rs_scatter<true, kR0>
+                : ri == 1 ? &k_rs_scatter<true, kR1> : &k_rs_scatter<true, kR2>;
+    hipLaunchKernelGGL(k_keys, dim3(p.gc), dim3(kRsBlock), 0, b.s, b.pkts,
+                       reinterpret_cast<const uint2*>(b.desc), b.npk, b.stride, b.st->num_slots,
+                       b.st->switch_id, sc.k_in, b.actions, sp.bits, 0, sc.hist, sp.nch, p.ack_hint ? 1 : 0,
+                       sc.unsorted, epoch);
+    if (int rc = check_launch("switch keys launch")) return rc;
+    uint32_t *kc = sc.k_in, *vc = sc.v_in, *kn = sc.k_out, *vn = sc.v_out;
+    for (int pass = 0; pass < sp.passes; ++pass) {
+        const int shift = pass * sp.bits;
+        if (pass > 0)
+            hipLaunchKernelGGL(k_hist, dim3(p.gc), dim3(kRsBlock), 0, b.s, kc, b.npk, shift, sp.bits, sc.hist,
+                               sp.nch);
+        hipLaunchKernelGGL(k_rs_colscan, dim3(p.gd), dim3(kRsBlock), 0, b.s, sc.hist, sp.nch, p.nb, sc.totals);
+        if (pass == 0)
+            hipLaunchKernelGGL(k_sc0, dim3(p.gc), dim3(kRsBlock), 0, b.s, kc, nullptr, kn, vn, b.npk, shift,
+                               sp.bits, sc.hist, sc.totals, sp.nch);
+        else
+            hipLaunchKernelGGL(k_sc1, dim3(p.gc), dim3(kRsBlock), 0, b.s, kc, vc, kn, vn, b.npk, shift,
+                               sp.bits, sc.hist, sc.totals, sp.nch);
+        if (int rc = check_launch("switch sort launch")) return rc;
+        std::swap(kc, kn);
+        std::swap(vc, vn);
+    }
+    return INA_OK;
+}
+
+// the run over the sorted (keys, ids): where the plan's sort left them, and what else of the
+// scratch the register-resident kernel may read
+static void launch_run(const SwitchBatch& b, const SwitchPlan& p, const SwitchScratch& sc) {
+    uint32_t *kc = sc.k_in, *vc = sc.v_in, *kn = sc.k_out, *vn = sc.v_out;
+    if (p.path == kPathDigits && p.sp.passes % 2) {        // where the passes left the keys
+        std::swap(kc, kn);
+        std::swap(vc, vn);
+    }
+    if (p.pre) {                                           // the in-order run reads the arrival-order keys
+        kn = kc;
+        vn = nullptr;
+    }
+    if (!p.fast) {
+        hipLaunchKernelGGL(k_switch_run, dim3(p.gr), dim3(kSwBlock), 0, b.s, *b.st, b.pkts, b.npk, b.stride, kc, vc,
+                           b.actions);
+        return;
+    }
+    const bool bucket = p.path == kPathBucket, split = b.pay != nullptr, narrow = p.narrow;
+    // bucket sort: the run kernel may read A's output, and stops before the bucket B left out
+    const uint32_t* nforeign = p.skip != 0xFFFFFFFFu ? sc.nforeign : nullptr;
+    const uint32_t* unsorted = bucket ? sc.unsorted : nullptr;
+    auto* run = split ? (b.ps.on ? (narrow ? &k_switch_run2<true, true, true> : &k_switch_run2<true, false, true>)
+                                 : (narrow ? &k_switch_run2<false, true, true> : &k_switch_run2<false, false, true>))
+                      : (b.ps.on ? (narrow ? &k_switch_run2<true, true, false> : &k_switch_run2<true, false, false>)
+                                 : (narrow ? &k_switch_run2<false, true, false> : &k_switch_run2<false, false, false>));
+    hipLaunchKernelGGL(run, dim3(p.gr), dim3(kSwBlock), 0, b.s, *b.st, b.pkts, b.pay, b.npk, b.stride, kc, vc, b.actions,
+                       p.win, p.plain ? ~(kAckBit | kPlainBit) : p.ack_hint ? ~kAckBit : 0xFFFFFFFFu, b.ps, nforeign, kn, vn,
+                       unsorted, sc.k_out, sc.tab,
+                       p.drop_prefill ? 1 : 0, p.keys_from_desc ? reinterpret_cast<const uint2*>(b.desc) : nullptr);
+}
+
+// same checks, same order as ever (tests/test_capi.py asserts the strings)
+static int switch_check_args(const ina_switch_state_t* st, const uint8_t* pkts, size_t npk, size_t stride,
+                             const uint64_t* desc, const uint8_t* actions, const void* scratch, int phase,
+                             const uint8_t* pay) {
+    const bool split = pay != nullptr;
+    if (split && (!st || st->V % 4 || st->V <= 0 || st->V > kMaxV || stride != 16 || ((uintptr_t)pay & 15u)))
+        return set_error(INA_EINVAL, "split rows need V a multiple of 4 <= 256 and 16-byte aligned rows%s", "");
+    if (phase == 1 && !desc && npk)
+        return set_error(INA_EINVAL, "the separate slot sort needs the batch's descriptors%s", "");
+    if (!st || st->V <= 0 || st->V > kMaxV || st->num_slots == 0)
+        return set_error(INA_EINVAL, "bad switch state (V in [1,256])%s", "");
+    if (!split && stride < (size_t)INA_NGA_HDR_BYTES + 4u * (size_t)st->V)
+        return set_error(INA_EINVAL, "stride must be >= 15+4V%s", "");
+    if (stride > 0xFFFFFFFFu) return set_error(INA_EINVAL, "stride too large%s", "");
+    if (npk == 0) return INA_OK;
+    if (npk > 0x7FFFFFFFu) return set_error(INA_EINVAL, "too many packets%s", "");
+    if (!pkts || !actions || !scratch || !st->count || !st->frag || !st->regs)
+        return set_error(INA_EINVAL, "null pointer%s", "");
+    if (desc && ((uintptr_t)desc & 7u))
+        return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
+    return INA_OK;
+}
+
+// phase: 0 sort + run; 1 the slot sort alone (descriptor batches: it reads only the
+// descriptors, so it may run before or beside the kernels that fill the payload); 2 the run
+// alone over a scratch a phase-1 call filled for the same batch (paths whose sort reads the
+// packets -- the one-workgroup small-batch paths -- sort in phase 2 instead)
+// pay != NULL: split rows -- pkts are the 16-byte header rows (stride 16), pay the 4V-byte
+// payload rows (include/ina.h "split NGA rows"); only the register-resident run kernels
+// take them
+static int switch_process_impl(const ina_switch_state_t* st, uint8_t* pkts, size_t npk, size_t stride,
+                               const uint64_t* desc, uint8_t* actions, void* scratch,
+                               ina_stream_t stream, const PsFuse& ps, bool* fused_out, int phase = 0,
+                               uint8_t* pay = nullptr) {
+    *fused_out = false;
+    const bool split = pay != nullptr;
+    if (int rc = switch_check_args(st, pkts, npk, stride, desc, actions, scratch, phase, pay); rc || npk == 0)
+        return rc;
+    // the switch keys of this batch: read once here, or (a run alone) its sort's record
+    SwitchTuning t;
+    SortRecord rec{SwitchTuning{}, npk, stride, st->num_slots, st->V, split, pkts, pay, actions, st->switch_id};
+    if (phase == 2) {
+        if (!sort_record_find(scratch, rec, &t))
+            return set_error(INA_EINVAL,
+                             "run alone: no sort of this batch (rows, actions, shape, switch id) was queued into "
+                             "this scratch%s", "");
+    } else {
+        t = switch_tuning();
+        rec.t = t;
+        sort_record_set(scratch, false, rec);                  // this call overwrites the scratch
+    }
+    const SwitchPlan p = switch_plan(*st, npk, stride, aligned16(pkts), desc != nullptr, split, ps.on != 0, phase, t);
+    if (split && !p.fast) return set_error(INA_EINVAL, "split rows need 16-byte aligned rows and registers%s", "");
+    if (p.path == kPathDigits && p.ri == 3)
+        return set_error(INA_EINVAL, "8,192-packet chunks are the bucket sort's only%s", "");
+    const SwitchScratch sc = switch_scratch(scratch, npk, st->num_slots);
+    const SwitchBatch b{st, pkts, pay, npk, stride, desc, actions, ps, hs(stream)};
+
+    // the sort stages.  The two one-workgroup paths' sort reads the packets, so it goes with the
+    // run (phases 0 and 2; k_switch_tiny is both in one launch); the others sort in phases 0 and 1
+    const bool sort_with_run = p.path == kPathTiny || p.path == kPathSmall;
+    if (sort_with_run ? phase != 1 : phase != 2) {
+        int rc = INA_OK;
+        if (p.path == kPathSmall) {
+            launch_sort_small(b, p, sc);
+            rc = check_launch("switch sort launch");
+        } else if (p.path == kPathBucket) {
+            const uint32_t epoch = draw_sort_epoch();
+            launch_chunk_pass(b, p, sc, epoch);
+            launch_bucket_pass(b, p, sc, epoch);
+            if (p.loc) launch_local_lists(b, p, sc);
+            rc = check_launch("switch sort launch");
+        } else if (p.path == kPathDigits) {
+            rc = launch_digit_passes(b, p, sc, draw_sort_epoch());
+        }
+        if (rc) return rc;
+    }
+    // a sort alone records its batch, once every launch succeeded
+    if (phase == 1) {
+        sort_record_set(scratch, true, rec);
+        return INA_OK;
+    }
+    // the run stage
+    if (p.path == kPathTiny) launch_tiny(b, p);
+    else launch_run(b, p, sc);
+    if (int rc = check_launch(p.path == kPathTiny ? "switch tiny launch" : "switch run launch")) return rc;
+    *fused_out = p.fast && ps.on != 0;
+    // a run alone consumes the record
+    if (phase == 2) sort_record_set(scratch, false, rec);
+    return INA_OK;
 }
 
 }  // namespace ina
@@ -3897,318 +4289,8 @@ int ina_lab_bk_times(unsigned long long* host_out) {   // lab builds only
 
 size_t ina_switch_scratch_bytes(size_t npkts, uint32_t num_slots) {
     if (npkts == 0 || npkts > 0x7FFFFFFFu || num_slots == 0) return 256;
-    return 4 * align_up(npkts * 4, 256) + align_up(sort_temp_bytes(npkts, num_slots), 256) + 256;
-}
-
-// phase: 0 sort + run; 1 the slot sort alone (descriptor batches: it reads only the
-// descriptors, so it may run before or beside the kernels that fill the payload); 2 the run
-// alone over a scratch a phase-1 call filled for the same batch (paths whose sort reads the
-// packets -- the one-workgroup small-batch paths -- sort in phase 2 instead)
-// pay != NULL: split rows -- pkts are the 16-byte header rows (stride 16), pay the 4V-byte
-// payload rows (include/ina.h "split NGA rows"); only the register-resident run kernels
-// take them
-static int switch_process_impl(const ina_switch_state_t* st, uint8_t* pkts, size_t npk, size_t stride,
-                               const uint64_t* desc, uint8_t* actions, void* scratch,
-                               ina_stream_t stream, const PsFuse& ps, bool* fused_out, int phase = 0,
-                               uint8_t* pay = nullptr) {
-    *fused_out = false;
-    const bool split = pay != nullptr;
-    if (split && (!st || st->V % 4 || st->V <= 0 || st->V > kMaxV || stride != 16 || ((uintptr_t)pay & 15u)))
-        return set_error(INA_EINVAL, "split rows need V a multiple of 4 <= 256 and 16-byte aligned rows%s", "");
-    if (phase == 1 && !desc && npk)
-        return set_error(INA_EINVAL, "the separate slot sort needs the batch's descriptors%s", "");
-    const bool do_sort = phase != 2, do_run = phase != 1;
-    if (!st || st->V <= 0 || st->V > kMaxV || st->num_slots == 0)
-        return set_error(INA_EINVAL, "bad switch state (V in [1,256])%s", "");
-    if (!split && stride < (size_t)INA_NGA_HDR_BYTES + 4u * (size_t)st->V)
-        return set_error(INA_EINVAL, "stride must be >= 15+4V%s", "");
-    if (stride > 0xFFFFFFFFu) return set_error(INA_EINVAL, "stride too large%s", "");
-    if (npk == 0) return INA_OK;
-    if (npk > 0x7FFFFFFFu) return set_error(INA_EINVAL, "too many packets%s", "");
-    if (!pkts || !actions || !scratch || !st->count || !st->frag || !st->regs)
-        return set_error(INA_EINVAL, "null pointer%s", "");
-    if (desc && ((uintptr_t)desc & 7u))
-        return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
-    // the switch keys of this batch: read once here, or (a run alone) its sort's record
-    SwitchTuning t;
-    SortRecord rec{SwitchTuning{}, npk, stride, st->num_slots, st->V, split, pkts, pay, actions, st->switch_id};
-    if (phase == 2) {
-        if (!sort_record_find(scratch, rec, &t))
-            return set_error(INA_EINVAL,
-                             "run alone: no sort of this batch (rows, actions, shape, switch id) was queued into "
-                             "this scratch%s", "");
-    } else {
-        t = switch_tuning();
-        rec.t = t;
-        sort_record_set(scratch, false, rec);                  // this call overwrites the scratch
-    }
-    // a sort alone records its batch once every launch succeeded; a run alone consumes the record
-    auto sorted_ok = [&]() {
-        if (phase == 1) sort_record_set(scratch, true, rec);
-        return INA_OK;
-    };
-    auto run_ok = [&]() {
-        if (phase == 2) sort_record_set(scratch, false, rec);
-        return INA_OK;
-    };
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    uint8_t* base = reinterpret_cast<uint8_t*>(align_up((uintptr_t)scratch, 256));
-    size_t arr = align_up(npk * 4, 256);
-    uint32_t* k_in = reinterpret_cast<uint32_t*>(base);
-    uint32_t* k_out = reinterpret_cast<uint32_t*>(base + arr);
-    uint32_t* v_in = reinterpret_cast<uint32_t*>(base + 2 * arr);
-    uint32_t* v_out = reinterpret_cast<uint32_t*>(base + 3 * arr);
-    const SortPlan sp = sort_plan(npk, st->num_slots, t);
-    const SortAux ax = sort_aux(base + 4 * arr, npk, st->num_slots);
-    // sort chunk geometry (sort_plan): one instantiation per rounds-per-wave choice
-    constexpr int kR0 = INA_RS_ROUNDS_SMALL, kR1 = INA_RS_ROUNDS_MID, kR2 = kRsRounds, kR3 = INA_RS_ROUNDS_BIG;
-    static_assert(kR0 % 4 == 0 && kR1 % 4 == 0 && kR2 % 4 == 0 && kR3 % 4 == 0, "chunk sort: 16 waves x rounds/4");
-    const int ri = sp.rounds == kR0 ? 0 : sp.rounds == kR1 ? 1 : sp.rounds == kR2 ? 2 : 3;
-    const unsigned gc = (unsigned)sp.nch;
-    const uint32_t nb = 1u << sp.bits;
-
-    uint32_t *kc = k_in, *vc = v_in, *kn = k_out, *vn = v_out;
-    const bool fast = stride % 16 == 0 && ((uintptr_t)pkts & 15u) == 0 && st->V % 4 == 0 &&
-                      st->V <= kMaxV && ((uintptr_t)st->regs & 15u) == 0;
-    if (split && !fast) return set_error(INA_EINVAL, "split rows need 16-byte aligned rows and registers%s", "");
-    // keys carry the PS-ack bit for the run kernel when bit 31 is outside every digit
-    const bool ack_hint = fast && sp.passes * sp.bits <= 31 && t.ack_fast;
-    const bool small = npk <= (size_t)t.small_sort;
-    // chunk + bucket sort: keys of one or two digits (the low digit is one workgroup's LDS
-    // bins) and at most kBkMaxChunks chunks (B's LDS rows); else the digit passes
-    const bool bucket = !small && t.sort_mode == 0 && sp.bucket_ok && sp.nch <= (size_t)kBkMaxChunks;
-    const uint32_t* nforeign = nullptr;
-    const uint32_t* unsorted = nullptr;     // bucket sort: the run kernel may read A's output
-    uint32_t epoch = 0;
-    uint32_t loc_gsize = 0;                 // the near-sorted path's granule: 1/8 of a sort chunk
-    bool drop_prefill = false;              // the detection pass (mode 1) stores every packet's drop
-    bool keys_from_desc = false;            // narrow + descriptors, one call: no arrival-order key array
-    bool plain = false;                     // the digit pass marks plain packets (kPlainBit)
-    if (small && fast && npk <= (size_t)t.tiny_max) {
-        // sort and run in ONE launch of one workgroup (k_switch_tiny)
-        if (!do_run) return sorted_ok();
-        uint32_t win = (uint32_t)INA_SWITCH_WIN_SMALL;
-        if (const int wv = t.win) win = (uint32_t)wv;
-        const bool narrow = (uint64_t)st->num_slots + 1 <= (1u << 20);
-#define INA_TINY(P_, T_, B_, S_) hipLaunchKernelGGL((k_switch_tiny<P_, T_, B_, S_>), dim3(1), dim3(kSmallBlock), 0, s, \
-                                                   *st, pkts, pay, (uint32_t)npk, stride, actions, win, ps)
-        if (ps.on) {
-            if (narrow) { if (split) INA_TINY(true, uint32_t, 12, true); else INA_TINY(true, uint32_t, 12, false); }
-            else { if (split) INA_TINY(true, unsigned long long, 32, true); else INA_TINY(true, unsigned long long, 32, false); }
-        } else {
-            if (narrow) { if (split) INA_TINY(false, uint32_t, 12, true); else INA_TINY(false, uint32_t, 12, false); }
-            else { if (split) INA_TINY(false, unsigned long long, 32, true); else INA_TINY(false, unsigned long long, 32, false); }
-        }
-#undef INA_TINY
-        if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "switch tiny launch%s", "");
-        *fused_out = ps.on != 0;
-        return run_ok();
-    } else if (small) {
-        if (!do_run) return sorted_ok();                         // this sort reads the packets
-        if ((uint64_t)st->num_slots + 1 <= (1u << 20))
-            hipLaunchKernelGGL((k_switch_sort_small<uint32_t, 12>), dim3(1), dim3(kSmallBlock), 0, s, pkts,
-                               (uint32_t)npk, stride, st->num_slots, st->switch_id, actions, kc, vc);
-        else
-            hipLaunchKernelGGL((k_switch_sort_small<unsigned long long, 32>), dim3(1), dim3(kSmallBlock), 0,
-                               s, pkts, (uint32_t)npk, stride, st->num_slots, st->switch_id, actions, kc, vc);
-        if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "switch sort launch%s", "");
-    } else if (bucket) {
-        // A: keys + each chunk sorted by the high digit (bits lb..eb-1) -> (kn, vn) and the
-        // per (digit, chunk) run lengths / starts; B: each bucket gathered in chunk order and
-        // sorted on its low digit -> (kc, vc)
-        const int lb = sp.lbits;                           // low digit bits (0: one-digit keys)
-        const uint2* dsc = reinterpret_cast<const uint2*>(desc);
-        const int ah = ack_hint ? 1 : 0;
-        // dense ascending runs skip the sort (run table, switch_runs_body): the register-
-        // resident run kernel only (ina_set_tuning key 18 = 0 turns it off)
-        const bool runs_on = fast && t.runs != 0;
-        // near-sorted batches (local disorder) skip the sort and run from per-slot lists: the
-        // narrow run (V <= 32) after the split chunk pass, <= kLocMaxGran granules
-        // (the decision keeps PM and SM in the digit pass's count array: G <= 8,192 granules for the
-        // 2,048-bin pass, <= 4,096 for the 512-bin one)
-        const bool loc = fast && st->V <= kNarrowMaxV && (sp.wide || t.pre_all) && t.local != 0 &&
-                         sp.nch * kGranPerChunk <= (size_t)(sp.wide ? kLocMaxGran : kLocMaxGran / 2);
-        loc_gsize = (uint32_t)((size_t)kRsWaves * 64u * (size_t)sp.rounds / kGranPerChunk);
-        // never 0 (fresh scratch reads as "unsorted": the safe side); a stale epoch equal to
-        // this one (2^32 calls later) also only costs the full sort
-        // keys of 19-22 bits (2,048-bin digits) with the register-resident run kernel: the
-        // chunk pass split in two (detection, then decision + digits), so structured batches skip the digits
-        const bool pre = (sp.wide || t.pre_all) && fast;
-        drop_prefill = pre;
-        // the detection pass's arrival-order keys are read only by the in-order narrow run and the
-        // near-sorted lists; with descriptors the pass stores only the waves that found a descent
-        // (a batch in slot order or of dense runs: none of its 26 MB at NGA-32 C3 size), the lists
-        // read those and make the rest from the descriptors, the in-order run makes all (KeySrc).
-        // A sort queued alone still writes every key (its run may come without the descriptors).
-        keys_from_desc = INA_KEYS_FROM_DESC && pre && desc && phase == 0 && st->V <= kNarrowMaxV;
-        // plain packets (kPlainBit): the digit pass of a narrow split-row batch reads its header rows
-        // and marks them, so the sorted run reads no header row for them.  One call only (a sort
-        // queued alone reads nothing but the descriptors), no PS step, and the ack hint on (both
-        // hint bits outside the digits, masked out of the slot by the run)
-        plain = INA_SWITCH_PLAIN && pre && split && phase == 0 && !ps.on && ack_hint && st->V <= kNarrowMaxV &&
-                sp.passes * sp.bits <= 30 && st->num_slots < kPlainBit;
-        if (do_sort) {
-        epoch = g_sort_epoch.fetch_add(1u) + 1u;
-        if (epoch == 0u) epoch = g_sort_epoch.fetch_add(1u) + 1u;
-        if (pre) {
-#define INA_A_DETECT(RR)                                                                              \
-            hipLaunchKernelGGL((desc ? &k_sort_chunks<RR, true, 64, 1> : &k_sort_chunks<RR, false, 64, 1>),      \
-                               dim3(gc), dim3(kBkThr), 0, s, pkts, dsc, npk, stride, st->num_slots,       \
-                               st->switch_id, actions, sp.hbits, lb, ax.hist, ax.rst, sp.nch, kc, vc, ah, \
-                               ax.unsorted, epoch, runs_on ? ax.brk_cnt : nullptr, ax.brk_ent, loc ? ax.gstat : nullptr, ax.units, 0u, \
-                               keys_from_desc ? ax.kflags : nullptr, nullptr)
-            if (ri == 3) INA_A_DETECT(kR3 / 4);
-            else if (ri == 2) INA_A_DETECT(kR2 / 4);
-            else if (ri == 1) INA_A_DETECT(kR1 / 4);
-            else INA_A_DETECT(kR0 / 4);
-#undef INA_A_DETECT
-
-#define INA_A_SORT(RR)                                                                                \
-            hipLaunchKernelGGL((sp.wide ? (desc ? &k_sort_chunks<RR, true, kBinsBig, 2> : &k_sort_chunks<RR, false, kBinsBig, 2>) \
-                                        : (desc ? &k_sort_chunks<RR, true, kRsBins, 2> : &k_sort_chunks<RR, false, kRsBins, 2>)), \
-                               dim3(gc), dim3(kBkThr), 0, s, pkts, dsc, npk, stride, st->num_slots,       \
-                               st->switch_id, actions, sp.hbits, lb, ax.hist, ax.rst, sp.nch, kn, vn, ah, \
-                               ax.unsorted, epoch, runs_on ? ax.brk_cnt : nullptr, ax.brk_ent, loc ? ax.gstat : nullptr, ax.units, \
-                               (uint32_t)t.decide_delay * 100u, nullptr,                                  \
-                               plain ? reinterpret_cast<const uint32_t*>(pkts) : nullptr)
-            if (ri == 3) INA_A_SORT(kR3 / 4);
-            else if (ri == 2) INA_A_SORT(kR2 / 4);
-            else if (ri == 1) INA_A_SORT(kR1 / 4);
-            else INA_A_SORT(kR0 / 4);
-#undef INA_A_SORT
-        } else {
-#define INA_A_LAUNCH(RR)                                                                              \
-        hipLaunchKernelGGL((sp.wide ? (desc ? &k_sort_chunks<RR, true, kBinsBig> : &k_sort_chunks<RR, false, kBinsBig>) \
-                                    : (desc ? &k_sort_chunks<RR, true, kRsBins> : &k_sort_chunks<RR, false, kRsBins>)), \
-                           dim3(gc), dim3(kBkThr), 0, s, pkts, dsc, npk, stride, st->num_slots,       \
-                           st->switch_id, actions, sp.hbits, lb, ax.hist, ax.rst, sp.nch, kn, vn, ah,  \
-                           ax.unsorted, epoch, runs_on ? ax.brk_cnt : nullptr, ax.brk_ent, loc ? ax.gstat : nullptr, ax.units, 0u, nullptr, \
-                           nullptr)
-        if (ri == 3) INA_A_LAUNCH(kR3 / 4);
-        else if (ri == 2) INA_A_LAUNCH(kR2 / 4);
-        else if (ri == 1) INA_A_LAUNCH(kR1 / 4);
-        else INA_A_LAUNCH(kR0 / 4);
-#undef INA_A_LAUNCH
-        }
-        }
-        // the bucket of foreign packets only (a pool of a multiple of 2^lb slots) is left out
-        // when the register-resident run kernel takes the batch (it stops before them); the
-        // generic run kernel reads every position, so then it is gathered like the others
-        uint32_t skip = 0xFFFFFFFFu;
-        if (fast && (st->num_slots & ((1u << lb) - 1u)) == 0u) {
-            skip = st->num_slots >> lb;
-            nforeign = ax.nforeign;
-        }
-        const uint32_t CH = (uint32_t)kRsWaves * 64u * (uint32_t)sp.rounds;
-        // buckets past the sentinel's (num_slots >> lb) are always empty: no block for them,
-        // so at 2^17 slots 257 blocks (one per CU, one generation) instead of 512
-        const unsigned gb = std::min<unsigned>(1u << sp.hbits, (st->num_slots >> lb) + 1u);
-        const int tile = t.bucket_tile;
-        const bool big = tile == kLcRoundsBig || (tile == 0 && npk > (size_t)gb * kBigTileAvg);
-        if (do_sort)
-            // the bucket pass's bins follow the low digit: 1,024 for keys of 19-21 bits (three
-            // blocks per CU with the packed counts), 2,048 for 22 bits
-            hipLaunchKernelGGL((sp.wide ? (lb <= 10 ? (big ? &k_sort_buckets<kLcRoundsBig, 1024> : &k_sort_buckets<kLcRounds, 1024>)
-                                                    : (big ? &k_sort_buckets<kLcRoundsBig, kBinsBig> : &k_sort_buckets<kLcRounds, kBinsBig>))
-                                        : (big ? &k_sort_buckets<kLcRoundsBig, kRsBins> : &k_sort_buckets<kLcRounds, kRsBins>)),
-                               dim3(gb),
-                               dim3(kBkThr), 0, s, kn, vn, kc, vc, ax.hist, ax.rst, (uint32_t)sp.nch, CH, lb,
-                               ax.nforeign, skip, ax.unsorted, epoch, fast ? 0 : 1,
-                               (runs_on && !pre) ? ax.brk_cnt : nullptr, ax.brk_ent, (uint32_t)npk, pre ? 1 : 0);
-        if (do_sort && loc)
-            // the near-sorted path's per-slot lists into the idle k_out (exits at once unless the
-            // decision chose the path)
-            hipLaunchKernelGGL(k_local_lists, dim3((unsigned)std::min<size_t>(sp.nch * kGranPerChunk / kLocU, 2048)),
-                               dim3(kLlWaves * 64), 0, s,
-                               KeySrc{kc, keys_from_desc ? dsc : nullptr, st->num_slots, st->switch_id, ack_hint,
-                                      ax.kflags, 0u, 6u + (uint32_t)__builtin_ctz((unsigned)(sp.rounds / 4))},
-                               npk, st->num_slots, ack_hint ? ~kAckBit : 0xFFFFFFFFu,
-                               ax.unsorted, ax.units, loc_gsize, k_out, ax.tab);
-        if (pre) {                                 // the in-order run reads the arrival-order keys
-            kn = kc;
-            vn = nullptr;
-        }
-        if (fast) unsorted = ax.unsorted;
-        if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "switch sort launch%s", "");
-    } else {
-        // LSD digit passes (keys of three digits, batches beyond B's rows, or key 12 = 3):
-        // keys + pass-0 histogram, then per pass a column scan and a scatter
-        if (ri == 3) return set_error(INA_EINVAL, "8,192-packet chunks are the bucket sort's only%s", "");
-        auto* k_keys = desc ? (ri == 0 ? &k_switch_keys<kR0, true> : ri == 1 ? &k_switch_keys<kR1, true>
-                                                                    : &k_switch_keys<kR2, true>)
-                            : (ri == 0 ? &k_switch_keys<kR0, false> : ri == 1 ? &k_switch_keys<kR1, false>
-                                                                     : &k_switch_keys<kR2, false>);
-        auto* k_hist = ri == 0 ? &k_rs_hist<kR0> : ri == 1 ? &k_rs_hist<kR1> : &k_rs_hist<kR2>;
-        auto* k_sc0 = ri == 0 ? &k_rs_scatter<false, kR0>
-                    : ri == 1 ? &k_rs_scatter<false, kR1> : &k_rs_scatter<false, kR2>;
-        auto* k_sc1 = ri == 0 ? &k_rs_scatter<true, kR0>
-                    : ri == 1 ? &k_rs_scatter<true, kR1> : &k_rs_scatter<true, kR2>;
-        const unsigned gd = (nb + kRsWaves - 1) / kRsWaves;
-        if (do_sort) {
-        uint32_t lsd_epoch = g_sort_epoch.fetch_add(1u) + 1u;
-        if (lsd_epoch == 0u) lsd_epoch = g_sort_epoch.fetch_add(1u) + 1u;
-        hipLaunchKernelGGL(k_keys, dim3(gc), dim3(kRsBlock), 0, s, pkts,
-                           reinterpret_cast<const uint2*>(desc), npk, stride, st->num_slots,
-                           st->switch_id, k_in, actions, sp.bits, 0, ax.hist, sp.nch, ack_hint ? 1 : 0,
-                           ax.unsorted, lsd_epoch);
-        if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "switch keys launch%s", "");
-        // (k_in, ids) -> (k_out, v_out) -> (k_in, v_in) -> ...
-        for (int pass = 0; pass < sp.passes; ++pass) {
-            const int shift = pass * sp.bits;
-            if (pass > 0)
-                hipLaunchKernelGGL(k_hist, dim3(gc), dim3(kRsBlock), 0, s, kc, npk, shift, sp.bits, ax.hist,
-                                   sp.nch);
-            hipLaunchKernelGGL(k_rs_colscan, dim3(gd), dim3(kRsBlock), 0, s, ax.hist, sp.nch, nb, ax.totals);
-            if (pass == 0)
-                hipLaunchKernelGGL(k_sc0, dim3(gc), dim3(kRsBlock), 0, s, kc, nullptr, kn, vn, npk, shift,
-                                   sp.bits, ax.hist, ax.totals, sp.nch);
-            else
-                hipLaunchKernelGGL(k_sc1, dim3(gc), dim3(kRsBlock), 0, s, kc, vc, kn, vn, npk, shift,
-                                   sp.bits, ax.hist, ax.totals, sp.nch);
-            if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "switch sort launch%s", "");
-            std::swap(kc, kn);
-            std::swap(vc, vn);
-        }
-        } else {
-            for (int pass = 0; pass < sp.passes; ++pass) {    // where the passes left the keys
-                std::swap(kc, kn);
-                std::swap(vc, vn);
-            }
-        }
-    }
-    if (!do_run) return sorted_ok();
-    if (fast) {
-        // a wave runs the segments that start in its window of `win` sorted positions: a
-        // segment is a chain of dependent round trips, so small windows (more waves) win
-        // at every size -- tools/lab/switch_lab.py, profiles/r01/lab/switch_lab_win.log:
-        // 1,024 packets 52.9 -> 27.7 us (64 -> 8 positions), 819,200 packets 277 -> 266 us
-        // (64 -> 16 positions, one pass of the grid)
-        // V <= 32 (NGA-32, the P4 program's format): 8 packets of a segment side by side per
-        // wave (run_segment_narrow); wider packets: a packet per wave instruction
-        const bool narrow = st->V <= kNarrowMaxV;
-        uint32_t win = npk <= 65536 ? (uint32_t)INA_SWITCH_WIN_SMALL : (uint32_t)INA_SWITCH_WIN_LARGE;
-        // a narrow wave moves a whole segment per batch: a window of 64 sorted positions
-        // (about 8 segments) keeps the grid at npk / 256 workgroups
-        if (narrow && (INA_SWITCH_NARROW_SLOTS || npk > 65536)) win = INA_SWITCH_WIN_NARROW;   // 8 lane groups: ~8 segments
-        if (const int wv = t.win) win = (uint32_t)wv;
-        const size_t per_block = (size_t)win * (kSwBlock / 64);
-        unsigned gr = (unsigned)std::min<size_t>((npk + per_block - 1) / per_block, INA_SWITCH_GRID);
-        auto* run = split ? (ps.on ? (narrow ? &k_switch_run2<true, true, true> : &k_switch_run2<true, false, true>)
-                                   : (narrow ? &k_switch_run2<false, true, true> : &k_switch_run2<false, false, true>))
-                          : (ps.on ? (narrow ? &k_switch_run2<true, true, false> : &k_switch_run2<true, false, false>)
-                                   : (narrow ? &k_switch_run2<false, true, false> : &k_switch_run2<false, false, false>));
-        hipLaunchKernelGGL(run, dim3(gr), dim3(kSwBlock), 0, s, *st, pkts, pay, npk, stride, kc, vc, actions,
-                           win, plain ? ~(kAckBit | kPlainBit) : ack_hint ? ~kAckBit : 0xFFFFFFFFu, ps, nforeign, kn, vn,
-                           unsorted, k_out, ax.tab,
-                           drop_prefill ? 1 : 0, keys_from_desc ? reinterpret_cast<const uint2*>(desc) : nullptr);
-        *fused_out = ps.on != 0;
-    } else {
-        unsigned gw = (unsigned)((npk + (kSwBlock / 64) - 1) / (kSwBlock / 64));
-        hipLaunchKernelGGL(k_switch_run, dim3(gw), dim3(kSwBlock), 0, s, *st, pkts, npk, stride, kc,
-                           vc, actions);
-    }
-    if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "switch run launch%s", "");
-    return run_ok();
+    // + 256: the caller's base may be unaligned
+    return align_up(switch_scratch(nullptr, npkts, num_slots).end, 256) + 256;
 }
 
 static int switch_apply_impl(const ina_switch_state_t* st, uint8_t* pkts, size_t npk, size_t stride,
@@ -4217,7 +4299,7 @@ static int switch_apply_impl(const ina_switch_state_t* st, uint8_t* pkts, size_t
                              float* out, size_t n, uint8_t* acks, size_t ack_stride,
                              ina_nga_desc_t* ack_desc, int keep_forwarded, ina_stream_t stream, int phase,
                              uint8_t* pay) {
-    if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
+    if (int rc = check_k(k)) return rc;
     if (npk == 0) return INA_OK;
     if (!local || !out) return set_error(INA_EINVAL, "null pointer%s", "");
     if (((uintptr_t)local & 15u) || ((uintptr_t)out & 15u))
@@ -4276,12 +4358,11 @@ int ina_switch_process(const ina_switch_state_t* st, uint8_t* pkts, size_t npk, 
 int ina_switch_batch_path(const void* scratch, size_t npk, uint32_t num_slots, int* path) {
     if (!scratch || !path || npk == 0 || npk > 0x7FFFFFFFu || num_slots == 0)
         return set_error(INA_EINVAL, "bad arguments%s", "");
-    const uint8_t* base = reinterpret_cast<const uint8_t*>(align_up((uintptr_t)scratch, 256));
-    const SortAux ax = sort_aux(const_cast<uint8_t*>(base) + 4 * align_up(npk * 4, 256), npk, num_slots);
+    const SwitchScratch sc = switch_scratch(scratch, npk, num_slots);
     uint32_t e[kLocEpoch + 1];
     // the caller's stream may be a non-blocking one: wait for the whole device first
     if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(e, ax.unsorted, sizeof(e), hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(e, sc.unsorted, sizeof(e), hipMemcpyDeviceToHost) != hipSuccess)
         return set_error(INA_EHIP, "reading the control block%s", "");
     *path = e[kLocEpoch] == e[1] ? INA_PATH_LOCAL
           : e[0] != e[1]        ? INA_PATH_IN_ORDER
@@ -4299,22 +4380,13 @@ int ina_route_ipv4(const uint8_t* actions, const uint32_t* dst_ip, uint32_t dst_
     if (!actions || !egress || (nent > 0 && (!keys || !ports)))
         return set_error(INA_EINVAL, "null pointer%s", "");
     unsigned g = (unsigned)std::min<size_t>((npk + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_route_ipv4, dim3(g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       actions, dst_ip, dst_default, npk, keys, ports, nent, egress);
-    if (hipGetLastError() != hipSuccess) return set_error(INA_EHIP, "route launch%s", "");
-    return INA_OK;
+    hipLaunchKernelGGL(k_route_ipv4, dim3(g), dim3(256), 0, hs(stream), actions, dst_ip, dst_default, npk, keys,
+                       ports, nent, egress);
+    return check_launch("route launch");
 }
 
 }  // extern "C"
 
 #if INA_STORE_CHECK
-namespace ina {
-unsigned long long store_violations_switch() {
-    unsigned long long v = 0, z = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
-        return ~0ull;                                  // unreadable: report as a violation
-    return v;
-}
-}  // namespace ina
+unsigned long long ina::store_violations_switch() { return take_store_violations(); }
 #endif

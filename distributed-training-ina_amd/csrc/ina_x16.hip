@@ -32,11 +32,11 @@
 namespace ina {
 namespace {
 
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using u32x4 = u32x4_t;
+using u32x2 = u32x2_t;
+using f32x4 = f32x4_t;
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kHostBlock;
 
 __device__ __forceinline__ u32x4 q32x4(f32x4 v, float s) {
     return u32x4{(uint32_t)q32(v.x, s), (uint32_t)q32(v.y, s), (uint32_t)q32(v.z, s), (uint32_t)q32(v.w, s)};
@@ -256,35 +256,7 @@ __global__ __launch_bounds__(kBlk) void k_dequantize_i16_x16(const int16_t* __re
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-inline unsigned grid_of(size_t items, int cap) {
-    size_t g = (items + kBlk - 1) / kBlk;
-    if (g > (size_t)cap) g = (size_t)cap;             // grid-stride beyond
-    return g ? (unsigned)g : 1u;
-}
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-inline hipStream_t hs(ina_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-int check_k(int k) {
-    if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
-    return INA_OK;
-}
-int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? INA_OK : set_error(INA_EHIP, "16-bit kernel launch: %s", hipGetErrorString(e));
-}
-
-int fill_x16(PtrPack<uint16_t>& pk, const void* const* bufs, int W, bool& all_aligned) {
-    if (!bufs || W < 1 || W > INA_MAX_WORKERS) return set_error(INA_EINVAL, "W must be in [1, %s]", "64");
-    all_aligned = true;
-    for (int w = 0; w < W; ++w) {
-        if (!bufs[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
-        if ((uintptr_t)bufs[w] & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
-        pk.p[w] = static_cast<const uint16_t*>(bufs[w]);
-        all_aligned &= al16(bufs[w]);
-    }
-    for (int w = W; w < INA_MAX_WORKERS; ++w) pk.p[w] = nullptr;
-    return INA_OK;
-}
+int launched() { return check_launch("16-bit kernel launch"); }
 
 // XT-dispatched launches (xtype already checked)
 #define INA_X16_LAUNCH(xt, KERNEL, ...)                                                       \
@@ -306,11 +278,11 @@ int reduce_i16(const void* const* bufs, int xtype, int W, int16_t* out, size_t n
     if (n == 0) return INA_OK;
     PtrPack<uint16_t> pk;
     bool al;
-    if (int rc = fill_x16(pk, bufs, W, al)) return rc;
+    if (int rc = fill_pack(pk, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const float sc = ldexpf(1.0f, k);
-    if (al && al16(out) && (!ovf || slot_ballot_ok(V))) {
+    if (al && aligned16(out) && (!ovf || slot_ballot_ok(V))) {
         const int lps = slot_ballot_ok(V) ? V / 8 : 1;
         const dim3 g(grid_of((n + 7) / 8, default_grid_cap())), b(kBlk);
         switch (W) {
@@ -348,7 +320,7 @@ int ina_quantize_x16_i32(const void* x, int xtype, int32_t* q, size_t n, int k, 
     if (n == 0) return INA_OK;
     if (!x || !q) return set_error(INA_EINVAL, "null pointer%s", "");
     if ((uintptr_t)x & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
-    const int vec = al16(x) && al16(q);
+    const int vec = aligned16(x) && aligned16(q);
     // one chunk per thread, the grid covering the bucket, like the fp32 quantiser
     INA_X16_LAUNCH(xtype, k_quantize_x16_i32, dim3(grid_of(vec ? n / 4 + 1 : n, ew_grid_cap())), dim3(kBlk), 0,
                    hs(stream), static_cast<const uint16_t*>(x), q, n, ldexpf(1.0f, k), vec);
@@ -373,11 +345,11 @@ int ina_quantize_reduce_x16_i32(const void* const* bufs, int xtype, int W, int32
     if (n == 0) return INA_OK;
     PtrPack<uint16_t> pk;
     bool al;
-    if (int rc = fill_x16(pk, bufs, W, al)) return rc;
+    if (int rc = fill_pack(pk, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     // one worker: the sum is the quantised buffer itself
     if (W == 1) return ina_quantize_x16_i32(bufs[0], xtype, out, n, k, stream);
-    const int vec = al && al16(out);
+    const int vec = al && aligned16(out);
     const float sc = ldexpf(1.0f, k);
     // the sibling's grids: covering for W <= 8, the streaming cap beyond
     const dim3 g(grid_of(vec ? n / 4 + 1 : n, W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
@@ -403,12 +375,12 @@ int ina_absmax_multi_x16(const void* const* xs, int xtype, int W, const float* b
     if (!out_dev) return set_error(INA_EINVAL, "null out%s", "");
     PtrPack<uint16_t> pk;
     bool al;
-    if (int rc = fill_x16(pk, xs, W, al)) return rc;
+    if (int rc = fill_pack(pk, xs, W, al)) return rc;
     hipStream_t s = hs(stream);
     if (hipMemsetAsync(out_dev, 0, sizeof(float), s) != hipSuccess)
         return set_error(INA_EHIP, "memset absmax%s", "");
     if (n == 0) return INA_OK;
-    const int vec = al && (!base || al16(base));
+    const int vec = al && (!base || aligned16(base));
     // every block ends in one atomicMax on the same word, so the grid stays small (the
     // fp32 multi-bucket pass's 512 workgroups)
     INA_X16_LAUNCH(xtype, k_absmax_multi_x16, dim3(grid_of(vec ? n / 4 + 1 : n, 512)), dim3(kBlk), 0, s, pk, W,
@@ -422,7 +394,7 @@ int ina_dequantize_i32_x16(const int32_t* sv, void* y, int ytype, size_t n, int 
     if (n == 0) return INA_OK;
     if (!sv || !y) return set_error(INA_EINVAL, "null pointer%s", "");
     if ((uintptr_t)y & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
-    const int vec = al16(sv) && al16(y);
+    const int vec = aligned16(sv) && aligned16(y);
     INA_X16_LAUNCH(ytype, k_dequantize_i32_x16, dim3(grid_of(vec ? n / 4 + 1 : n, ew_grid_cap())), dim3(kBlk), 0,
                    hs(stream), sv, static_cast<uint16_t*>(y), n, ldexpf(1.0f, -k), vec);
     return launched();
@@ -434,7 +406,7 @@ int ina_dequantize_i16_x16(const int16_t* sv, void* y, int ytype, size_t n, int 
     if (n == 0) return INA_OK;
     if (!sv || !y) return set_error(INA_EINVAL, "null pointer%s", "");
     if ((uintptr_t)y & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
-    const int vec = al16(sv) && al16(y);
+    const int vec = aligned16(sv) && aligned16(y);
     INA_X16_LAUNCH(ytype, k_dequantize_i16_x16, dim3(grid_of(vec ? n / 8 + 1 : n, ew_grid_cap())), dim3(kBlk), 0,
                    hs(stream), sv, static_cast<uint16_t*>(y), n, ldexpf(1.0f, -k), vec);
     return launched();
@@ -443,13 +415,5 @@ int ina_dequantize_i16_x16(const int16_t* sv, void* y, int ytype, size_t n, int 
 }  // extern "C"
 
 #if INA_STORE_CHECK
-namespace ina {
-unsigned long long store_violations_x16() {
-    unsigned long long v = 0, z = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_store_violations), sizeof(v)) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_store_violations), &z, sizeof(z)) != hipSuccess)
-        return ~0ull;                                  // unreadable: report as a violation
-    return v;
-}
-}  // namespace ina
+unsigned long long ina::store_violations_x16() { return take_store_violations(); }
 #endif

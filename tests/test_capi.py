@@ -215,6 +215,62 @@ def test_set_tuning_rejects_unknown_keys_and_values():
     assert lib.ina_set_tuning(17, 5) == _lib.INA_EINVAL        # bucket tile: 0 auto / 4 / 8
     for v in (4, 8, 0):
         assert lib.ina_set_tuning(17, v) == _lib.INA_OK
+    # every switch key at the edges of what it takes; each key's last accepted value is its default,
+    # so the process-global tuning ends as a fresh library has it
+    ok, bad = _lib.INA_OK, _lib.INA_EINVAL
+    int_min, int_max = -(1 << 31), (1 << 31) - 1
+    switch_keys = {
+        9: ((0, 2, 768, 2048, 1), (-1, 2049, int_min, int_max)),    # one-workgroup sort: 0..2048, 1 the default
+        12: ((3, 0), (-1, 1, 2, 4)),                                  # sort: 0 auto, 3 digit passes
+        13: ((4, 8, 16, 0), (-1, 1, 2, 12, 32)),                      # chunk rounds: 0 auto, 4 / 8 / 16
+        15: ((0, 1, 2048, 128), (-1, 2049, int_min, int_max)),        # tiny path: 0..2048 packets
+        17: ((4, 8, 0), (-1, 1, 2, 16)),                              # bucket tile: 0 auto, 4 / 8
+        21: ((100000, 1, 0), (-1, 100001, int_min, int_max)),         # decision delay: 0..100000 us
+    }
+    for key, (accepted, refused) in switch_keys.items():
+        for v in refused:
+            assert lib.ina_set_tuning(key, v) == bad, (key, v)
+        for v in accepted:
+            assert lib.ina_set_tuning(key, v) == ok, (key, v)
+        for v in refused:                                            # a refusal after a set, too
+            assert lib.ina_set_tuning(key, v) == bad, (key, v)
+    for key in (11, 18, 19, 20):                                      # flags: any value, stored as 0 / 1
+        for v in (0, -1, 2, int_min, int_max, 1):
+            assert lib.ina_set_tuning(key, v) == ok, (key, v)
+    for v in (0, 1, 64, -1, 65):                                      # run window: lab builds only
+        assert lib.ina_set_tuning(10, v) == bad, v
+
+
+# ina_switch_scratch_bytes as the library returned it before the scratch layout became one function:
+# rows npkts (each sort chunk tier's edge), columns num_slots (each key width's edge).  Callers
+# size their buffers from these.
+_SCRATCH_SLOTS = (1, 511, 512, 1 << 17, 1 << 18, 1 << 20, 1 << 22, (1 << 31) - 1)
+_SCRATCH_BYTES = {
+    1: (6656, 14080, 10496, 1058560, 2111232, 8410880, 33593088, 17180399360),
+    1023: (22016, 29440, 25856, 1073920, 2126592, 8426240, 33608448, 17180414720),
+    1024: (22016, 29440, 25856, 1073920, 2126592, 8426240, 33608448, 17180414720),
+    262144: (4383232, 5431552, 4448512, 6476032, 8573184, 16961792, 46321920, 17318465792),
+    262145: (4386304, 5438208, 4451584, 6482688, 8583936, 16980736, 46357248, 17318992640),
+    524288: (8762880, 10855680, 8889600, 11900160, 15045888, 25531648, 59086080, 17457059072),
+    524289: (8765952, 10862336, 8892672, 11906816, 15056640, 25550592, 59121408, 17457585920),
+    2097152: (35040768, 43400448, 35536128, 44444928, 53882112, 76950784, 135671040, 18288618752),
+    2097153: (35043840, 43407104, 35539200, 44451584, 53892864, 76969728, 135706368, 18289145600),
+    6553600: (109494784, 135610624, 111034624, 136655104, 163918080, 222638336, 352661760, 20644704512),
+}
+
+
+def test_switch_scratch_bytes_pinned():
+    """The scratch size is part of the C ABI's contract (callers allocate from it): every value of
+    the table above, and 256 for the degenerate arguments."""
+    from ina_amd import _lib
+    lib = _lib.load()
+    for npk, row in _SCRATCH_BYTES.items():
+        for slots, want in zip(_SCRATCH_SLOTS, row):
+            assert lib.ina_switch_scratch_bytes(npk, slots) == want, (npk, slots)
+    assert lib.ina_switch_scratch_bytes(0, 16) == 256                 # no packets
+    assert lib.ina_switch_scratch_bytes(16, 0) == 256                 # no slots
+    assert lib.ina_switch_scratch_bytes(1 << 31, 16) == 256           # more than 2^31 - 1 packets
+    assert lib.ina_switch_scratch_bytes((1 << 31) - 1, 16) == 36381396480
 
 
 def test_switch_scratch_bytes_monotonic():

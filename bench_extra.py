@@ -219,6 +219,75 @@ def run_blk(dev):
     return rows
 
 
+def run_blk_packets(dev):
+    """Per-block scales on the packet path (include/ina_pkt_blk.h) at the ResNet-50 size, W = 8, V = 256
+    and 32, cold caches, median of 20, the whole set twice in this process (run 1 / run 2), as run_blk.
+    The GIVEN multi split pack beside ina_quantize_pack_nga_multi_split, and apply_completed_blk on
+    split rows beside the packed apply_completed on the same batch (the switch's output for 8 worker
+    streams, 1 packet in 8 completed): sibling timed twice, bar = sibling time x bytes ratio + spread.
+    The AUTO pack beside what a caller writes today: block_scales with base, then the GIVEN pack."""
+    from ina_amd import ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(18)
+    n, k, W = 25_557_032, 16, 8
+    xs = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(W)]
+    base = torch.randn(n, device=dev, generator=gen) * 1e-2
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+    bitmaps = [1 << w for w in range(W)]
+
+    def given(run, name, nb_sib, nblk, f_blk, f_sib):
+        ta, tb, tc = _time(f_sib), _time(f_blk), _time(f_sib)
+        lo, hi = min(ta, tc), max(ta, tc)
+        bar = hi * (nb_sib + nblk) / nb_sib + (hi - lo)
+        rows.append(_row(f"{name} [blk given, run {run}]", tb, nb_sib + nblk,
+                         sibling_us=[round(ta * 1e6, 2), round(tc * 1e6, 2)], sibling_spread_us=round((hi - lo) * 1e6, 2),
+                         bar_us=round(bar * 1e6, 2), bar_met=bool(tb <= bar)))
+        return hi - lo
+
+    for run in (1, 2):
+        for V in (256, 32):
+            npk = (n + V - 1) // V
+            hdrs = [torch.zeros((npk, 16), dtype=torch.uint8, device=dev) for _ in range(W)]
+            pays = [torch.empty((npk, 4 * V), dtype=torch.uint8, device=dev) for _ in range(W)]
+            kb = ops.block_scales(xs, V, bits=32, base=base)
+            kout = torch.empty(npk, dtype=torch.int8, device=dev)
+            nb_pack = (4 * W + 4) * n + W * npk * (16 + 4 * V)
+            spread = given(run, f"quantize_pack_nga_multi_split W={W} V={V}", nb_pack, npk,
+                           lambda: ops.quantize_pack_nga_multi_split_blk(xs, V, bitmaps, W, 1, 1, base=base, kblk=kb,
+                                                                         hdrs=hdrs, pays=pays),
+                           lambda: ops.quantize_pack_nga_multi_split(xs, k, V, bitmaps, W, 1, 1, base=base, hdrs=hdrs,
+                                                                     pays=pays))
+            ta = _time(lambda: ops.quantize_pack_nga_multi_split_blk(xs, V, bitmaps, W, 1, 1, base=base, kblk_out=kout,
+                                                                     hdrs=hdrs, pays=pays))
+            tc = _time(lambda: (ops.block_scales(xs, V, bits=32, base=base, out=kout),
+                                ops.quantize_pack_nga_multi_split_blk(xs, V, bitmaps, W, 1, 1, base=base, kblk=kout,
+                                                                      hdrs=hdrs, pays=pays)))
+            rows.append(_row(f"quantize_pack_nga_multi_split W={W} V={V} [blk auto, run {run}]", ta, nb_pack + npk,
+                             scales_then_given_us=round(tc * 1e6, 2), sibling_spread_us=round(spread * 1e6, 2),
+                             beats_scales_then_given_by_more_than_spread=bool(tc - ta > spread)))
+            # the PS apply on the switch's output: split rows against the packed rows of the same batch
+            slots = max(16384, npk)                      # a pool for the whole bucket: no slot is shared
+            ops.quantize_pack_nga_multi_split_blk(xs, V, bitmaps, W, 1, 1, base=base, kblk=kb, hdrs=hdrs, pays=pays,
+                                                  num_slots=slots)
+            hd = torch.stack(hdrs, 1).reshape(W * npk, 16).contiguous()
+            pa = torch.stack(pays, 1).reshape(W * npk, 4 * V).contiguous()
+            del hdrs, pays
+            act_s = ops.Switch(V, slots, 1, dev).process_split(hd, pa)
+            rows_p = ops.quantize_pack_nga_multi(xs, k, V, bitmaps, W, 1, 1, base=base, num_slots=slots)
+            pk = torch.stack(rows_p, 1).reshape(W * npk, -1).contiguous()
+            del rows_p
+            act_p = ops.Switch(V, slots, 1, dev).process(pk)
+            done = int((act_s == 1).sum()), int((act_p == 1).sum())          # ACT_FWD_AGG
+            assert done == (npk, npk), done
+            nb_apply = npk * (16 + 4 * V) + W * npk + 8 * n
+            given(run, f"apply_completed (split rows vs packed) W={W} V={V}", nb_apply, npk,
+                  lambda: ops.apply_completed_blk(hd, act_s, V, 1, base, kb, 0.1, out=y, pay=pa),
+                  lambda: ops.apply_completed(pk, act_p, V, 1, base, k, 0.1, out=y))
+            del hd, pa, pk
+    return rows
+
+
 DEFAULTS = {"max_blocks": 16384, "reduce_blocks": 0, "stream_blocks": 16384, "combine_blocks": 256,
             "combine_ina_blocks": 8192, "ew_blocks": 1 << 24}
 
@@ -595,4 +664,5 @@ def run_extra(dev):
     del hosts, hout, dbuf, b3, o3
     rows += run_x16(dev)
     rows += run_blk(dev)
+    rows += run_blk_packets(dev)
     return {"rows": rows, "sweep": sweep, "grid_sweeps": gsweep}

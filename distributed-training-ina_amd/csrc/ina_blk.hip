@@ -37,6 +37,16 @@
 #include "ina_device.h"
 
 namespace ina {
+
+// ina_scale_for's rule for the number of summands
+int scale_lim(int degree, int bits, double& lim) {
+    if (bits != 16 && bits != 32) return set_error(INA_EINVAL, "bits must be 16 or 32%s", "");
+    if (degree < 1) return set_error(INA_EINVAL, "degree must be >= 1%s", "");
+    lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)degree - 0.5;
+    if (lim <= 0.0) return set_error(INA_EINVAL, "too many summands (degree) for this width%s", "");
+    return INA_OK;
+}
+
 namespace {
 
 using u32x4 = u32x4_t;
@@ -48,53 +58,10 @@ constexpr int kBlk = 256;
 // ---------------------------------------------------------------------------
 // scales
 // ---------------------------------------------------------------------------
-// a given scale: -127 / -128 read as -126
-__device__ __forceinline__ int rd_k(const int8_t* __restrict__ kblk, size_t s) {
-    const int k = kblk[s];
-    return k < -126 ? -126 : k;
-}
-// 2^k for k in [-127, 127], built from its bits: 2^-127 is the subnormal 0x00400000 (ldexpf(1, -127)),
-// which an exp2 / division would flush or round
-__device__ __forceinline__ float pow2f(int k) {
-    return __uint_as_float(k >= -126 ? (uint32_t)(k + 127) << 23 : 0x00400000u);
-}
-// |d| as its bit pattern, NaN -> 0
-__device__ __forceinline__ uint32_t absbits(float d) {
-    const uint32_t u = __float_as_uint(d) & 0x7FFFFFFFu;
-    return u > 0x7F800000u ? 0u : u;
-}
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t fold4(uint32_t m, f32x4 a) {
-    return umax(umax(m, absbits(a.x)), umax(umax(absbits(a.y), absbits(a.z)), absbits(a.w)));
-}
+// (rd_k, pow2f, absbits, umax, fold4, scale_of and group_max are in ina_device.h: the block-scaled
+// packet kernels of ina_kernels.hip run the same ones)
 __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
     return f32x4{__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z), __fsub_rn(a.w, b.w)};
-}
-
-// ina_scale_for(amax, degree, bits) for amax given as its bits and lim = (2^(bits-1) - 1) / degree
-// - 1/2 as the host computed it: the largest k in [-126, 127] with amax * 2^k <= lim (-126 if
-// none).  amax = ma * 2^ea, lim = ml * 2^el with ma, ml in [1, 2): k = el - ea when ma <= ml, else
-// el - ea - 1 -- exponents and mantissas compared as integers, so the answer is the host's exact
-// double comparison for every fp32 amax (an fp32 mantissa, subnormal ones included, converts to
-// double exactly).
-__device__ __forceinline__ int scale_of(uint32_t u, double lim) {
-    if (u == 0u) return 127;
-    if (u >= 0x7F800000u) return -126;
-    const uint32_t e = u >> 23, m = u & 0x7FFFFFu;
-    const uint64_t d = (uint64_t)__double_as_longlong((double)(e ? (m | 0x800000u) : m));   // exact
-    const int ea = (int)(d >> 52) - 1023 + (int)(e ? e : 1u) - 150;
-    const uint64_t l = (uint64_t)__double_as_longlong(lim);
-    const int el = (int)(l >> 52) - 1023;
-    const uint64_t mant = (1ull << 52) - 1ull;
-    int k = el - ea - ((d & mant) > (l & mant) ? 1 : 0);
-    return k < -126 ? -126 : (k > 127 ? 127 : k);
-}
-
-// max over the `lanes` (a power of two <= 64, wave-uniform) adjacent lanes of a group; every
-// lane of the wave must reach it
-__device__ __forceinline__ uint32_t group_max(uint32_t m, int lanes) {
-    for (int off = 1; off < lanes; off <<= 1) m = umax(m, (uint32_t)__shfl_xor((int)m, off, 64));
-    return m;
 }
 
 // ---------------------------------------------------------------------------
@@ -498,14 +465,6 @@ inline bool vec_v(int V, int& shift) {
     return true;
 }
 int check_v(int V) { return V < 1 ? set_error(INA_EINVAL, "V must be >= 1%s", "") : INA_OK; }
-// ina_scale_for's rule for the number of summands
-int scale_lim(int degree, int bits, double& lim) {
-    if (bits != 16 && bits != 32) return set_error(INA_EINVAL, "bits must be 16 or 32%s", "");
-    if (degree < 1) return set_error(INA_EINVAL, "degree must be >= 1%s", "");
-    lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)degree - 0.5;
-    if (lim <= 0.0) return set_error(INA_EINVAL, "too many summands (degree) for this width%s", "");
-    return INA_OK;
-}
 int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) {
     lim = 1.0;
     if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)

@@ -207,4 +207,54 @@ __device__ __forceinline__ uint32_t rne16x2(float lo, float hi) {
     return rne16<XT>(lo) | (rne16<XT>(hi) << 16);
 }
 
+// ---------------------------------------------------------------------------
+// per-block scales (include/ina_blk.h): shared by ina_blk.hip and the block-scaled packet
+// kernels of ina_kernels.hip
+// ---------------------------------------------------------------------------
+// a given scale: -127 / -128 read as -126
+__device__ __forceinline__ int rd_k(const int8_t* __restrict__ kblk, size_t s) {
+    const int k = kblk[s];
+    return k < -126 ? -126 : k;
+}
+// 2^k for k in [-127, 127], built from its bits: 2^-127 is the subnormal 0x00400000 (ldexpf(1, -127)),
+// which an exp2 / division would flush or round
+__device__ __forceinline__ float pow2f(int k) {
+    return __uint_as_float(k >= -126 ? (uint32_t)(k + 127) << 23 : 0x00400000u);
+}
+// |d| as its bit pattern, NaN -> 0
+__device__ __forceinline__ uint32_t absbits(float d) {
+    const uint32_t u = __float_as_uint(d) & 0x7FFFFFFFu;
+    return u > 0x7F800000u ? 0u : u;
+}
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t fold4(uint32_t m, f32x4_t a) {
+    return umax(umax(m, absbits(a.x)), umax(umax(absbits(a.y), absbits(a.z)), absbits(a.w)));
+}
+
+// ina_scale_for(amax, degree, bits) for amax given as its bits and lim = (2^(bits-1) - 1) / degree
+// - 1/2 as the host computed it: the largest k in [-126, 127] with amax * 2^k <= lim (-126 if
+// none).  amax = ma * 2^ea, lim = ml * 2^el with ma, ml in [1, 2): k = el - ea when ma <= ml, else
+// el - ea - 1 -- exponents and mantissas compared as integers, so the answer is the host's exact
+// double comparison for every fp32 amax (an fp32 mantissa, subnormal ones included, converts to
+// double exactly).
+__device__ __forceinline__ int scale_of(uint32_t u, double lim) {
+    if (u == 0u) return 127;
+    if (u >= 0x7F800000u) return -126;
+    const uint32_t e = u >> 23, m = u & 0x7FFFFFu;
+    const uint64_t d = (uint64_t)__double_as_longlong((double)(e ? (m | 0x800000u) : m));   // exact
+    const int ea = (int)(d >> 52) - 1023 + (int)(e ? e : 1u) - 150;
+    const uint64_t l = (uint64_t)__double_as_longlong(lim);
+    const int el = (int)(l >> 52) - 1023;
+    const uint64_t mant = (1ull << 52) - 1ull;
+    int k = el - ea - ((d & mant) > (l & mant) ? 1 : 0);
+    return k < -126 ? -126 : (k > 127 ? 127 : k);
+}
+
+// max over the `lanes` (a power of two <= 64, wave-uniform) adjacent lanes of a group; every
+// lane of the wave must reach it
+__device__ __forceinline__ uint32_t group_max(uint32_t m, int lanes) {
+    for (int off = 1; off < lanes; off <<= 1) m = umax(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    return m;
+}
+
 }  // namespace ina

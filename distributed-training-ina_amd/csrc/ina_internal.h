@@ -31,6 +31,9 @@ int ew_grid_cap();            // ina_kernels.hip: grid cap of the elementwise ke
 int default_grid_cap();       // ina_kernels.hip: grid cap of the default-cap kernels (tuning key 0)
 int stream_grid_cap();        // ina_kernels.hip: grid cap of the flat packet kernels (tuning key 4)
 int combine_ina_grid_cap();   // ina_kernels.hip: grid cap of the INA combines, blk one included (tuning key 6)
+// ina_blk.hip: ina_scale_for's rule for `degree` summands at `bits` (16 or 32): lim = (2^(bits-1) - 1) /
+// degree - 1/2, INA_EINVAL when it is not positive
+int scale_lim(int degree, int bits, double& lim);
 int check_x16_type(int xtype);   // ina_x16.hip: INA_OK for INA_X16_BF16 / INA_X16_F16, else INA_EINVAL
 // checked builds (INA_STORE_CHECK, ina_device.h): each source's stream_store contract
 // violations since the last read, cleared by the read

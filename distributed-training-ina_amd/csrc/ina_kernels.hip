@@ -846,6 +846,30 @@ struct SrcX16 {
                      (uint32_t)q32(a.w, s)};
     }
 };
+// SrcQ32 with one scale per packet (include/ina_pkt_blk.h): element e belongs to packet e / V and is
+// quantised with 2^kblk[e / V] (-127 / -128 read as -126).  four() is only called on a chunk of one
+// packet (V % 4 == 0 on the vector paths), so it is one scale-byte load per lane per chunk, the
+// same address across a packet's lanes.  shift = log2(V) for a power of two, else -1 (a division).
+struct SrcQ32B {
+    const float* __restrict__ x;
+    const float* __restrict__ base;   // may be null
+    const int8_t* __restrict__ kblk;
+    uint32_t V;
+    int shift;
+    // off is a whole number of packets (pack_nga_launch's packet ranges)
+    SrcQ32B shifted(size_t off) const {
+        return SrcQ32B{x + off, base ? base + off : nullptr, kblk + off / V, V, shift};
+    }
+    __device__ __forceinline__ float scale(size_t e) const {
+        return pow2f(rd_k(kblk, shift >= 0 ? e >> shift : e / V));
+    }
+    __device__ __forceinline__ uint32_t one(size_t e) const {
+        return SrcQ32{x, base, scale(e)}.one(e);
+    }
+    __device__ __forceinline__ u32x4 four(size_t e) const {
+        return SrcQ32{x, base, scale(e)}.four(e);
+    }
+};
 // sources that quantise on the fly (the fused worker packs) against stored int32 words
 template <typename Src> constexpr bool kQuantSrc = !std::is_same_v<Src, SrcI32>;
 
@@ -1273,6 +1297,85 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackSplit a, 
     }
 }
 
+// k_qpack_nga_multi_split with one scale per packet (include/ina_pkt_blk.h).  Chunk t belongs to
+// packet t >> shift (L = V/4 = 1 << shift chunks a packet; shift < 0: t / L, given scales only).
+// GIVEN reads kblk[packet] (one byte load per lane per chunk, one address per packet).  AUTO
+// (V a power of two in [8, 256], G = all the call's workers) holds the lane's G delta chunks in
+// registers, takes the packet's max |delta| with the butterfly of ina_blk.hip's AUTO reduce over
+// the packet's L adjacent lanes, writes kblk[packet] and quantises the held chunks: each bucket
+// is read once.  The loop is wave-uniform (t0 steps whole waves); lanes past the last chunk
+// contribute 0 to the butterfly and store nothing.
+template <int G, bool AUTO>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackSplit a, const float* __restrict__ base,
+                                                                      size_t n, int8_t* __restrict__ kblk,
+                                                                      double lim, int shift, uint32_t L,
+                                                                      uint32_t num_slots, size_t nch, size_t np) {
+    const size_t gs = (size_t)gridDim.x * kBlock;
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (size_t t0 = tid & ~(size_t)63; t0 < nch; t0 += gs) {         // wave-uniform
+        const size_t t = t0 + (size_t)lane, e0 = 4 * t;
+        if constexpr (!AUTO) {
+            if (t >= nch) continue;                    // no cross-lane step below
+        }
+        int k = 0;
+        if constexpr (!AUTO) k = rd_k(kblk, shift >= 0 ? t >> shift : t / L);
+        // worker g's chunk of deltas, quantised with 2^kk, into its payload row
+        auto put = [&](int g, f32x4 y, int kk) {
+            const float s = pow2f(kk);
+            const u32x4 q{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s), (uint32_t)q32(y.w, s)};
+            packet_store(bswap4(q), a.pay[g] + t);
+        };
+        f32x4 d[G];
+        if (e0 + 4 <= n) {
+            f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
+#pragma unroll
+            for (int g = 0; g < G; ++g) d[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
+            if (base) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    d[g].x = __fsub_rn(d[g].x, b.x); d[g].y = __fsub_rn(d[g].y, b.y);
+                    d[g].z = __fsub_rn(d[g].z, b.z); d[g].w = __fsub_rn(d[g].w, b.w);
+                }
+            }
+            if constexpr (!AUTO) {                     // given scales: nothing to wait for
+#pragma unroll
+                for (int g = 0; g < G; ++g) put(g, d[g], k);
+            }
+        } else {                                       // the bucket's last chunk and the zero tail
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                d[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (e0 < n) d[g].x = base ? __fsub_rn(a.x[g][e0], base[e0]) : a.x[g][e0];
+                if (e0 + 1 < n) d[g].y = base ? __fsub_rn(a.x[g][e0 + 1], base[e0 + 1]) : a.x[g][e0 + 1];
+                if (e0 + 2 < n) d[g].z = base ? __fsub_rn(a.x[g][e0 + 2], base[e0 + 2]) : a.x[g][e0 + 2];
+                if constexpr (!AUTO) put(g, d[g], k);
+            }
+        }
+        if constexpr (AUTO) {
+            uint32_t m = 0u;
+#pragma unroll
+            for (int g = 0; g < G; ++g) m = fold4(m, d[g]);
+            m = group_max(m, 1 << shift);
+            k = scale_of(m, lim);
+            if (t < nch && (lane & ((1 << shift) - 1)) == 0) kblk[t >> shift] = (int8_t)k;
+            if (t >= nch) continue;
+#pragma unroll
+            for (int g = 0; g < G; ++g) put(g, d[g], k);
+        }
+    }
+    for (size_t p = tid; p < np; p += gs) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const u32x4 r = nga_hdr_row(a.bitmap[g], a.fcs[g], a.seq0[g] + (uint32_t)p, num_slots);
+            packet_store(r, a.hdr[g] + p);
+            if (a.desc[g]) a.desc[g][p] = u32x2{r.y, r.z};
+        }
+    }
+}
+
 // the same from bf16 / fp16 buckets (ina.h INA_X16_*): 8-byte worker loads, the fp32 base
 // chunk still read once per group
 struct QPackSplitX16 {
@@ -1550,15 +1653,22 @@ static_assert(64 % INA_APPLY_WIN == 0, "windows tile the wave's 64 lanes");
 constexpr int kApB = INA_APPLY_BATCH;
 constexpr int kApWin = INA_APPLY_WIN;   // packets per window (<= 64)
 
+// BLK (include/ina_pkt_blk.h): the dequantise scale is 2^-kblk[slot], one wave-uniform byte load
+// per completed packet (the slot comes out of readfirstlane), in place of `inv`.
+// SPLIT: split rows (ina_switch_batch_t's convention): pkts = 16-byte header rows (pstride 16), pay
+// = 4V-byte payload rows.  Lane l reads the aligned chunk l of the payload row and byte-swaps it;
+// windows, batches, the local-row prefetch, the update and the stores are the packed kernel's.
+template <bool BLK, bool SPLIT>
 __global__ __launch_bounds__(kBlock) void k_apply_completed_nga(
         const uint8_t* __restrict__ pkts, uint32_t npk, uint32_t pstride,
         const uint8_t* __restrict__ actions, uint32_t seq0, uint32_t nslots,
         const float* __restrict__ local, float inv, float ws, float* __restrict__ out, size_t n,
-        uint8_t* __restrict__ acks, size_t ack_stride, int V) {
+        uint8_t* __restrict__ acks, size_t ack_stride, int V,
+        const int8_t* __restrict__ kblk, const uint8_t* __restrict__ pay) {
     const int lane = threadIdx.x & 63;
     const int L = V >> 2;
     const bool vl = lane < L;
-    const int chn = 1 + (vl ? lane : 0);
+    [[maybe_unused]] const int chn = 1 + (vl ? lane : 0);
     const uint32_t wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t nwaves = (gridDim.x * kBlock) >> 6;
 #if INA_APPLY_MW
@@ -1598,7 +1708,11 @@ __global__ __launch_bounds__(kBlock) void k_apply_completed_nga(
             for (int b = 0; b < kApB; ++b) {
                 const u32x4* pk = reinterpret_cast<const u32x4*>(pkts + (size_t)pid[b] * pstride);
                 hv[b] = pk[0];
-                a[b] = __builtin_nontemporal_load(pk + chn);
+                if constexpr (SPLIT)
+                    a[b] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pay + (size_t)pid[b] * 4 * (size_t)V) +
+                                                      (vl ? lane : 0));
+                else
+                    a[b] = __builtin_nontemporal_load(pk + chn);
             }
             // slots from the headers, then every local row of the batch in flight at once
             uint32_t slot[kApB];
@@ -1615,18 +1729,23 @@ __global__ __launch_bounds__(kBlock) void k_apply_completed_nga(
 #pragma unroll
             for (int b = 0; b < kApB; ++b) {
                 if (slot[b] >= nslots) continue;               // past the batch, or not this bucket
+                if constexpr (BLK) inv = pow2f(-rd_k(kblk, slot[b]));
                 if (lane == 0 && acks) {
                     u32x4 hd = hv[b];
                     hd.y = (hd.y & ~0xFF00u) | ((uint32_t)INA_FLAG_ACK << 8);
                     *reinterpret_cast<u32x4*>(acks + (size_t)slot[b] * ack_stride) = hd;
                 }
-                const uint32_t pw = (uint32_t)__builtin_amdgcn_update_dpp((int)hv[b].w, (int)a[b].w,
-                                                                          0x138, 0xF, 0xF, false);
+                [[maybe_unused]] const uint32_t pw = (uint32_t)__builtin_amdgcn_update_dpp((int)hv[b].w, (int)a[b].w,
+                                                                                           0x138, 0xF, 0xF, false);
                 uint32_t v[4];
-                v[0] = __builtin_amdgcn_perm(a[b].x, pw, kSelBE);
-                v[1] = __builtin_amdgcn_perm(a[b].y, a[b].x, kSelBE);
-                v[2] = __builtin_amdgcn_perm(a[b].z, a[b].y, kSelBE);
-                v[3] = __builtin_amdgcn_perm(a[b].w, a[b].z, kSelBE);
+                if constexpr (SPLIT) {
+                    v[0] = bswap(a[b].x); v[1] = bswap(a[b].y); v[2] = bswap(a[b].z); v[3] = bswap(a[b].w);
+                } else {
+                    v[0] = __builtin_amdgcn_perm(a[b].x, pw, kSelBE);
+                    v[1] = __builtin_amdgcn_perm(a[b].y, a[b].x, kSelBE);
+                    v[2] = __builtin_amdgcn_perm(a[b].z, a[b].y, kSelBE);
+                    v[3] = __builtin_amdgcn_perm(a[b].w, a[b].z, kSelBE);
+                }
                 if (!vl) continue;
                 const size_t e = (size_t)slot[b] * (size_t)V + 4 * (size_t)lane;
                 if (e + 4 <= n) {
@@ -1882,7 +2001,9 @@ using namespace ina;
 template <typename Src>
 static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina_nga_params_t* prm,
                            const uint8_t* ovf, uint8_t* pkts, size_t pstride, hipStream_t s,
-                           uint64_t* desc = nullptr) {
+                           uint64_t* desc = nullptr, int cap = 0) {
+    // cap > 0 (the block-scaled pack): the vector kernels' grids are held under it as well, so
+    // tuning key 0 reaches their grid-stride loops
     if (!prm || prm->V <= 0 || prm->num_slots == 0)
         return set_error(INA_EINVAL, "bad nga params%s", "");
     const int V = prm->V;
@@ -1907,13 +2028,13 @@ static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina
             // packet: one 16-byte load per lane leaves too little in flight),
             // profiles/r03/lab/pack_ppw_lab.log
             if (INA_PACK_PPW && kQuantSrc<Src> && V == 256 && C <= 65 + 64) {
-                hipLaunchKernelGGL((k_pack_nga_v256<Src>), dim3(grid_for(np * 64, 1, 1 << 20)), dim3(kBlock), 0, s,
+                hipLaunchKernelGGL((k_pack_nga_v256<Src>), dim3(grid_for(np * 64, 1, cap > 0 ? cap : 1 << 20)), dim3(kBlock), 0, s,
                                    src.shifted(v0), n - v0, hp, ovf ? ovf + p0 : nullptr, pkts + p0 * pstride,
                                    (uint32_t)pstride, (uint32_t)np,
                                    desc ? reinterpret_cast<u32x2*>(desc + p0) : nullptr);
                 continue;
             }
-            hipLaunchKernelGGL((k_pack_nga_flat<Src, INA_PACK_U>), dim3(grid_for(np * C, INA_PACK_U, g_stream_blocks)),
+            hipLaunchKernelGGL((k_pack_nga_flat<Src, INA_PACK_U>), dim3(grid_for(np * C, INA_PACK_U, cap > 0 ? std::min(cap, g_stream_blocks.load()) : g_stream_blocks.load())),
                                dim3(kBlock), 0, s, src.shifted(v0), n - v0, hp, ovf ? ovf + p0 : nullptr,
                                pkts + p0 * pstride, (uint32_t)C, (uint32_t)(V / 4), (uint32_t)(np * C),
                                desc ? reinterpret_cast<u32x2*>(desc + p0) : nullptr);
@@ -2544,10 +2665,132 @@ int ina_apply_completed_nga(const uint8_t* pkts, size_t npk, int V, size_t pstri
     const uint32_t ns32 = nslots > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)nslots;
     const size_t windows = (npk + kApWin - 1) / kApWin;
     unsigned g = (unsigned)std::min<size_t>((windows + 3) / 4, 2048);
-    hipLaunchKernelGGL(k_apply_completed_nga, dim3(g), dim3(kBlock), 0, hs(stream), pkts,
+    hipLaunchKernelGGL((k_apply_completed_nga<false, false>), dim3(g), dim3(kBlock), 0, hs(stream), pkts,
                        (uint32_t)npk, (uint32_t)pstride, actions, seq0, ns32, local,
-                       ldexpf(1.0f, -k), (float)weight_step, out, n, acks, ack_stride, V);
+                       ldexpf(1.0f, -k), (float)weight_step, out, n, acks, ack_stride, V,
+                       (const int8_t*)nullptr, (const uint8_t*)nullptr);
     return check_launch("apply_completed_nga");
+}
+
+// ---- per-block scales on the packet path (include/ina_pkt_blk.h) --------------------------------
+int ina_quantize_pack_nga_blk_desc(const float* x, const float* base, size_t n, const int8_t* kblk,
+                                   const ina_nga_params_t* prm, uint8_t* pkts, size_t pstride,
+                                   ina_nga_desc_t* desc, ina_stream_t stream) {
+    if (n && (!x || !kblk)) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (desc && ((uintptr_t)desc & 7u)) return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
+    if (!prm || prm->V <= 0 || prm->num_slots == 0) return set_error(INA_EINVAL, "bad nga params%s", "");
+    const uint32_t V = (uint32_t)prm->V;
+    int shift = -1;
+    if ((V & (V - 1)) == 0)
+        for (shift = 0; (1u << shift) < V; ++shift) {}
+    bool al = aligned16(x) && (!base || aligned16(base));
+    return pack_nga_launch(SrcQ32B{x, base, kblk, V, shift}, al, n, prm, nullptr, pkts, pstride, hs(stream), desc,
+                           default_grid_cap());
+}
+
+int ina_quantize_pack_nga_multi_split_blk(const float* const* x, int W, const float* base, size_t n, int8_t* kblk,
+                                          int mode, int degree, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                          uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
+    if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
+        return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
+    double lim = 1.0;
+    if (mode == INA_BLK_AUTO) {
+        if (int rc = scale_lim(degree, 32, lim)) return rc;
+    }
+    if (!x || !prm || !hdr || !pay || W < 1 || W > INA_MAX_WORKERS)
+        return set_error(INA_EINVAL, "x, prm, hdr, pay non-null and W in [1, %s]", "64");
+    const int V = prm[0].V;
+    if (int rc = split_geometry(V, prm[0].num_slots)) return rc;
+    const size_t npk = (n + (size_t)V - 1) / (size_t)V;
+    if (npk == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (base && !aligned16(base)) return set_error(INA_EINVAL, "base must be 16-byte aligned%s", "");
+    for (int w = 0; w < W; ++w) {
+        if (prm[w].V != V || prm[w].num_slots != prm[0].num_slots)
+            return set_error(INA_EINVAL, "every worker needs the same V and num_slots%s", "");
+        if (!x[w] || !hdr[w] || !pay[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
+        if (!aligned16(x[w]) || !aligned16(hdr[w]) || !aligned16(pay[w]))
+            return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
+        if (desc && (!desc[w] || ((uintptr_t)desc[w] & 7u)))
+            return set_error(INA_EINVAL, "descriptors must be non-null and 8-byte aligned%s", "");
+    }
+    const uint32_t L = (uint32_t)V / 4;
+    int shift = -1;                                    // log2(L) when L is a power of two
+    if ((L & (L - 1)) == 0)
+        for (shift = 0; (1u << shift) < L; ++shift) {}
+    bool autok = mode == INA_BLK_AUTO;
+    // AUTO in the pack's own launch needs a packet to be adjacent lanes of one wave (V a power of
+    // two in [8, 256]) and every worker in one group; otherwise the scales kernel runs first and
+    // the pack reads what it wrote -- the same scales, so the same rows
+    if (autok && !(shift >= 1 && W <= kQpGroup)) {
+        if (int rc = ina_block_scales_f32(x, W, base, n, V, degree, 32, kblk, stream)) return rc;
+        autok = false;
+    }
+    const size_t nch = npk * (size_t)V / 4;
+    const dim3 grid(grid_for(std::max(nch, npk), 1)), blk(kBlock);
+    hipStream_t s = hs(stream);
+    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
+        const int G = std::min(kQpGroup, W - w0);
+        QPackSplit a{};
+        for (int g = 0; g < G; ++g) {
+            const ina_nga_params_t& q = prm[w0 + g];
+            a.x[g] = x[w0 + g];
+            a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
+            a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
+            a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
+            a.bitmap[g] = q.bitmap;
+            a.seq0[g] = q.seq0;
+            a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
+        }
+        switch (G) {
+#define INA_QPSB(g_)                                                                                             \
+    case g_:                                                                                                     \
+        if (autok)                                                                                               \
+            hipLaunchKernelGGL((k_qpack_nga_multi_split_blk<g_, true>), grid, blk, 0, s, a, base, n, kblk, lim,  \
+                               shift, L, prm[0].num_slots, nch, npk);                                            \
+        else                                                                                                     \
+            hipLaunchKernelGGL((k_qpack_nga_multi_split_blk<g_, false>), grid, blk, 0, s, a, base, n, kblk, lim, \
+                               shift, L, prm[0].num_slots, nch, npk);                                            \
+        break;
+            INA_QPSB(1) INA_QPSB(2) INA_QPSB(3) INA_QPSB(4) INA_QPSB(5) INA_QPSB(6) INA_QPSB(7) INA_QPSB(8)
+#undef INA_QPSB
+        }
+    }
+    return check_launch("quantize_pack_nga_multi_split_blk");
+}
+
+int ina_apply_completed_nga_blk(const uint8_t* rows, const uint8_t* pay, size_t npk, int V, size_t pstride,
+                                const uint8_t* actions, uint32_t seq0, const float* local, const int8_t* kblk,
+                                double weight_step, float* out, size_t n, uint8_t* acks, size_t ack_stride,
+                                ina_stream_t stream) {
+    if (V <= 0 || V % 4 || V > 256) return set_error(INA_EINVAL, "V must be a multiple of 4 <= 256%s", "");
+    if (pay) {
+        if (pstride != 16 || !aligned16(rows) || !aligned16(pay))
+            return set_error(INA_EINVAL, "split rows: 16-byte header rows (stride 16) and 4V-byte payload rows, both "
+                                         "16-byte aligned%s", "");
+    } else if (pstride % 16 || pstride < (size_t)INA_NGA_HDR_BYTES + 4u * (size_t)V || !aligned16(rows)) {
+        return set_error(INA_EINVAL, "packets must be 16-byte aligned rows of stride %% 16 == 0%s", "");
+    }
+    if (acks && (ack_stride % 16 || !aligned16(acks)))
+        return set_error(INA_EINVAL, "ack rows must be 16-byte aligned%s", "");
+    if (npk == 0 || n == 0) return INA_OK;
+    if (npk > 0x7FFFFFFFu || pstride > 0xFFFFFFFFu) return set_error(INA_EINVAL, "too many packets%s", "");
+    if (!rows || !actions || !local || !out || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (!aligned16(local) || !aligned16(out)) return set_error(INA_EINVAL, "local/out must be 16-byte aligned%s", "");
+    const size_t nslots = (n + (size_t)V - 1) / (size_t)V;
+    const uint32_t ns32 = nslots > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)nslots;
+    const size_t windows = (npk + kApWin - 1) / kApWin;
+    // the sibling's grid, held under tuning key 0 as well
+    unsigned g = (unsigned)std::min<size_t>((windows + 3) / 4, (size_t)std::min(2048, default_grid_cap()));
+    if (pay)
+        hipLaunchKernelGGL((k_apply_completed_nga<true, true>), dim3(g), dim3(kBlock), 0, hs(stream), rows,
+                           (uint32_t)npk, (uint32_t)pstride, actions, seq0, ns32, local, 1.0f, (float)weight_step,
+                           out, n, acks, ack_stride, V, kblk, pay);
+    else
+        hipLaunchKernelGGL((k_apply_completed_nga<true, false>), dim3(g), dim3(kBlock), 0, hs(stream), rows,
+                           (uint32_t)npk, (uint32_t)pstride, actions, seq0, ns32, local, 1.0f, (float)weight_step,
+                           out, n, acks, ack_stride, V, kblk, pay);
+    return check_launch("apply_completed_nga_blk");
 }
 
 int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id, uint32_t aggregator_index,

@@ -140,6 +140,12 @@ SIGNATURES_BLK = {
     "ina_ps_apply_blk_i32": [_vp, _vp, _vp, _i, _d, _vp, _sz, _vp],
     "ina_ps_combine_ina_blk_f32": [_vp, _vp, _i, _i, _d, _vp, _sz, _vp, _vp],
 }
+# the per-block-scale entry points of the packet path (include/ina_pkt_blk.h)
+SIGNATURES_PKT_BLK = {
+    "ina_quantize_pack_nga_blk_desc": [_vp, _vp, _sz, _vp, C.POINTER(NgaParams), _vp, _sz, _vp, _vp],
+    "ina_quantize_pack_nga_multi_split_blk": [_vp, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ina_apply_completed_nga_blk": [_vp, _vp, _sz, _i, _sz, _vp, _u32, _vp, _vp, _d, _vp, _sz, _vp, _sz, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -154,7 +160,7 @@ def open_library(path: str) -> C.CDLL:
     if not os.path.exists(path):
         raise InaError(f"libina.so not built at {path}; run `make -C {CSRC}` or __graft_entry__.build()")
     lib = C.CDLL(path)
-    for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK}.items():
+    for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

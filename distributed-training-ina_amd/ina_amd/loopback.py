@@ -73,12 +73,16 @@ class SwitchStandIn:
         act = routed
         return pk, act
 
-    def aggregate_apply(self, sock, seq0: int, local: torch.Tensor, k: int, weight_step: float,
+    def aggregate_apply(self, sock, seq0: int, local: torch.Tensor, k, weight_step: float,
                         timeout_ms: int = 30000) -> torch.Tensor:
         """Receive, switch, then ONE fused kernel: completed slots -> dequantise -> update
-        (local + weight_step * sum * 2^-k) and PS acks, which then free the slots."""
+        (local + weight_step * sum * 2^-k) and PS acks, which then free the slots.  k: the global
+        exponent, or an int8 tensor of one exponent per slot (the scales the workers packed with)."""
         pk, act = self._switch_batch(sock, timeout_ms)
-        new = ops.apply_completed(pk, act, self.V, seq0, local, k, weight_step, acks=self.acks)
+        if isinstance(k, torch.Tensor):
+            new = ops.apply_completed_blk(pk, act, self.V, seq0, local, k, weight_step, acks=self.acks)
+        else:
+            new = ops.apply_completed(pk, act, self.V, seq0, local, k, weight_step, acks=self.acks)
         self.switch.process(self.acks)
         return new
 
@@ -96,23 +100,49 @@ class SwitchStandIn:
 
 
 def worker_send(sock, params: torch.Tensor, base: torch.Tensor, worker_id: int, W: int, V: int,
-                k: int, seq0: int, switch_id: int = 1, num_slots: int = _lib.NUM_REGISTER) -> int:
+                k, seq0: int, switch_id: int = 1, num_slots: int = _lib.NUM_REGISTER) -> int:
     """Worker data plane: quantise(params - base) + NGA-V pack in one GPU pass, then
     sendmmsg.  num_slots must be the aggregator's pool size (index = seq mod num_slots,
-    DataManager.py:119)."""
-    pk = ops.quantize_pack_nga(params.reshape(-1).contiguous(), k, V, bitmap=worker_id, count=W,
-                               switch_id=switch_id, seq0=seq0, base=base.reshape(-1).contiguous(),
-                               num_slots=num_slots)
+    DataManager.py:119).  k: the global exponent, or an int8 tensor of one exponent per packet
+    (agree_block_scales)."""
+    pack = ops.quantize_pack_nga_blk if isinstance(k, torch.Tensor) else ops.quantize_pack_nga
+    pk = pack(params.reshape(-1).contiguous(), k, V, bitmap=worker_id, count=W,
+              switch_id=switch_id, seq0=seq0, base=base.reshape(-1).contiguous(),
+              num_slots=num_slots)
     return send_device_packets(sock, pk, _lib.NGA_HDR_BYTES + 4 * V)
+
+
+def agree_block_scales(conns, mine: torch.Tensor | None = None, device=None) -> torch.Tensor:
+    """The per-packet scales of one bucket, agreed over the control connections (ps.send_data
+    framing): every worker sends its int8 scales, the PS takes the element-wise MIN (include/ina_blk.h:
+    a scale no worker overflows at) and returns it to every worker.
+      worker: agree_block_scales(ctl, mine) -- ctl its connection, mine its ops.block_scales(
+              [p], V, bits=32, degree=W, base=glob); returns the agreed scales on mine's device.
+      PS:     agree_block_scales(conns, device=dev) -- the W connections; returns them on dev."""
+    if mine is not None:
+        ps.send_data(conns, mine.cpu())
+        return ps.get_data(conns).to(mine.device)
+    got = [ps.get_data(c) for c in conns]
+    for g in got:
+        if not isinstance(g, torch.Tensor) or g.dtype != torch.int8 or g.shape != got[0].shape:
+            raise ValueError("block scales: every worker sends one int8 tensor of the same length")
+    agreed = torch.stack(got).amin(dim=0)
+    for c in conns:
+        ps.send_data(c, agreed)
+    return agreed.to(device) if device is not None else agreed
 
 
 def seq_base(epoch: int, npk: int) -> int:
     return (1 + epoch * npk) & 0xFFFFFFFF      # send_data numbers from 1 (DataManager.py:106)
 
 
-def ps_serve(model, W: int, epochs: int, tcp_port: int, data_path: str, k: int = 16,
-             V: int = 256, on_epoch=None, timeout_ms: int = 60000):
-    """PS side (master_loop's epoch, launch.py:209-242, with the INA data plane)."""
+def ps_serve(model, W: int, epochs: int, tcp_port: int, data_path: str, k=16,
+             V: int = 256, on_epoch=None, timeout_ms: int = 60000, on_listen=None):
+    """PS side (master_loop's epoch, launch.py:209-242, with the INA data plane).  k: the global
+    exponent of every epoch, or "block": one exponent per packet, agreed with the workers each epoch
+    (agree_block_scales) before they pack.  on_listen() is called once both sockets accept peers."""
+    if isinstance(k, str) and k != "block":
+        raise ValueError(f"unknown k {k!r}: an integer exponent or 'block'")
     dev = next(model.parameters()).device
     local = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
     n = local.numel()
@@ -126,6 +156,8 @@ def ps_serve(model, W: int, epochs: int, tcp_port: int, data_path: str, k: int =
     srv.listen(W)
     conns = []
     try:
+        if on_listen:
+            on_listen()
         for _ in range(W):
             c, _ = srv.accept()
             conns.append(c)
@@ -134,7 +166,8 @@ def ps_serve(model, W: int, epochs: int, tcp_port: int, data_path: str, k: int =
                              "num_slots": sw.num_slots})
         for epoch in range(epochs):
             t0 = time.time()
-            new = sw.aggregate_apply(data, seq_base(epoch, sw.npk), local, k, 1.0 / (W + 1),
+            ke = agree_block_scales(conns, device=dev) if k == "block" else k
+            new = sw.aggregate_apply(data, seq_base(epoch, sw.npk), local, ke, 1.0 / (W + 1),
                                      timeout_ms)
             t_agg = time.time()
             torch.nn.utils.vector_to_parameters(new, model.parameters())
@@ -168,7 +201,10 @@ def worker_serve(idx: int, W: int, tcp_port: int, data_path: str, make_model, tr
         for epoch in range(epochs):
             train_step(model, idx, epoch)
             p = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
-            worker_send(data, p, glob, idx + 1, W, V, k, seq_base(epoch, npk),
+            ke = k
+            if k == "block":
+                ke = agree_block_scales(ctl, ops.block_scales([p], V, bits=32, degree=W, base=glob))
+            worker_send(data, p, glob, idx + 1, W, V, ke, seq_base(epoch, npk),
                         num_slots=cfg["num_slots"])
             glob = ps.get_data(ctl).to(device)
             torch.nn.utils.vector_to_parameters(glob, model.parameters())

@@ -14,7 +14,8 @@ These are the kernels that replace the reference's CPU / switch arithmetic:
   pack_c128                  send_gradients' packet loop (communicator.cc:23-37)
   ps_combine                 aggregate() (launch.py:42-52)
   absmax / scale_for         per-bucket dynamic scale for the quantiser (build-defined)
-  block_scales / *_blk       one scale per block of V values instead (include/ina_blk.h)
+  block_scales / *_blk       one scale per block of V values instead (include/ina_blk.h); on the
+                             packet path the block is the packet (include/ina_pkt_blk.h)
 """
 from __future__ import annotations
 
@@ -956,6 +957,115 @@ def ps_combine_ina_blk(local: torch.Tensor, paras, V: int, weight_step: float, o
     check(load().ina_ps_combine_ina_blk_f32(local.data_ptr(), arr, len(paras), V, float(weight_step),
                                             out.data_ptr(), n, kblk_out.data_ptr() if kblk_out is not None else None,
                                             _stream(local)), "ps_combine_ina_blk")
+    return out
+
+
+# -- per-block scales on the packet path (include/ina_pkt_blk.h): the block is the packet ----------
+def quantize_pack_nga_blk(x: torch.Tensor, kblk: torch.Tensor, V: int, bitmap: int, count: int, switch_id: int,
+                          seq0: int, base: torch.Tensor | None = None, flags: int = 0,
+                          num_slots: int = NUM_REGISTER, stride: int | None = None,
+                          out: torch.Tensor | None = None, desc=None):
+    """quantize_pack_nga() with packet p's payload scaled by 2^kblk[p] (int8, one per packet; -127 /
+    -128 read as -126).  Returns what quantize_pack_nga returns."""
+    V = _blk_v(V)
+    _blk_f32(x, "x")
+    if base is not None:
+        _blk_f32(base, "base")
+        if base.numel() != x.numel():
+            raise ValueError("base and x differ in length")
+        _same_device(x, base)
+    stride = stride or nga_stride(V)
+    npk = (x.numel() + V - 1) // V
+    kblk = _blk_scales_arg(kblk, npk, x, given=True)
+    out = torch.empty((npk, stride), dtype=torch.uint8, device=x.device) if out is None else out
+    _req(out, torch.uint8, "out")
+    _fits(out, npk * stride)
+    _same_device(x, out)
+    prm = _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
+                         seq0 & 0xFFFFFFFF, num_slots, V)
+    d = _desc_arg(desc, npk, x.device)
+    check(load().ina_quantize_pack_nga_blk_desc(x.data_ptr(), base.data_ptr() if base is not None else None,
+                                                x.numel(), kblk.data_ptr(), C.byref(prm), out.data_ptr(), stride,
+                                                d.data_ptr() if d is not None else None, _stream(x)),
+          "quantize_pack_nga_blk")
+    return (out, d) if d is not None else out
+
+
+def quantize_pack_nga_multi_split_blk(xs, V: int, bitmaps, count: int, switch_id: int, seq0,
+                                      base: torch.Tensor | None = None, kblk: torch.Tensor | None = None,
+                                      degree: int | None = None, kblk_out: torch.Tensor | None = None,
+                                      flags: int = 0, num_slots: int = NUM_REGISTER, hdrs=None, pays=None,
+                                      descs=None):
+    """quantize_pack_nga_multi_split() with one scale per packet: returns (hdrs, pays, kblk) or (hdrs,
+    pays, descs, kblk).  kblk=None computes the scales in the same call from these workers' deltas
+    xs[w] - base for `degree` summands (default: their number) and returns them (in kblk_out when
+    given); a given kblk is read."""
+    V = _blk_v(V)
+    xs, n = _blk_bufs(xs, "xs")
+    W, dev = len(xs), xs[0].device
+    if base is not None:
+        _blk_f32(base, "base")
+        if base.numel() != n:
+            raise ValueError("base and xs differ in length")
+        _same_device(xs[0], base)
+    bitmaps = list(bitmaps)
+    seqs = [int(seq0)] * W if isinstance(seq0, numbers.Integral) else list(seq0)
+    if len(bitmaps) != W or len(seqs) != W:
+        raise ValueError("one bitmap and one seq0 per worker")
+    npk = (n + V - 1) // V
+    mode = _lib.BLK_AUTO if kblk is None else _lib.BLK_GIVEN
+    degree = _blk_degree(degree, W, 32) if kblk is None else 1
+    kblk = _blk_scales_arg(kblk if kblk is not None else kblk_out, npk, xs[0])
+    hdrs = [None] * W if hdrs is None else list(hdrs)
+    pays = [None] * W if pays is None else list(pays)
+    if len(hdrs) != W or len(pays) != W:
+        raise ValueError("one header and one payload array per worker")
+    rows = [_split_rows(npk, V, dev, h, p) for h, p in zip(hdrs, pays)]
+    hdrs, pays = [r[0] for r in rows], [r[1] for r in rows]
+    _same_device(xs[0], *hdrs, *pays)
+    ds = None
+    if descs is not None and descs is not False:
+        if descs is not True and (len(descs) != W or any(d is None for d in descs)):
+            raise ValueError("descs: True, or one int64 tensor per worker")
+        ds = [_desc_arg(True if descs is True else descs[w], npk, dev) for w in range(W)]
+    prm = (_lib.NgaParams * W)(*[_lib.NgaParams(bitmaps[w] & 0xFFFFFFFF, count & 0xFF, flags & 0xFF,
+                                                switch_id & 0xFF, 0, seqs[w] & 0xFFFFFFFF, num_slots, V)
+                                 for w in range(W)])
+    check(load().ina_quantize_pack_nga_multi_split_blk(
+        ptr_array([x.data_ptr() for x in xs]), W, base.data_ptr() if base is not None else None, n,
+        kblk.data_ptr(), mode, degree, prm, ptr_array([h.data_ptr() for h in hdrs]),
+        ptr_array([p.data_ptr() for p in pays]),
+        ptr_array([d.data_ptr() for d in ds]) if ds is not None else None, _stream(xs[0])),
+        "quantize_pack_nga_multi_split_blk")
+    return (hdrs, pays, ds, kblk) if ds is not None else (hdrs, pays, kblk)
+
+
+def apply_completed_blk(pkts: torch.Tensor, actions: torch.Tensor, V: int, seq0: int, local: torch.Tensor,
+                        kblk: torch.Tensor, weight_step: float, out=None, acks=None, pay=None):
+    """apply_completed() with slot s dequantised by 2^-kblk[s] (int8, one per slot of local).  pay=None:
+    pkts are packed rows [npkts, stride].  With pay ([npkts, 4V] uint8) pkts are the 16-byte header
+    rows [npkts, 16] of split rows."""
+    V = _blk_v(V)
+    _req(pkts, torch.uint8, "pkts")
+    _req(actions, torch.uint8, "actions")
+    _blk_f32(local, "local")
+    out = torch.empty_like(local) if out is None else out
+    _fits(out, local.numel())
+    _check_apply(pkts, actions, V, local, out, acks)
+    npk, stride = pkts.shape
+    if pay is not None:
+        _split_rows(npk, V, pkts.device, pkts, pay)
+        _same_device(pkts, pay)
+    elif stride < NGA_HDR_BYTES + 4 * V:
+        raise ValueError("pkts rows are shorter than 15 + 4V bytes")
+    kblk = _blk_scales_arg(kblk, -(-local.numel() // V), local, given=True)
+    ack_ptr, ack_stride = None, 0
+    if acks is not None:
+        ack_ptr, ack_stride = acks.data_ptr(), acks.shape[1]
+    check(load().ina_apply_completed_nga_blk(pkts.data_ptr(), pay.data_ptr() if pay is not None else None, npk, V,
+                                             stride, actions.data_ptr(), seq0 & 0xFFFFFFFF, local.data_ptr(),
+                                             kblk.data_ptr(), float(weight_step), out.data_ptr(), local.numel(),
+                                             ack_ptr, ack_stride, _stream(pkts)), "apply_completed_blk")
     return out
 
 

@@ -108,7 +108,9 @@ def main():
     ap.add_argument("--local-steps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--V", type=int, default=256)
-    ap.add_argument("--k", type=int, default=16)
+    ap.add_argument("--k", type=lambda v: v if v == "block" else int(v), default=16,
+                    help="the quantiser's global exponent, or 'block': one exponent per packet, "
+                         "agreed by the workers each epoch")
     ARGS = args = ap.parse_args()
     from ina_amd.loopback import ps_serve
     torch.manual_seed(0)

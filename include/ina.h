@@ -293,6 +293,8 @@ int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npkts, i
  * One exponent per block of V values (block floating point) for the quantiser, the fused
  * reduces and the PS update; the contract is stated in ina_blk.h. */
 #include "ina_blk.h"   /* INA_BLK_GIVEN / INA_BLK_AUTO and the ina_*_blk_* entry points */
+/* The same on the packet path, where the block is the packet: the worker packs and the PS apply. */
+#include "ina_pkt_blk.h"   /* the block-scaled packs and ina_apply_completed_nga_blk */
 
 /* C-128 pack (communicator.cc:23-37): npkts x 524-byte packet_t, all words htonl. */
 int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,

@@ -36,6 +36,10 @@
  * work.  V a power of two in [8, 256] with every buffer 16-byte aligned takes the vector path;
  * any other V or alignment takes a slower path with identical results.  out may alias bufs[0]
  * where the sibling allows it, and local in the PS calls.
+ *
+ * The packet path (the NGA packs and the PS apply of completed packets, where a block is one
+ * packet's payload) takes the same scales under the same contract; its three entry points are
+ * declared in ina_pkt_blk.h, which ina.h includes after this file.
  */
 #ifndef INA_BLK_H
 #define INA_BLK_H

@@ -459,9 +459,8 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs a) {
 // ---------------------------------------------------------------------------
 // the vector path's block sizes; shift = log2(V) - 2
 inline bool vec_v(int V, int& shift) {
-    if (V < 8 || V > 256 || (V & (V - 1))) return false;
-    shift = 0;
-    while ((4 << shift) < V) ++shift;
+    if (V < 8 || V > 256 || log2_exact((uint32_t)V) < 0) return false;
+    shift = log2_exact((uint32_t)V) - 2;
     return true;
 }
 int check_v(int V) { return V < 1 ? set_error(INA_EINVAL, "V must be >= 1%s", "") : INA_OK; }

@@ -67,6 +67,14 @@ inline unsigned grid_for(size_t work_items, int per_thread, int cap_override = 0
     return (unsigned)blocks;
 }
 
+// log2 of a power of two, -1 for anything else
+inline int log2_exact(uint32_t v) {
+    if (v == 0 || (v & (v - 1))) return -1;
+    int s = 0;
+    while ((1u << s) < v) ++s;
+    return s;
+}
+
 inline int check_k(int k) {
     if (k < -126 || k > 127) return set_error(INA_EINVAL, "k out of range [-126,127]%s", "");
     return INA_OK;

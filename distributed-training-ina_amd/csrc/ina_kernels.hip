@@ -799,7 +799,33 @@ struct SrcI32 {
         return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(v + e));
     }
 };
+// The quantise step of every fused pack: the worker's delta x - b where the call has a base (the
+// fp32 op sequence of the PS update, no FMA), then q32 of its four values.
+__device__ __forceinline__ f32x4 delta4(f32x4 x, f32x4 b, bool has_base) {
+    if (has_base) {
+        x.x = __fsub_rn(x.x, b.x); x.y = __fsub_rn(x.y, b.y);
+        x.z = __fsub_rn(x.z, b.z); x.w = __fsub_rn(x.w, b.w);
+    }
+    return x;
+}
+__device__ __forceinline__ u32x4 quant4(f32x4 y, float s) {
+    return u32x4{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s), (uint32_t)q32(y.w, s)};
+}
+// How the split multi pack reads 4 worker values: fp32 as they are, or bf16 / fp16 (ina.h
+// INA_X16_*) widened in registers from one 8-byte load
+struct LdF32 {
+    using X = float;
+    using Raw = f32x4;
+    static __device__ __forceinline__ f32x4 widen4(Raw r) { return r; }
+};
+template <int XT>
+struct LdX16 {
+    using X = uint16_t;
+    using Raw = u32x2;
+    static __device__ __forceinline__ f32x4 widen4(Raw r) { return widen16x4<XT>(r); }
+};
 struct SrcQ32 {
+    using Ld = LdF32;
     const float* __restrict__ x;
     const float* __restrict__ base;   // may be null
     float s;
@@ -814,12 +840,9 @@ struct SrcQ32 {
             // same vector, so it is loaded with the default policy and stays in the
             // Infinity Cache between them (nt: the steady-state 8-worker step 0.690 ->
             // 0.661 ms; one cold pack unchanged; profiles/r03/lab/qpack_base_lab.log)
-            f32x4 b = *reinterpret_cast<const f32x4*>(base + e);
-            a.x = __fsub_rn(a.x, b.x); a.y = __fsub_rn(a.y, b.y);
-            a.z = __fsub_rn(a.z, b.z); a.w = __fsub_rn(a.w, b.w);
+            a = delta4(a, *reinterpret_cast<const f32x4*>(base + e), true);
         }
-        return u32x4{(uint32_t)q32(a.x, s), (uint32_t)q32(a.y, s), (uint32_t)q32(a.z, s),
-                     (uint32_t)q32(a.w, s)};
+        return quant4(a, s);
     }
 };
 
@@ -827,6 +850,7 @@ struct SrcQ32 {
 // (float)x[e], from half the bytes (one 8-byte load per 4 values); base stays fp32
 template <int XT>
 struct SrcX16 {
+    using Ld = LdX16<XT>;
     const uint16_t* __restrict__ x;
     const float* __restrict__ base;   // may be null
     float s;
@@ -838,12 +862,9 @@ struct SrcX16 {
     __device__ __forceinline__ u32x4 four(size_t e) const {
         f32x4 a = widen16x4<XT>(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(x + e)));
         if (base) {                                    // shared: default policy, as in SrcQ32
-            f32x4 b = *reinterpret_cast<const f32x4*>(base + e);
-            a.x = __fsub_rn(a.x, b.x); a.y = __fsub_rn(a.y, b.y);
-            a.z = __fsub_rn(a.z, b.z); a.w = __fsub_rn(a.w, b.w);
+            a = delta4(a, *reinterpret_cast<const f32x4*>(base + e), true);
         }
-        return u32x4{(uint32_t)q32(a.x, s), (uint32_t)q32(a.y, s), (uint32_t)q32(a.z, s),
-                     (uint32_t)q32(a.w, s)};
+        return quant4(a, s);
     }
 };
 // SrcQ32 with one scale per packet (include/ina_pkt_blk.h): element e belongs to packet e / V and is
@@ -905,6 +926,37 @@ constexpr uint32_t kSelWire = 0x07000102u;   // perm(next, v): {v.b2, v.b1, v.b0
 #define INA_UNPACK_HDR_SPLIT 1
 #endif
 
+// The header: the 15 wire bytes of packet `seq` as four little-endian words, byte 15 zero.
+// fcs = count | flags << 8 | switch_id << 16; a descriptor (header bytes 4..11, ina.h) is
+// {row.y, row.z}.  The split kernels and k_nga_make_desc call it.  The packed kernels (chunk 0 /
+// lane 0 beside value 0's top byte, and their descriptor loops) still spell these words out:
+// from this row k_qpack_nga_multi<G> and k_qpack_nga_multi_v256<G> keep their instruction and
+// VGPR counts but come out with the operands of one v_or3_b32 swapped, and their code is held
+// byte-identical.
+__device__ __forceinline__ u32x4 nga_hdr_row(uint32_t bitmap, uint32_t fcs, uint32_t seq, uint32_t num_slots) {
+    const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
+    return u32x4{bswap(bitmap), (fcs & 0xFFFFu) | (bi << 16),
+                 (bi >> 16) | (((fcs >> 16) & 0xFFu) << 16) | (bf << 24), bf >> 8};
+}
+// The ragged tail: the first N words of the chunk at values e0.. of a bucket of n, one value at a time
+// through src.one, zero past n.  N = 3 where the caller's whole chunks take four() (word 3 is then
+// past n), N = 4 where a whole chunk can come this way too.
+template <int N, typename Src>
+__device__ __forceinline__ u32x4 tail4(const Src& src, size_t e0, size_t n) {
+    u32x4 v = u32x4{0u, 0u, 0u, 0u};
+    v.x = e0 < n ? src.one(e0) : 0u;
+    v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
+    v.z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
+    if constexpr (N == 4) v.w = e0 + 3 < n ? src.one(e0 + 3) : 0u;
+    return v;
+}
+// a value chunk on the wire: bytes 2,1,0 of each value and byte 3 of the one after it (nx: the
+// next chunk's first value)
+__device__ __forceinline__ u32x4 wire4(u32x4 v, uint32_t nx) {
+    return u32x4{__builtin_amdgcn_perm(v.y, v.x, kSelWire), __builtin_amdgcn_perm(v.z, v.y, kSelWire),
+                 __builtin_amdgcn_perm(v.w, v.z, kSelWire), __builtin_amdgcn_perm(nx, v.w, kSelWire)};
+}
+
 template <typename Src, int U>
 __global__ __launch_bounds__(kBlock) void k_pack_nga_flat(Src src, size_t n, NgaHdr h,
                                                           const uint8_t* __restrict__ ovf,
@@ -945,9 +997,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_flat(Src src, size_t n, Nga
                 if (e0 + 4 <= n) {
                     v[u] = src.four(e0);
                 } else {                                   // last packet of the bucket: zero tail
-                    v[u].x = e0 < n ? src.one(e0) : 0u;
-                    v[u].y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
-                    v[u].z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
+                    v[u] = tail4<3>(src, e0, n);
                 }
             }
             nx0[u] = 0u;
@@ -977,10 +1027,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_flat(Src src, size_t n, Nga
                 o.w = (bf >> 8) | (nx & 0xFF000000u);        // value 0's top byte at byte 15
                 if (desc && !INA_PACK_DESC_SPLIT) desc[p] = u32x2{o.y, o.z};   // header bytes 4..11 (ina.h)
             } else if (c <= L) {
-                o.x = __builtin_amdgcn_perm(v[u].y, v[u].x, kSelWire);
-                o.y = __builtin_amdgcn_perm(v[u].z, v[u].y, kSelWire);
-                o.z = __builtin_amdgcn_perm(v[u].w, v[u].z, kSelWire);
-                o.w = __builtin_amdgcn_perm(nx, v[u].w, kSelWire);
+                o = wire4(v[u], nx);
             } else {
                 o = u32x4{0u, 0u, 0u, 0u};                   // padding chunks
             }
@@ -999,11 +1046,15 @@ constexpr int kQpGroup = 8;
 // stores: nt like the other packet kernels (write-through and default-policy stores were
 // slower in both layouts, profiles/r03/lab/qpack_multi_lab.log)
 __device__ __forceinline__ void qpm_store(u32x4 v, u32x4* p) { packet_store(v, p); }
+// a group's per-worker header parameters: the last member of the kernel-argument structs
+struct NgaKeys {
+    uint32_t bitmap[kQpGroup], seq0[kQpGroup], fcs[kQpGroup];   // fcs: count | flags<<8 | sw<<16
+};
 struct QPackGroup {
     const float* x[kQpGroup];
     uint8_t* pkts[kQpGroup];
     u32x2* desc[kQpGroup];          // all null or all set
-    uint32_t bitmap[kQpGroup], seq0[kQpGroup], fcs[kQpGroup];   // fcs: count | flags<<8 | sw<<16
+    NgaKeys k;
 };
 
 template <int G>
@@ -1019,9 +1070,9 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi(QPackGroup a, const 
         for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < np; p += gs) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                const uint32_t seq = a.seq0[g] + p;
+                const uint32_t seq = a.k.seq0[g] + p;
                 const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
-                const uint32_t f = a.fcs[g];
+                const uint32_t f = a.k.fcs[g];
                 a.desc[g][p] = u32x2{(f & 0xFFFFu) | (bi << 16),
                                      (bi >> 16) | (((f >> 16) & 0xFFu) << 16) | (bf << 24)};
             }
@@ -1041,18 +1092,10 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi(QPackGroup a, const 
         for (int g = 0; g < G; ++g) {
             v[g] = u32x4{0u, 0u, 0u, 0u};
             if (full) {
-                f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
-                if (base) {
-                    x.x = __fsub_rn(x.x, b.x); x.y = __fsub_rn(x.y, b.y);
-                    x.z = __fsub_rn(x.z, b.z); x.w = __fsub_rn(x.w, b.w);
-                }
-                v[g] = u32x4{(uint32_t)q32(x.x, s), (uint32_t)q32(x.y, s), (uint32_t)q32(x.z, s),
-                             (uint32_t)q32(x.w, s)};
+                const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
+                v[g] = quant4(delta4(x, b, base != nullptr), s);
             } else if (body) {                         // last packet of the bucket: zero tail
-                const SrcQ32 src{a.x[g], base, s};
-                v[g].x = e0 < n ? src.one(e0) : 0u;
-                v[g].y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
-                v[g].z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
+                v[g] = tail4<3>(SrcQ32{a.x[g], base, s}, e0, n);
             }
             nx0[g] = 0u;
             if (lane == 63 && t < nch && c < L) {      // the next chunk's first value
@@ -1067,18 +1110,15 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi(QPackGroup a, const 
             if (t >= nch) continue;
             u32x4 o;
             if (c == 0) {
-                const uint32_t seq = a.seq0[g] + p;
+                const uint32_t seq = a.k.seq0[g] + p;
                 const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
-                const uint32_t f = a.fcs[g];
-                o.x = bswap(a.bitmap[g]);
+                const uint32_t f = a.k.fcs[g];
+                o.x = bswap(a.k.bitmap[g]);
                 o.y = (f & 0xFFFFu) | (bi << 16);
                 o.z = (bi >> 16) | (((f >> 16) & 0xFFu) << 16) | (bf << 24);
                 o.w = (bf >> 8) | (nx & 0xFF000000u);
             } else if (c <= L) {
-                o.x = __builtin_amdgcn_perm(v[g].y, v[g].x, kSelWire);
-                o.y = __builtin_amdgcn_perm(v[g].z, v[g].y, kSelWire);
-                o.z = __builtin_amdgcn_perm(v[g].w, v[g].z, kSelWire);
-                o.w = __builtin_amdgcn_perm(nx, v[g].w, kSelWire);
+                o = wire4(v[g], nx);
             } else {
                 o = u32x4{0u, 0u, 0u, 0u};
             }
@@ -1099,11 +1139,8 @@ __global__ __launch_bounds__(kBlock) void k_nga_make_desc(DescGroup a, int G, ui
     const uint32_t gs = gridDim.x * kBlock;
     for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < np; p += gs) {
         for (int g = 0; g < G; ++g) {
-            const uint32_t seq = a.seq0[g] + p;
-            const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
-            const uint32_t f = a.fcs[g];
-            a.desc[g][p] = u32x2{(f & 0xFFFFu) | (bi << 16),
-                                 (bi >> 16) | (((f >> 16) & 0xFFu) << 16) | (bf << 24)};
+            const u32x4 r = nga_hdr_row(0u, a.fcs[g], a.seq0[g] + p, num_slots);
+            a.desc[g][p] = u32x2{r.y, r.z};
         }
     }
 }
@@ -1132,9 +1169,9 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_v256(QPackGroup a, c
         for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < np; p += gs) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                const uint32_t seq = a.seq0[g] + p;
+                const uint32_t seq = a.k.seq0[g] + p;
                 const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
-                const uint32_t f = a.fcs[g];
+                const uint32_t f = a.k.fcs[g];
                 a.desc[g][p] = u32x2{(f & 0xFFFFu) | (bi << 16),
                                      (bi >> 16) | (((f >> 16) & 0xFFu) << 16) | (bf << 24)};
             }
@@ -1151,36 +1188,23 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_v256(QPackGroup a, c
         for (int g = 0; g < G; ++g) {
             v[g] = u32x4{0u, 0u, 0u, 0u};
             if (full) {
-                f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
-                if (base) {
-                    x.x = __fsub_rn(x.x, b.x); x.y = __fsub_rn(x.y, b.y);
-                    x.z = __fsub_rn(x.z, b.z); x.w = __fsub_rn(x.w, b.w);
-                }
-                v[g] = u32x4{(uint32_t)q32(x.x, s), (uint32_t)q32(x.y, s), (uint32_t)q32(x.z, s),
-                             (uint32_t)q32(x.w, s)};
+                const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
+                v[g] = quant4(delta4(x, b, base != nullptr), s);
             } else {
-                const SrcQ32 src{a.x[g], base, s};
-                v[g].x = e0 < n ? src.one(e0) : 0u;
-                v[g].y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
-                v[g].z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
+                v[g] = tail4<3>(SrcQ32{a.x[g], base, s}, e0, n);
             }
         }
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v[g].x, 0x130, 0xF, 0xF, false);
             u32x4* row = reinterpret_cast<u32x4*>(a.pkts[g] + (size_t)p * stride);
-            u32x4 o;
-            o.x = __builtin_amdgcn_perm(v[g].y, v[g].x, kSelWire);
-            o.y = __builtin_amdgcn_perm(v[g].z, v[g].y, kSelWire);
-            o.z = __builtin_amdgcn_perm(v[g].w, v[g].z, kSelWire);
-            o.w = __builtin_amdgcn_perm(nx, v[g].w, kSelWire);
-            qpm_store(o, row + 1 + lane);
+            qpm_store(wire4(v[g], nx), row + 1 + lane);
             if (lane == 0) {
-                const uint32_t seq = a.seq0[g] + p;
+                const uint32_t seq = a.k.seq0[g] + p;
                 const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
-                const uint32_t f = a.fcs[g];
+                const uint32_t f = a.k.fcs[g];
                 u32x4 h;
-                h.x = bswap(a.bitmap[g]);
+                h.x = bswap(a.k.bitmap[g]);
                 h.y = (f & 0xFFFFu) | (bi << 16);
                 h.z = (bi >> 16) | (((f >> 16) & 0xFFu) << 16) | (bf << 24);
                 h.w = (bf >> 8) | (v[g].x & 0xFF000000u);
@@ -1199,11 +1223,6 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_v256(QPackGroup a, c
 // body stores straddle 16-byte boundaries), and the payload stream of a bucket IS its
 // values in order, byte-swapped, zero-padded to whole packets: packing is an elementwise
 // pass.  sendmmsg / recvmmsg carry it as two iovecs per datagram (same bytes on the wire).
-__device__ __forceinline__ u32x4 nga_hdr_row(uint32_t bitmap, uint32_t fcs, uint32_t seq, uint32_t num_slots) {
-    const uint32_t bi = bswap(seq % num_slots), bf = bswap(seq);
-    return u32x4{bswap(bitmap), (fcs & 0xFFFFu) | (bi << 16),
-                 (bi >> 16) | (((fcs >> 16) & 0xFFu) << 16) | (bf << 24), bf >> 8};
-}
 __device__ __forceinline__ u32x4 bswap4(u32x4 v) {
     return u32x4{bswap(v.x), bswap(v.y), bswap(v.z), bswap(v.w)};
 }
@@ -1224,6 +1243,8 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_split(Src src, size_t n, Ng
         if (vec && e0 + 4 <= n) {
             v = src.four(e0);
         } else {
+            // tail4<4>'s words, spelled out: through the helper k_pack_nga_split<SrcI32> comes out in
+            // another instruction order (199 instructions, 18 VGPRs, no scratch either way)
             v.x = e0 < n ? src.one(e0) : 0u;
             v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
             v.z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
@@ -1241,18 +1262,22 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_split(Src src, size_t n, Ng
 }
 
 // up to kQpGroup workers' fused quantise(x_w - base) + split pack in one launch: the base
-// chunk loaded once for every worker, each worker's payload stream coalesced
-struct QPackSplit {
-    const float* x[kQpGroup];
+// chunk loaded once for every worker, each worker's payload stream coalesced.  X: float, or
+// uint16_t for bf16 / fp16 buckets (8-byte worker loads, the base still fp32).
+template <typename X>
+struct QPackRows {
+    const X* x[kQpGroup];
     u32x4* hdr[kQpGroup];
     u32x4* pay[kQpGroup];
     u32x2* desc[kQpGroup];          // all null or all set
-    uint32_t bitmap[kQpGroup], seq0[kQpGroup], fcs[kQpGroup];
+    NgaKeys k;
 };
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackSplit a, const float* __restrict__ base,
+// Src: SrcQ32, or SrcX16<XT>; its Ld loads and widens the worker chunks.
+template <typename Src, int G>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<typename Src::Ld::X> a, const float* __restrict__ base,
                                                                   size_t n, float s, uint32_t num_slots,
                                                                   size_t nch, size_t np) {
+    using Ld = typename Src::Ld;
     const size_t gs = (size_t)gridDim.x * kBlock;
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
     for (size_t t = tid; t < nch; t += gs) {
@@ -1260,37 +1285,25 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackSplit a, 
         if (e0 + 4 <= n) {
             f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
             if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
-            f32x4 x[G];
+            typename Ld::Raw x[G];
 #pragma unroll
-            for (int g = 0; g < G; ++g) x[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
+            for (int g = 0; g < G; ++g) x[g] = __builtin_nontemporal_load(reinterpret_cast<const typename Ld::Raw*>(a.x[g] + e0));
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                f32x4 y = x[g];
-                if (base) {
-                    y.x = __fsub_rn(y.x, b.x); y.y = __fsub_rn(y.y, b.y);
-                    y.z = __fsub_rn(y.z, b.z); y.w = __fsub_rn(y.w, b.w);
-                }
-                const u32x4 q{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s),
-                              (uint32_t)q32(y.w, s)};
+                const u32x4 q = quant4(delta4(Ld::widen4(x[g]), b, base != nullptr), s);
                 packet_store(bswap4(q), a.pay[g] + t);
             }
         } else {                                       // the bucket's last chunk: zero tail
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                const SrcQ32 src{a.x[g], base, s};
-                u32x4 v;
-                v.x = e0 < n ? src.one(e0) : 0u;
-                v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
-                v.z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
-                v.w = e0 + 3 < n ? src.one(e0 + 3) : 0u;
-                packet_store(bswap4(v), a.pay[g] + t);
+                packet_store(bswap4(tail4<4>(Src{a.x[g], base, s}, e0, n)), a.pay[g] + t);
             }
         }
     }
     for (size_t p = tid; p < np; p += gs) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const u32x4 r = nga_hdr_row(a.bitmap[g], a.fcs[g], a.seq0[g] + (uint32_t)p, num_slots);
+            const u32x4 r = nga_hdr_row(a.k.bitmap[g], a.k.fcs[g], a.k.seq0[g] + (uint32_t)p, num_slots);
             packet_store(r, a.hdr[g] + p);
             if (a.desc[g]) a.desc[g][p] = u32x2{r.y, r.z};
         }
@@ -1306,7 +1319,7 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackSplit a, 
 // is read once.  The loop is wave-uniform (t0 steps whole waves); lanes past the last chunk
 // contribute 0 to the butterfly and store nothing.
 template <int G, bool AUTO>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackSplit a, const float* __restrict__ base,
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<float> a, const float* __restrict__ base,
                                                                       size_t n, int8_t* __restrict__ kblk,
                                                                       double lim, int shift, uint32_t L,
                                                                       uint32_t num_slots, size_t nch, size_t np) {
@@ -1323,9 +1336,7 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackSplit
         if constexpr (!AUTO) k = rd_k(kblk, shift >= 0 ? t >> shift : t / L);
         // worker g's chunk of deltas, quantised with 2^kk, into its payload row
         auto put = [&](int g, f32x4 y, int kk) {
-            const float s = pow2f(kk);
-            const u32x4 q{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s), (uint32_t)q32(y.w, s)};
-            packet_store(bswap4(q), a.pay[g] + t);
+            packet_store(bswap4(quant4(y, pow2f(kk))), a.pay[g] + t);
         };
         f32x4 d[G];
         if (e0 + 4 <= n) {
@@ -1333,12 +1344,9 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackSplit
             if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
 #pragma unroll
             for (int g = 0; g < G; ++g) d[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
-            if (base) {
+            if (base) {                                // one test for the group, as the held registers were scheduled
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    d[g].x = __fsub_rn(d[g].x, b.x); d[g].y = __fsub_rn(d[g].y, b.y);
-                    d[g].z = __fsub_rn(d[g].z, b.z); d[g].w = __fsub_rn(d[g].w, b.w);
-                }
+                for (int g = 0; g < G; ++g) d[g] = delta4(d[g], b, true);
             }
             if constexpr (!AUTO) {                     // given scales: nothing to wait for
 #pragma unroll
@@ -1369,64 +1377,7 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackSplit
     for (size_t p = tid; p < np; p += gs) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const u32x4 r = nga_hdr_row(a.bitmap[g], a.fcs[g], a.seq0[g] + (uint32_t)p, num_slots);
-            packet_store(r, a.hdr[g] + p);
-            if (a.desc[g]) a.desc[g][p] = u32x2{r.y, r.z};
-        }
-    }
-}
-
-// the same from bf16 / fp16 buckets (ina.h INA_X16_*): 8-byte worker loads, the fp32 base
-// chunk still read once per group
-struct QPackSplitX16 {
-    const uint16_t* x[kQpGroup];
-    u32x4* hdr[kQpGroup];
-    u32x4* pay[kQpGroup];
-    u32x2* desc[kQpGroup];          // all null or all set
-    uint32_t bitmap[kQpGroup], seq0[kQpGroup], fcs[kQpGroup];
-};
-template <int XT, int G>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_x16(QPackSplitX16 a, const float* __restrict__ base,
-                                                                      size_t n, float s, uint32_t num_slots,
-                                                                      size_t nch, size_t np) {
-    const size_t gs = (size_t)gridDim.x * kBlock;
-    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    for (size_t t = tid; t < nch; t += gs) {
-        const size_t e0 = 4 * t;
-        if (e0 + 4 <= n) {
-            f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
-            u32x2 x[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) x[g] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.x[g] + e0));
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                f32x4 y = widen16x4<XT>(x[g]);
-                if (base) {
-                    y.x = __fsub_rn(y.x, b.x); y.y = __fsub_rn(y.y, b.y);
-                    y.z = __fsub_rn(y.z, b.z); y.w = __fsub_rn(y.w, b.w);
-                }
-                const u32x4 q{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s),
-                              (uint32_t)q32(y.w, s)};
-                packet_store(bswap4(q), a.pay[g] + t);
-            }
-        } else {                                       // the bucket's last chunk: zero tail
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const SrcX16<XT> src{a.x[g], base, s};
-                u32x4 v;
-                v.x = e0 < n ? src.one(e0) : 0u;
-                v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
-                v.z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
-                v.w = e0 + 3 < n ? src.one(e0 + 3) : 0u;
-                packet_store(bswap4(v), a.pay[g] + t);
-            }
-        }
-    }
-    for (size_t p = tid; p < np; p += gs) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const u32x4 r = nga_hdr_row(a.bitmap[g], a.fcs[g], a.seq0[g] + (uint32_t)p, num_slots);
+            const u32x4 r = nga_hdr_row(a.k.bitmap[g], a.k.fcs[g], a.k.seq0[g] + (uint32_t)p, num_slots);
             packet_store(r, a.hdr[g] + p);
             if (a.desc[g]) a.desc[g][p] = u32x2{r.y, r.z};
         }
@@ -1471,18 +1422,15 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_v256(Src src, size_t n, Nga
         if (e0 + 4 <= n) {
             v = src.four(e0);
         } else {
+            // tail4<3>'s words, spelled out: through the helper k_pack_nga_v256<SrcI32> comes out in
+            // another instruction order (209 instructions, 28 VGPRs, no scratch either way)
             v.x = e0 < n ? src.one(e0) : 0u;
             v.y = e0 + 1 < n ? src.one(e0 + 1) : 0u;
             v.z = e0 + 2 < n ? src.one(e0 + 2) : 0u;
         }
         const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.x, 0x130, 0xF, 0xF, false);
         u32x4* row = reinterpret_cast<u32x4*>(pkts + (size_t)p * stride);
-        u32x4 o;
-        o.x = __builtin_amdgcn_perm(v.y, v.x, kSelWire);
-        o.y = __builtin_amdgcn_perm(v.z, v.y, kSelWire);
-        o.z = __builtin_amdgcn_perm(v.w, v.z, kSelWire);
-        o.w = __builtin_amdgcn_perm(nx, v.w, kSelWire);
-        packet_store(o, row + 1 + lane);
+        packet_store(wire4(v, nx), row + 1 + lane);
         if (lane == 0) {
             const uint32_t seq = h.seq0 + p;
             const uint32_t bi = bswap(seq % h.num_slots), bf = bswap(seq);
@@ -1998,6 +1946,23 @@ __global__ __launch_bounds__(kBlock) void k_absmax_multi_f32(PtrPack<float> xs, 
 // ===========================================================================
 using namespace ina;
 
+// the header's count | flags << 8 | switch_id << 16 word (NgaHdr::flags_count_sw, NgaKeys::fcs)
+static uint32_t nga_fcs(const ina_nga_params_t& q) {
+    return (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
+}
+// worker slot g of a group's keys, its sequence numbers starting p0 packets in
+static void fill_keys(NgaKeys& k, int g, const ina_nga_params_t& q, size_t p0 = 0) {
+    k.bitmap[g] = q.bitmap;
+    k.seq0[g] = q.seq0 + (uint32_t)p0;
+    k.fcs[g] = nga_fcs(q);
+}
+// f(integral_constant<int, G>) for a group of G in [1, kQpGroup] workers: the group kernels' instantiations
+template <int g = 1, typename F>
+static void with_group(int G, F&& f) {
+    if (G == g) f(std::integral_constant<int, g>{});
+    else if constexpr (g < kQpGroup) with_group<g + 1>(G, f);
+}
+
 template <typename Src>
 static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina_nga_params_t* prm,
                            const uint8_t* ovf, uint8_t* pkts, size_t pstride, hipStream_t s,
@@ -2012,8 +1977,7 @@ static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina
     size_t npk = (n + (size_t)V - 1) / (size_t)V;
     if (npk == 0) return INA_OK;
     if (!pkts) return set_error(INA_EINVAL, "null pointer%s", "");
-    NgaHdr h{prm->bitmap, prm->seq0, prm->num_slots,
-             (uint32_t)prm->count | ((uint32_t)prm->flags << 8) | ((uint32_t)prm->switch_id << 16), V};
+    NgaHdr h{prm->bitmap, prm->seq0, prm->num_slots, nga_fcs(*prm), V};
     if (pstride % 16 == 0 && V % 4 == 0 && src_aligned && aligned16(pkts)) {
         // 32-bit chunk indices: huge buckets go in packet ranges
         const size_t C = pstride / 16;
@@ -2048,6 +2012,73 @@ static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina
                                desc);
     }
     return check_launch("pack_nga");
+}
+
+// ---- split rows (include/ina.h): shared by their entry points -------------------------------
+static int split_geometry(int V, uint32_t num_slots) {
+    if (V <= 0 || V % 4 || V > 256 || num_slots == 0)
+        return set_error(INA_EINVAL, "split rows need V a multiple of 4 in [4, 256] and num_slots > 0%s", "");
+    return INA_OK;
+}
+
+// What the three split multi entry points check after their own first checks.  npk = 0 with
+// INA_OK: an empty bucket, nothing to write.  kblk: checked non-null when need_kblk.
+template <typename X>
+static int check_multi_split(const X* const* x, int W, const float* base, size_t n, const ina_nga_params_t* prm,
+                             uint8_t* const* hdr, uint8_t* const* pay, ina_nga_desc_t* const* desc,
+                             bool need_kblk, const int8_t* kblk, size_t& npk) {
+    npk = 0;
+    if (!x || !prm || !hdr || !pay || W < 1 || W > INA_MAX_WORKERS)
+        return set_error(INA_EINVAL, "x, prm, hdr, pay non-null and W in [1, %s]", "64");
+    const int V = prm[0].V;
+    if (int rc = split_geometry(V, prm[0].num_slots)) return rc;
+    npk = (n + (size_t)V - 1) / (size_t)V;
+    if (npk == 0) return INA_OK;
+    if (need_kblk && !kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (base && !aligned16(base)) return set_error(INA_EINVAL, "base must be 16-byte aligned%s", "");
+    for (int w = 0; w < W; ++w) {
+        if (prm[w].V != V || prm[w].num_slots != prm[0].num_slots)
+            return set_error(INA_EINVAL, "every worker needs the same V and num_slots%s", "");
+        if (!x[w] || !hdr[w] || !pay[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
+        if (!aligned16(x[w]) || !aligned16(hdr[w]) || !aligned16(pay[w]))
+            return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
+        if (desc && (!desc[w] || ((uintptr_t)desc[w] & 7u)))
+            return set_error(INA_EINVAL, "descriptors must be non-null and 8-byte aligned%s", "");
+    }
+    return INA_OK;
+}
+// workers [w0, w0 + G) of a split multi call as one kernel argument
+template <typename X, typename XV>
+static QPackRows<X> fill_rows(int w0, int G, const XV* const* x, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                              uint8_t* const* pay, ina_nga_desc_t* const* desc) {
+    QPackRows<X> a{};
+    for (int g = 0; g < G; ++g) {
+        a.x[g] = static_cast<const X*>(x[w0 + g]);
+        a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
+        a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
+        a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
+        fill_keys(a.k, g, prm[w0 + g]);
+    }
+    return a;
+}
+// the fp32 and 16-bit split multi packs: groups of up to kQpGroup workers, a launch each
+template <typename Src, typename XV>
+static int qpack_multi_split(const char* what, const XV* const* x, int W, const float* base, size_t n, int k,
+                             const ina_nga_params_t* prm, uint8_t* const* hdr, uint8_t* const* pay,
+                             ina_nga_desc_t* const* desc, size_t npk, ina_stream_t stream) {
+    using X = typename Src::Ld::X;
+    const float sc = ldexpf(1.0f, k);
+    const size_t nch = npk * (size_t)prm[0].V / 4;
+    const dim3 grid(grid_for(std::max(nch, npk), 1, ew_grid_cap())), blk(kBlock);
+    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
+        const int G = std::min(kQpGroup, W - w0);
+        const QPackRows<X> a = fill_rows<X>(w0, G, x, prm, hdr, pay, desc);
+        with_group(G, [&](auto g) {
+            hipLaunchKernelGGL((k_qpack_nga_multi_split<Src, g.value>), grid, blk, 0, hs(stream), a, base, n, sc,
+                               prm[0].num_slots, nch, npk);
+        });
+    }
+    return check_launch(what);
 }
 
 extern "C" {
@@ -2346,10 +2377,9 @@ int ina_nga_make_descriptors(const ina_nga_params_t* prm, int W, size_t npk, ina
         const int G = std::min(kQpGroup, W - w0);
         DescGroup a{};
         for (int g = 0; g < G; ++g) {
-            const ina_nga_params_t& q = prm[w0 + g];
             a.desc[g] = reinterpret_cast<u32x2*>(desc[w0 + g]);
-            a.seq0[g] = q.seq0;
-            a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
+            a.seq0[g] = prm[w0 + g].seq0;
+            a.fcs[g] = nga_fcs(prm[w0 + g]);
         }
         hipLaunchKernelGGL(k_nga_make_desc, dim3(grid_for(npk, 1)), dim3(kBlock), 0, hs(stream), a, G,
                            prm[0].num_slots, (uint32_t)npk);
@@ -2396,36 +2426,28 @@ int ina_quantize_pack_nga_multi(const float* const* x, int W, const float* base,
             const size_t v0 = p0 * (size_t)V;
             QPackGroup a{};
             for (int g = 0; g < G; ++g) {
-                const ina_nga_params_t& q = prm[w0 + g];
                 a.x[g] = x[w0 + g] + v0;
                 a.pkts[g] = pkts[w0 + g] + p0 * pstride;
                 a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g] + p0) : nullptr;
-                a.bitmap[g] = q.bitmap;
-                a.seq0[g] = q.seq0 + (uint32_t)p0;
-                a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
+                fill_keys(a.k, g, prm[w0 + g], p0);
             }
             const dim3 blk(kBlock);
             const float* bp = base ? base + v0 : nullptr;
             const size_t nn = n - v0;
             if (INA_QPM_PPW && V == 256 && C <= 65 + 64) {          // a wave per packet
                 const dim3 grid(grid_for(np * 64, 1, INA_QPM_PPW_BLOCKS));
-                switch (G) {
-#define INA_QPM(g_) case g_: hipLaunchKernelGGL(k_qpack_nga_multi_v256<g_>, grid, blk, 0, s, a, bp, nn, sc, \
-                                                prm[0].num_slots, (uint32_t)pstride, (uint32_t)np); break;
-                    INA_QPM(1) INA_QPM(2) INA_QPM(3) INA_QPM(4) INA_QPM(5) INA_QPM(6) INA_QPM(7) INA_QPM(8)
-#undef INA_QPM
-                }
+                with_group(G, [&](auto g) {
+                    hipLaunchKernelGGL(k_qpack_nga_multi_v256<g.value>, grid, blk, 0, s, a, bp, nn, sc,
+                                       prm[0].num_slots, (uint32_t)pstride, (uint32_t)np);
+                });
                 continue;
             }
             const dim3 grid(grid_for(np * C, 1, g_stream_blocks));
             const uint32_t ns = prm[0].num_slots, VV = (uint32_t)V, CC = (uint32_t)C, L = (uint32_t)(V / 4),
                            nch = (uint32_t)(np * C);
-            switch (G) {
-#define INA_QPM(g_) case g_: hipLaunchKernelGGL(k_qpack_nga_multi<g_>, grid, blk, 0, s, a, bp, nn, sc, ns, \
-                                                VV, CC, L, nch); break;
-                INA_QPM(1) INA_QPM(2) INA_QPM(3) INA_QPM(4) INA_QPM(5) INA_QPM(6) INA_QPM(7) INA_QPM(8)
-#undef INA_QPM
-            }
+            with_group(G, [&](auto g) {
+                hipLaunchKernelGGL(k_qpack_nga_multi<g.value>, grid, blk, 0, s, a, bp, nn, sc, ns, VV, CC, L, nch);
+            });
         }
     }
     return check_launch("quantize_pack_nga_multi");
@@ -2443,12 +2465,6 @@ int ina_nga_descriptors(const uint8_t* pkts, size_t npk, size_t pstride, ina_nga
 }
 
 // ---- split rows (include/ina.h) ----------------------------------------------------------
-static int split_geometry(int V, uint32_t num_slots) {
-    if (V <= 0 || V % 4 || V > 256 || num_slots == 0)
-        return set_error(INA_EINVAL, "split rows need V a multiple of 4 in [4, 256] and num_slots > 0%s", "");
-    return INA_OK;
-}
-
 int ina_pack_nga_split(const int32_t* vals, size_t n, const ina_nga_params_t* prm, const uint8_t* ovf,
                        uint8_t* hdr, uint8_t* pay, ina_nga_desc_t* desc, ina_stream_t stream) {
     if (!prm) return set_error(INA_EINVAL, "null params%s", "");
@@ -2458,8 +2474,7 @@ int ina_pack_nga_split(const int32_t* vals, size_t n, const ina_nga_params_t* pr
     if (!vals || !hdr || !pay) return set_error(INA_EINVAL, "null pointer%s", "");
     if (!aligned16(hdr) || !aligned16(pay) || (desc && ((uintptr_t)desc & 7u)))
         return set_error(INA_EINVAL, "header / payload rows 16-byte aligned, descriptors 8%s", "");
-    NgaHdr h{prm->bitmap, prm->seq0, prm->num_slots,
-             (uint32_t)prm->count | ((uint32_t)prm->flags << 8) | ((uint32_t)prm->switch_id << 16), prm->V};
+    NgaHdr h{prm->bitmap, prm->seq0, prm->num_slots, nga_fcs(*prm), prm->V};
     const size_t nch = npk * V / 4;
     hipLaunchKernelGGL((k_pack_nga_split<SrcI32>), dim3(grid_for(std::max(nch, npk), 1, ew_grid_cap())),
                        dim3(kBlock), 0, hs(stream), SrcI32{vals}, n, h, ovf, reinterpret_cast<u32x4*>(hdr),
@@ -2472,47 +2487,10 @@ int ina_quantize_pack_nga_multi_split(const float* const* x, int W, const float*
                                       const ina_nga_params_t* prm, uint8_t* const* hdr, uint8_t* const* pay,
                                       ina_nga_desc_t* const* desc, ina_stream_t stream) {
     if (int rc = check_k(k)) return rc;
-    if (!x || !prm || !hdr || !pay || W < 1 || W > INA_MAX_WORKERS)
-        return set_error(INA_EINVAL, "x, prm, hdr, pay non-null and W in [1, %s]", "64");
-    const int V = prm[0].V;
-    if (int rc = split_geometry(V, prm[0].num_slots)) return rc;
-    const size_t npk = (n + (size_t)V - 1) / (size_t)V;
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, false, nullptr, npk)) return rc;
     if (npk == 0) return INA_OK;
-    if (base && !aligned16(base)) return set_error(INA_EINVAL, "base must be 16-byte aligned%s", "");
-    for (int w = 0; w < W; ++w) {
-        if (prm[w].V != V || prm[w].num_slots != prm[0].num_slots)
-            return set_error(INA_EINVAL, "every worker needs the same V and num_slots%s", "");
-        if (!x[w] || !hdr[w] || !pay[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
-        if (!aligned16(x[w]) || !aligned16(hdr[w]) || !aligned16(pay[w]))
-            return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
-        if (desc && (!desc[w] || ((uintptr_t)desc[w] & 7u)))
-            return set_error(INA_EINVAL, "descriptors must be non-null and 8-byte aligned%s", "");
-    }
-    const float sc = ldexpf(1.0f, k);
-    const size_t nch = npk * (size_t)V / 4;
-    const dim3 grid(grid_for(std::max(nch, npk), 1, ew_grid_cap())), blk(kBlock);
-    hipStream_t s = hs(stream);
-    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
-        const int G = std::min(kQpGroup, W - w0);
-        QPackSplit a{};
-        for (int g = 0; g < G; ++g) {
-            const ina_nga_params_t& q = prm[w0 + g];
-            a.x[g] = x[w0 + g];
-            a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
-            a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
-            a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
-            a.bitmap[g] = q.bitmap;
-            a.seq0[g] = q.seq0;
-            a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
-        }
-        switch (G) {
-#define INA_QPS(g_) case g_: hipLaunchKernelGGL(k_qpack_nga_multi_split<g_>, grid, blk, 0, s, a, base, n, sc, \
-                                                prm[0].num_slots, nch, npk); break;
-            INA_QPS(1) INA_QPS(2) INA_QPS(3) INA_QPS(4) INA_QPS(5) INA_QPS(6) INA_QPS(7) INA_QPS(8)
-#undef INA_QPS
-        }
-    }
-    return check_launch("quantize_pack_nga_multi_split");
+    return qpack_multi_split<SrcQ32>("quantize_pack_nga_multi_split", x, W, base, n, k, prm, hdr, pay, desc, npk, stream);
 }
 
 // ---- packs from bf16 / fp16 buckets (ina.h "bf16 / fp16 gradients"; the other 16-bit entry
@@ -2538,53 +2516,13 @@ int ina_quantize_pack_nga_multi_split_x16(const void* const* x, int xtype, int W
                                           uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
     if (int rc = check_x16_type(xtype)) return rc;
     if (int rc = check_k(k)) return rc;
-    if (!x || !prm || !hdr || !pay || W < 1 || W > INA_MAX_WORKERS)
-        return set_error(INA_EINVAL, "x, prm, hdr, pay non-null and W in [1, %s]", "64");
-    const int V = prm[0].V;
-    if (int rc = split_geometry(V, prm[0].num_slots)) return rc;
-    const size_t npk = (n + (size_t)V - 1) / (size_t)V;
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, false, nullptr, npk)) return rc;
     if (npk == 0) return INA_OK;
-    if (base && !aligned16(base)) return set_error(INA_EINVAL, "base must be 16-byte aligned%s", "");
-    for (int w = 0; w < W; ++w) {
-        if (prm[w].V != V || prm[w].num_slots != prm[0].num_slots)
-            return set_error(INA_EINVAL, "every worker needs the same V and num_slots%s", "");
-        if (!x[w] || !hdr[w] || !pay[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
-        if (!aligned16(x[w]) || !aligned16(hdr[w]) || !aligned16(pay[w]))
-            return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
-        if (desc && (!desc[w] || ((uintptr_t)desc[w] & 7u)))
-            return set_error(INA_EINVAL, "descriptors must be non-null and 8-byte aligned%s", "");
-    }
-    const float sc = ldexpf(1.0f, k);
-    const size_t nch = npk * (size_t)V / 4;
-    const dim3 grid(grid_for(std::max(nch, npk), 1, ew_grid_cap())), blk(kBlock);
-    hipStream_t s = hs(stream);
-    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
-        const int G = std::min(kQpGroup, W - w0);
-        QPackSplitX16 a{};
-        for (int g = 0; g < G; ++g) {
-            const ina_nga_params_t& q = prm[w0 + g];
-            a.x[g] = static_cast<const uint16_t*>(x[w0 + g]);
-            a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
-            a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
-            a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
-            a.bitmap[g] = q.bitmap;
-            a.seq0[g] = q.seq0;
-            a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
-        }
-        switch (G) {
-#define INA_QPS(g_) case g_:                                                                                  \
-            if (xtype == INA_X16_BF16)                                                                        \
-                hipLaunchKernelGGL((k_qpack_nga_multi_split_x16<INA_X16_BF16, g_>), grid, blk, 0, s, a, base, n, sc, \
-                                   prm[0].num_slots, nch, npk);                                               \
-            else                                                                                              \
-                hipLaunchKernelGGL((k_qpack_nga_multi_split_x16<INA_X16_F16, g_>), grid, blk, 0, s, a, base, n, sc,  \
-                                   prm[0].num_slots, nch, npk);                                               \
-            break;
-            INA_QPS(1) INA_QPS(2) INA_QPS(3) INA_QPS(4) INA_QPS(5) INA_QPS(6) INA_QPS(7) INA_QPS(8)
-#undef INA_QPS
-        }
-    }
-    return check_launch("quantize_pack_nga_multi_split_x16");
+    const char* what = "quantize_pack_nga_multi_split_x16";
+    if (xtype == INA_X16_BF16)
+        return qpack_multi_split<SrcX16<INA_X16_BF16>>(what, x, W, base, n, k, prm, hdr, pay, desc, npk, stream);
+    return qpack_multi_split<SrcX16<INA_X16_F16>>(what, x, W, base, n, k, prm, hdr, pay, desc, npk, stream);
 }
 
 int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npk, int V,
@@ -2680,11 +2618,8 @@ int ina_quantize_pack_nga_blk_desc(const float* x, const float* base, size_t n, 
     if (desc && ((uintptr_t)desc & 7u)) return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
     if (!prm || prm->V <= 0 || prm->num_slots == 0) return set_error(INA_EINVAL, "bad nga params%s", "");
     const uint32_t V = (uint32_t)prm->V;
-    int shift = -1;
-    if ((V & (V - 1)) == 0)
-        for (shift = 0; (1u << shift) < V; ++shift) {}
     bool al = aligned16(x) && (!base || aligned16(base));
-    return pack_nga_launch(SrcQ32B{x, base, kblk, V, shift}, al, n, prm, nullptr, pkts, pstride, hs(stream), desc,
+    return pack_nga_launch(SrcQ32B{x, base, kblk, V, log2_exact(V)}, al, n, prm, nullptr, pkts, pstride, hs(stream), desc,
                            default_grid_cap());
 }
 
@@ -2697,27 +2632,12 @@ int ina_quantize_pack_nga_multi_split_blk(const float* const* x, int W, const fl
     if (mode == INA_BLK_AUTO) {
         if (int rc = scale_lim(degree, 32, lim)) return rc;
     }
-    if (!x || !prm || !hdr || !pay || W < 1 || W > INA_MAX_WORKERS)
-        return set_error(INA_EINVAL, "x, prm, hdr, pay non-null and W in [1, %s]", "64");
-    const int V = prm[0].V;
-    if (int rc = split_geometry(V, prm[0].num_slots)) return rc;
-    const size_t npk = (n + (size_t)V - 1) / (size_t)V;
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, true, kblk, npk)) return rc;
     if (npk == 0) return INA_OK;
-    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
-    if (base && !aligned16(base)) return set_error(INA_EINVAL, "base must be 16-byte aligned%s", "");
-    for (int w = 0; w < W; ++w) {
-        if (prm[w].V != V || prm[w].num_slots != prm[0].num_slots)
-            return set_error(INA_EINVAL, "every worker needs the same V and num_slots%s", "");
-        if (!x[w] || !hdr[w] || !pay[w]) return set_error(INA_EINVAL, "null worker buffer%s", "");
-        if (!aligned16(x[w]) || !aligned16(hdr[w]) || !aligned16(pay[w]))
-            return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
-        if (desc && (!desc[w] || ((uintptr_t)desc[w] & 7u)))
-            return set_error(INA_EINVAL, "descriptors must be non-null and 8-byte aligned%s", "");
-    }
+    const int V = prm[0].V;
     const uint32_t L = (uint32_t)V / 4;
-    int shift = -1;                                    // log2(L) when L is a power of two
-    if ((L & (L - 1)) == 0)
-        for (shift = 0; (1u << shift) < L; ++shift) {}
+    const int shift = log2_exact(L);                   // -1: L is no power of two
     bool autok = mode == INA_BLK_AUTO;
     // AUTO in the pack's own launch needs a packet to be adjacent lanes of one wave (V a power of
     // two in [8, 256]) and every worker in one group; otherwise the scales kernel runs first and
@@ -2727,34 +2647,17 @@ int ina_quantize_pack_nga_multi_split_blk(const float* const* x, int W, const fl
         autok = false;
     }
     const size_t nch = npk * (size_t)V / 4;
+    // the default cap (tuning key 0, settable in the product build), not the siblings' ew_grid_cap() (key 14,
+    // lab build only): the geometry tests hold this wave-uniform loop and its AUTO butterfly under it
     const dim3 grid(grid_for(std::max(nch, npk), 1)), blk(kBlock);
-    hipStream_t s = hs(stream);
     for (int w0 = 0; w0 < W; w0 += kQpGroup) {
         const int G = std::min(kQpGroup, W - w0);
-        QPackSplit a{};
-        for (int g = 0; g < G; ++g) {
-            const ina_nga_params_t& q = prm[w0 + g];
-            a.x[g] = x[w0 + g];
-            a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
-            a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
-            a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
-            a.bitmap[g] = q.bitmap;
-            a.seq0[g] = q.seq0;
-            a.fcs[g] = (uint32_t)q.count | ((uint32_t)q.flags << 8) | ((uint32_t)q.switch_id << 16);
-        }
-        switch (G) {
-#define INA_QPSB(g_)                                                                                             \
-    case g_:                                                                                                     \
-        if (autok)                                                                                               \
-            hipLaunchKernelGGL((k_qpack_nga_multi_split_blk<g_, true>), grid, blk, 0, s, a, base, n, kblk, lim,  \
-                               shift, L, prm[0].num_slots, nch, npk);                                            \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_qpack_nga_multi_split_blk<g_, false>), grid, blk, 0, s, a, base, n, kblk, lim, \
-                               shift, L, prm[0].num_slots, nch, npk);                                            \
-        break;
-            INA_QPSB(1) INA_QPSB(2) INA_QPSB(3) INA_QPSB(4) INA_QPSB(5) INA_QPSB(6) INA_QPSB(7) INA_QPSB(8)
-#undef INA_QPSB
-        }
+        const QPackRows<float> a = fill_rows<float>(w0, G, x, prm, hdr, pay, desc);
+        with_group(G, [&](auto g) {
+            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<g.value, true> : &k_qpack_nga_multi_split_blk<g.value, false>;
+            hipLaunchKernelGGL(kernel, grid, blk, 0, hs(stream), a, base, n, kblk, lim, shift, L, prm[0].num_slots,
+                               nch, npk);
+        });
     }
     return check_launch("quantize_pack_nga_multi_split_blk");
 }

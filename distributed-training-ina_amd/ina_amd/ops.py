@@ -365,6 +365,59 @@ def _desc_arg(desc, npk, dev):
     return desc
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _ptrs(ts):
+    return ptr_array([t.data_ptr() for t in ts]) if ts is not None else None
+
+
+def _base_arg(base, n, ref, what, req=lambda t: _req(t, torch.float32, "base")):
+    """The optional base of a fused pack, checked against the bucket (n values, on ref's device)."""
+    if base is not None:
+        req(base)
+        if base.numel() != n:
+            raise ValueError(f"base and {what} differ in length")
+        _same_device(ref, base)
+
+
+def _ovf_arg(overflow, npk):
+    if overflow is None:
+        return None
+    _req(overflow, torch.uint8, "overflow")
+    _fits(overflow, npk, "overflow")
+    return overflow.data_ptr()
+
+
+def _nga_params(V, bitmap, count, switch_id, seq0, flags, num_slots):
+    return _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
+                          seq0 & 0xFFFFFFFF, num_slots, V)
+
+
+def _worker_keys(W, bitmaps, seq0):
+    """Per-worker header words and sequence starts (seq0: one int for all workers or one each)."""
+    bitmaps = list(bitmaps)
+    seqs = [int(seq0)] * W if isinstance(seq0, numbers.Integral) else list(seq0)
+    if len(bitmaps) != W or len(seqs) != W:
+        raise ValueError("one bitmap and one seq0 per worker")
+    return bitmaps, seqs
+
+
+def _worker_params(V, keys, count, switch_id, flags, num_slots):
+    return (_lib.NgaParams * len(keys[0]))(*[_nga_params(V, b, count, switch_id, q, flags, num_slots)
+                                             for b, q in zip(*keys)])
+
+
+def _worker_descs(descs, W, npk, dev):
+    """descs of a multi pack: None / False -> None; True -> W new tensors; W tensors -> checked."""
+    if descs is None or descs is False:
+        return None
+    if descs is not True and (len(descs) != W or any(d is None for d in descs)):
+        raise ValueError("descs: True, or one int64 tensor per worker")
+    return [_desc_arg(True if descs is True else descs[w], npk, dev) for w in range(W)]
+
+
 def pack_nga(vals: torch.Tensor, V: int, bitmap: int, count: int, switch_id: int, seq0: int,
              flags: int = 0, num_slots: int = NUM_REGISTER, stride: int | None = None,
              overflow: torch.Tensor | None = None, out: torch.Tensor | None = None,
@@ -377,16 +430,11 @@ def pack_nga(vals: torch.Tensor, V: int, bitmap: int, count: int, switch_id: int
     npk = (vals.numel() + V - 1) // V
     out = torch.empty((npk, stride), dtype=torch.uint8, device=vals.device) if out is None else out
     _fits(out, npk * stride)
-    prm = _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
-                         seq0 & 0xFFFFFFFF, num_slots, V)
-    ovp = None
-    if overflow is not None:
-        _req(overflow, torch.uint8, "overflow")
-        _fits(overflow, npk, "overflow")
-        ovp = overflow.data_ptr()
+    prm = _nga_params(V, bitmap, count, switch_id, seq0, flags, num_slots)
+    ovp = _ovf_arg(overflow, npk)
     d = _desc_arg(desc, npk, vals.device)
     check(load().ina_pack_nga_desc(vals.data_ptr(), vals.numel(), C.byref(prm), ovp, out.data_ptr(),
-                                   stride, d.data_ptr() if d is not None else None, _stream(vals)),
+                                   stride, _ptr(d), _stream(vals)),
           "pack_nga")
     return (out, d) if d is not None else out
 
@@ -409,19 +457,14 @@ def quantize_pack_nga(x: torch.Tensor, k: int, V: int, bitmap: int, count: int, 
     quantize() then pack_nga()); desc as in pack_nga.  x: float32, bfloat16 or float16 (base
     stays float32)."""
     xt = _req_grad(x, "x")
-    if base is not None:
-        _req(base, torch.float32, "base")
-        if base.numel() != x.numel():
-            raise ValueError("base and x differ in length")
-        _same_device(x, base)
+    _base_arg(base, x.numel(), x, "x")
     stride = stride or nga_stride(V)
     npk = (x.numel() + V - 1) // V
     out = torch.empty((npk, stride), dtype=torch.uint8, device=x.device) if out is None else out
     _fits(out, npk * stride)
-    prm = _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
-                         seq0 & 0xFFFFFFFF, num_slots, V)
+    prm = _nga_params(V, bitmap, count, switch_id, seq0, flags, num_slots)
     d = _desc_arg(desc, npk, x.device)
-    bp, dp = base.data_ptr() if base is not None else None, d.data_ptr() if d is not None else None
+    bp, dp = _ptr(base), _ptr(d)
     if xt:
         rc = load().ina_quantize_pack_nga_x16_desc(x.data_ptr(), xt, bp, x.numel(), k, C.byref(prm),
                                                    out.data_ptr(), stride, dp, _stream(x))
@@ -447,15 +490,8 @@ def quantize_pack_nga_multi(xs, k: int, V: int, bitmaps, count: int, switch_id: 
                         "through quantize_pack_nga_multi_split")
     xs, n = _bufs(xs, torch.float32, "xs")
     W, dev = len(xs), xs[0].device
-    if base is not None:
-        _req(base, torch.float32, "base")
-        if base.numel() != n:
-            raise ValueError("base and xs differ in length")
-        _same_device(xs[0], base)
-    bitmaps = list(bitmaps)
-    seqs = [int(seq0)] * W if isinstance(seq0, numbers.Integral) else list(seq0)
-    if len(bitmaps) != W or len(seqs) != W:
-        raise ValueError("one bitmap and one seq0 per worker")
+    _base_arg(base, n, xs[0], "xs")
+    keys = _worker_keys(W, bitmaps, seq0)
     stride = stride or nga_stride(V)
     npk = (n + V - 1) // V
     if outs is None:
@@ -467,19 +503,11 @@ def quantize_pack_nga_multi(xs, k: int, V: int, bitmaps, count: int, switch_id: 
         _fits(o, npk * stride)
         _req(o, torch.uint8, "outs")
         _same_device(xs[0], o)
-    ds = None
-    if descs is not None and descs is not False:
-        if descs is not True and (len(descs) != W or any(d is None for d in descs)):
-            raise ValueError("descs: True, or one int64 tensor per worker")
-        ds = [_desc_arg(True if descs is True else descs[w], npk, dev) for w in range(W)]
-    prm = (_lib.NgaParams * W)(*[_lib.NgaParams(bitmaps[w] & 0xFFFFFFFF, count & 0xFF, flags & 0xFF,
-                                                switch_id & 0xFF, 0, seqs[w] & 0xFFFFFFFF, num_slots, V)
-                                 for w in range(W)])
-    check(load().ina_quantize_pack_nga_multi(
-        ptr_array([x.data_ptr() for x in xs]), W, base.data_ptr() if base is not None else None, n, k,
-        prm, ptr_array([o.data_ptr() for o in outs]), stride,
-        ptr_array([d.data_ptr() for d in ds]) if ds is not None else None, _stream(xs[0])),
-        "quantize_pack_nga_multi")
+    ds = _worker_descs(descs, W, npk, dev)
+    prm = _worker_params(V, keys, count, switch_id, flags, num_slots)
+    check(load().ina_quantize_pack_nga_multi(_ptrs(xs), W, _ptr(base), n, k, prm, _ptrs(outs), stride, _ptrs(ds),
+                                             _stream(xs[0])),
+          "quantize_pack_nga_multi")
     return (outs, ds) if ds is not None else outs
 
 
@@ -498,6 +526,16 @@ def _split_rows(npk, V, dev, hdr=None, pay=None):
     return hdr, pay
 
 
+def _worker_rows(hdrs, pays, W, npk, V, dev):
+    """Per-worker split rows of a multi pack: given ones checked, missing ones allocated."""
+    hdrs = [None] * W if hdrs is None else list(hdrs)
+    pays = [None] * W if pays is None else list(pays)
+    if len(hdrs) != W or len(pays) != W:
+        raise ValueError("one header and one payload array per worker")
+    rows = [_split_rows(npk, V, dev, h, p) for h, p in zip(hdrs, pays)]
+    return [r[0] for r in rows], [r[1] for r in rows]
+
+
 def pack_nga_split(vals: torch.Tensor, V: int, bitmap: int, count: int, switch_id: int, seq0: int,
                    flags: int = 0, num_slots: int = NUM_REGISTER, overflow: torch.Tensor | None = None,
                    hdr: torch.Tensor | None = None, pay: torch.Tensor | None = None, desc=None):
@@ -507,16 +545,11 @@ def pack_nga_split(vals: torch.Tensor, V: int, bitmap: int, count: int, switch_i
     _req(vals, torch.int32, "vals")
     npk = (vals.numel() + V - 1) // V
     hdr, pay = _split_rows(npk, V, vals.device, hdr, pay)
-    prm = _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
-                         seq0 & 0xFFFFFFFF, num_slots, V)
-    ovp = None
-    if overflow is not None:
-        _req(overflow, torch.uint8, "overflow")
-        _fits(overflow, npk, "overflow")
-        ovp = overflow.data_ptr()
+    prm = _nga_params(V, bitmap, count, switch_id, seq0, flags, num_slots)
+    ovp = _ovf_arg(overflow, npk)
     d = _desc_arg(desc, npk, vals.device)
     check(load().ina_pack_nga_split(vals.data_ptr(), vals.numel(), C.byref(prm), ovp, hdr.data_ptr(),
-                                    pay.data_ptr(), d.data_ptr() if d is not None else None, _stream(vals)),
+                                    pay.data_ptr(), _ptr(d), _stream(vals)),
           "pack_nga_split")
     return (hdr, pay, d) if d is not None else (hdr, pay)
 
@@ -530,33 +563,13 @@ def quantize_pack_nga_multi_split(xs, k: int, V: int, bitmaps, count: int, switc
     bfloat16 or float16, one dtype for all workers (base stays float32)."""
     xs, n, xt = _grad_bufs(xs, "xs")
     W, dev = len(xs), xs[0].device
-    if base is not None:
-        _req(base, torch.float32, "base")
-        if base.numel() != n:
-            raise ValueError("base and xs differ in length")
-        _same_device(xs[0], base)
-    bitmaps = list(bitmaps)
-    seqs = [int(seq0)] * W if isinstance(seq0, numbers.Integral) else list(seq0)
-    if len(bitmaps) != W or len(seqs) != W:
-        raise ValueError("one bitmap and one seq0 per worker")
+    _base_arg(base, n, xs[0], "xs")
+    keys = _worker_keys(W, bitmaps, seq0)
     npk = (n + V - 1) // V
-    hdrs = [None] * W if hdrs is None else list(hdrs)
-    pays = [None] * W if pays is None else list(pays)
-    if len(hdrs) != W or len(pays) != W:
-        raise ValueError("one header and one payload array per worker")
-    rows = [_split_rows(npk, V, dev, h, p) for h, p in zip(hdrs, pays)]
-    hdrs, pays = [r[0] for r in rows], [r[1] for r in rows]
-    ds = None
-    if descs is not None and descs is not False:
-        if descs is not True and (len(descs) != W or any(d is None for d in descs)):
-            raise ValueError("descs: True, or one int64 tensor per worker")
-        ds = [_desc_arg(True if descs is True else descs[w], npk, dev) for w in range(W)]
-    prm = (_lib.NgaParams * W)(*[_lib.NgaParams(bitmaps[w] & 0xFFFFFFFF, count & 0xFF, flags & 0xFF,
-                                                switch_id & 0xFF, 0, seqs[w] & 0xFFFFFFFF, num_slots, V)
-                                 for w in range(W)])
-    xa, bp = ptr_array([x.data_ptr() for x in xs]), base.data_ptr() if base is not None else None
-    ha, pa = ptr_array([h.data_ptr() for h in hdrs]), ptr_array([p.data_ptr() for p in pays])
-    da = ptr_array([d.data_ptr() for d in ds]) if ds is not None else None
+    hdrs, pays = _worker_rows(hdrs, pays, W, npk, V, dev)
+    ds = _worker_descs(descs, W, npk, dev)
+    prm = _worker_params(V, keys, count, switch_id, flags, num_slots)
+    xa, bp, ha, pa, da = _ptrs(xs), _ptr(base), _ptrs(hdrs), _ptrs(pays), _ptrs(ds)
     if xt:
         rc = load().ina_quantize_pack_nga_multi_split_x16(xa, xt, W, bp, n, k, prm, ha, pa, da, _stream(xs[0]))
     else:
@@ -601,10 +614,9 @@ def make_descriptors(n_packets: int, W: int, count: int, switch_id: int, seq0,
     outs = [_desc_arg(o, n_packets, outs[0].device) for o in outs]
     if len(outs) != W:
         raise ValueError("one output per worker")
-    prm = (_lib.NgaParams * W)(*[_lib.NgaParams(0, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
-                                                seqs[w] & 0xFFFFFFFF, num_slots, 1) for w in range(W)])
+    prm = _worker_params(1, ([0] * W, seqs), count, switch_id, flags, num_slots)
     st = stream.cuda_stream if stream is not None else _stream(outs[0])
-    check(load().ina_nga_make_descriptors(prm, W, n_packets, ptr_array([o.data_ptr() for o in outs]), st),
+    check(load().ina_nga_make_descriptors(prm, W, n_packets, _ptrs(outs), st),
           "nga_make_descriptors")
     return outs
 
@@ -706,11 +718,7 @@ def absmax(x: torch.Tensor, base: torch.Tensor | None = None, out: torch.Tensor 
     """Device float32 [1] = max_i |x[i] - base[i]| (base optional; NaN ignored).  x: float32,
     bfloat16 or float16; base and the result stay float32."""
     xt = _req_grad(x, "x")
-    if base is not None:
-        _req(base, torch.float32, "base")
-        if base.numel() != x.numel():
-            raise ValueError("base and x differ in length")
-        _same_device(x, base)
+    _base_arg(base, x.numel(), x, "x")
     out = torch.empty(1, dtype=torch.float32, device=x.device) if out is None else out
     _fits(out, 1)
     _req(out, torch.float32, "out")
@@ -969,11 +977,7 @@ def quantize_pack_nga_blk(x: torch.Tensor, kblk: torch.Tensor, V: int, bitmap: i
     -128 read as -126).  Returns what quantize_pack_nga returns."""
     V = _blk_v(V)
     _blk_f32(x, "x")
-    if base is not None:
-        _blk_f32(base, "base")
-        if base.numel() != x.numel():
-            raise ValueError("base and x differ in length")
-        _same_device(x, base)
+    _base_arg(base, x.numel(), x, "x", lambda t: _blk_f32(t, "base"))
     stride = stride or nga_stride(V)
     npk = (x.numel() + V - 1) // V
     kblk = _blk_scales_arg(kblk, npk, x, given=True)
@@ -981,12 +985,10 @@ def quantize_pack_nga_blk(x: torch.Tensor, kblk: torch.Tensor, V: int, bitmap: i
     _req(out, torch.uint8, "out")
     _fits(out, npk * stride)
     _same_device(x, out)
-    prm = _lib.NgaParams(bitmap & 0xFFFFFFFF, count & 0xFF, flags & 0xFF, switch_id & 0xFF, 0,
-                         seq0 & 0xFFFFFFFF, num_slots, V)
+    prm = _nga_params(V, bitmap, count, switch_id, seq0, flags, num_slots)
     d = _desc_arg(desc, npk, x.device)
-    check(load().ina_quantize_pack_nga_blk_desc(x.data_ptr(), base.data_ptr() if base is not None else None,
-                                                x.numel(), kblk.data_ptr(), C.byref(prm), out.data_ptr(), stride,
-                                                d.data_ptr() if d is not None else None, _stream(x)),
+    check(load().ina_quantize_pack_nga_blk_desc(x.data_ptr(), _ptr(base), x.numel(), kblk.data_ptr(), C.byref(prm),
+                                                out.data_ptr(), stride, _ptr(d), _stream(x)),
           "quantize_pack_nga_blk")
     return (out, d) if d is not None else out
 
@@ -1003,40 +1005,19 @@ def quantize_pack_nga_multi_split_blk(xs, V: int, bitmaps, count: int, switch_id
     V = _blk_v(V)
     xs, n = _blk_bufs(xs, "xs")
     W, dev = len(xs), xs[0].device
-    if base is not None:
-        _blk_f32(base, "base")
-        if base.numel() != n:
-            raise ValueError("base and xs differ in length")
-        _same_device(xs[0], base)
-    bitmaps = list(bitmaps)
-    seqs = [int(seq0)] * W if isinstance(seq0, numbers.Integral) else list(seq0)
-    if len(bitmaps) != W or len(seqs) != W:
-        raise ValueError("one bitmap and one seq0 per worker")
+    _base_arg(base, n, xs[0], "xs", lambda t: _blk_f32(t, "base"))
+    keys = _worker_keys(W, bitmaps, seq0)
     npk = (n + V - 1) // V
     mode = _lib.BLK_AUTO if kblk is None else _lib.BLK_GIVEN
     degree = _blk_degree(degree, W, 32) if kblk is None else 1
     kblk = _blk_scales_arg(kblk if kblk is not None else kblk_out, npk, xs[0])
-    hdrs = [None] * W if hdrs is None else list(hdrs)
-    pays = [None] * W if pays is None else list(pays)
-    if len(hdrs) != W or len(pays) != W:
-        raise ValueError("one header and one payload array per worker")
-    rows = [_split_rows(npk, V, dev, h, p) for h, p in zip(hdrs, pays)]
-    hdrs, pays = [r[0] for r in rows], [r[1] for r in rows]
+    hdrs, pays = _worker_rows(hdrs, pays, W, npk, V, dev)
     _same_device(xs[0], *hdrs, *pays)
-    ds = None
-    if descs is not None and descs is not False:
-        if descs is not True and (len(descs) != W or any(d is None for d in descs)):
-            raise ValueError("descs: True, or one int64 tensor per worker")
-        ds = [_desc_arg(True if descs is True else descs[w], npk, dev) for w in range(W)]
-    prm = (_lib.NgaParams * W)(*[_lib.NgaParams(bitmaps[w] & 0xFFFFFFFF, count & 0xFF, flags & 0xFF,
-                                                switch_id & 0xFF, 0, seqs[w] & 0xFFFFFFFF, num_slots, V)
-                                 for w in range(W)])
-    check(load().ina_quantize_pack_nga_multi_split_blk(
-        ptr_array([x.data_ptr() for x in xs]), W, base.data_ptr() if base is not None else None, n,
-        kblk.data_ptr(), mode, degree, prm, ptr_array([h.data_ptr() for h in hdrs]),
-        ptr_array([p.data_ptr() for p in pays]),
-        ptr_array([d.data_ptr() for d in ds]) if ds is not None else None, _stream(xs[0])),
-        "quantize_pack_nga_multi_split_blk")
+    ds = _worker_descs(descs, W, npk, dev)
+    prm = _worker_params(V, keys, count, switch_id, flags, num_slots)
+    check(load().ina_quantize_pack_nga_multi_split_blk(_ptrs(xs), W, _ptr(base), n, kblk.data_ptr(), mode, degree, prm,
+                                                       _ptrs(hdrs), _ptrs(pays), _ptrs(ds), _stream(xs[0])),
+          "quantize_pack_nga_multi_split_blk")
     return (hdrs, pays, ds, kblk) if ds is not None else (hdrs, pays, kblk)
 
 

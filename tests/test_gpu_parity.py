@@ -1233,6 +1233,80 @@ def test_make_descriptors_equal_pack_descriptors():
         assert torch.equal(a, b)
 
 
+def test_one_header_from_every_pack_entry_point():
+    """One parameter set (flags 0x40, num_slots no power of two, a sequence that wraps 2^32 inside
+    the bucket) through every entry point that writes NGA headers: bytes 0..14 of every packet are
+    the oracle's, every descriptor is its packet's bytes 4..11, and the overflow bytes of the two
+    entry points that take them move the overflow bit of those packets alone."""
+    o = ops()
+    V, bitmap, count, sw, seq0, flags, slots = 32, 0xA5C31E07, 7, 3, 2**32 - 2, 0x40, 1000
+    n = 5 * V + 3
+    rng = np.random.default_rng(41)
+    q = rng.integers(-2**20, 2**20, n).astype(np.int32)
+    x = dev(q.astype(np.float32))                                  # quantises to q at k = 0
+    npk = -(-n // V)
+    ovf = np.zeros(npk, np.uint8)
+    ovf[[1, 4]] = 1
+    kw = dict(flags=flags, num_slots=slots)
+    want = orc.pack_nga(q, V, bitmap, count, sw, seq0, **kw)[:, :15]
+    want_ovf = orc.pack_nga(q, V, bitmap, count, sw, seq0, ovf=ovf, **kw)[:, :15]
+    diff = want ^ want_ovf
+    assert (diff[:, 5] == orc.FLAG_OVERFLOW * ovf).all() and not np.delete(diff, 5, axis=1).any()
+
+    def desc_of(h):
+        return np.ascontiguousarray(h[:, 4:12]).view(np.int64).ravel()
+
+    got = {}
+    pk, d = o.pack_nga(dev(q), V, bitmap, count, sw, seq0, overflow=dev(ovf), desc=True, **kw)
+    assert pk.shape[1] % 16 == 0                                   # the flat path
+    got["pack_nga flat"] = (host(pk)[:, :15], host(d), want_ovf)
+    pk, d = o.pack_nga(dev(q), V, bitmap, count, sw, seq0, overflow=dev(ovf), stride=15 + 4 * V, desc=True, **kw)
+    got["pack_nga bytes"] = (host(pk)[:, :15], host(d), want_ovf)
+    h, _, d = o.pack_nga_split(dev(q), V, bitmap, count, sw, seq0, overflow=dev(ovf), desc=True, **kw)
+    got["pack_nga_split"] = (host(h)[:, :15], host(d), want_ovf)
+    pk, d = o.quantize_pack_nga(x, 0, V, bitmap, count, sw, seq0, desc=True, **kw)
+    got["quantize_pack_nga"] = (host(pk)[:, :15], host(d), want)
+    pks, ds = o.quantize_pack_nga_multi([x], 0, V, [bitmap], count, sw, seq0, descs=True, **kw)
+    got["quantize_pack_nga_multi"] = (host(pks[0])[:, :15], host(ds[0]), want)
+    hs, _, ds = o.quantize_pack_nga_multi_split([x], 0, V, [bitmap], count, sw, seq0, descs=True, **kw)
+    got["quantize_pack_nga_multi_split"] = (host(hs[0])[:, :15], host(ds[0]), want)
+    for name, (hdr, d, w) in got.items():
+        assert np.array_equal(hdr, w), name
+        assert np.array_equal(d, desc_of(hdr)), name
+    made = o.make_descriptors(npk, 1, count, sw, seq0, device=DEV, **kw)
+    assert np.array_equal(host(made[0]), desc_of(want))
+
+
+@pytest.mark.parametrize("src", ["fp32", "bf16", "fp16", "blk"])
+def test_quantize_pack_nga_wave_per_packet_with_padding_chunks(src):
+    """The single-worker NGA-256 pack (a wave per packet) on rows with three padding chunks: the
+    padding is zero, the rest is the oracle's, from every source the kernel is built for."""
+    from tests import _blk_ref as R
+    o = ops()
+    V, n, k = 256, 3 * 256 + 5, 16
+    stride = o.nga_stride(V) + 48
+    rng = np.random.default_rng(43)
+    base = (rng.standard_normal(n) * 1e-2).astype(np.float32)
+    x = torch.from_numpy(mixed_floats(rng, n))
+    args = (V, 3, 8, 1, 2**32 - 2)
+    out = torch.full((-(-n // V), stride), 0xA5, dtype=torch.uint8, device=DEV)
+    if src == "blk":
+        kblk = np.array([12, -128, 127, 3], np.int8)
+        pk, d = o.quantize_pack_nga_blk(x.to(DEV), dev(kblk), *args, base=dev(base), num_slots=1000, stride=stride,
+                                        out=out, desc=True)
+        qv = R.quantize_i32((x.numpy() - base).astype(np.float32), kblk, V)
+    else:
+        x = x.to({"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[src])
+        pk, d = o.quantize_pack_nga(x.to(DEV), k, *args, base=dev(base), num_slots=1000, stride=stride, out=out,
+                                    desc=True)
+        qv = orc.quantize_i32((x.float().numpy() - base).astype(np.float32), k)
+    want = orc.pack_nga(qv, *args, num_slots=1000)
+    got = host(pk)
+    assert np.array_equal(got[:, :15 + 4 * V], want)
+    assert not got[:, 15 + 4 * V:].any()
+    assert np.array_equal(host(d), np.ascontiguousarray(want[:, 4:12]).view(np.int64).ravel())
+
+
 @pytest.mark.parametrize("V,W,per", [(32, 4, 300), (256, 8, 70)])
 def test_process_apply_packets_outside_the_bucket_are_forwarded(V, W, per):
     """keep_forwarded=False consumes only the completed packets the PS takes (frag_id -

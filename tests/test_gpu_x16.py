@@ -244,6 +244,36 @@ def test_quantize_pack_nga_multi_split(dtype, W, V):
             assert np.array_equal(host(h16[w]), wh) and np.array_equal(host(p16[w]), wp), w
 
 
+@pytest.mark.parametrize("with_base", [False, True])
+@pytest.mark.parametrize("V", [32, 256])
+@pytest.mark.parametrize("W", [9, 17])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_quantize_pack_nga_multi_split_second_group(dtype, W, V, with_base):
+    """More than 8 workers: the launches after the first take their own workers' buckets, header
+    words and sequence starts (one of them wrapping 2^32 inside the bucket; num_slots no power of
+    two).  Rows and descriptors against the oracle and against the fp32 call on the widened bucket."""
+    o = ops()
+    n = 5 * V + 3
+    _, dev, w32 = grads(dtype)
+    xs = [d[:n].clone() for d in dev[:W]]
+    base = fbase(n) if with_base else None
+    b = torch.from_numpy(base).to(DEV) if with_base else None
+    seqs = [1000 * w + 7 for w in range(W)]
+    seqs[W - 1] = 2**32 - 3                                        # wraps at packet 3 of 6, in the last group
+    bitmaps = [0x01000193 * (w + 1) & 0xFFFFFFFF for w in range(W)]
+    args = (16, V, bitmaps, W, 1, seqs)
+    h16, p16, d16 = o.quantize_pack_nga_multi_split(xs, *args, base=b, num_slots=1000, descs=True)
+    h32, p32, d32 = o.quantize_pack_nga_multi_split([x.float() for x in xs], *args, base=b, num_slots=1000,
+                                                    descs=True)
+    for w in range(W):
+        assert torch.equal(h16[w], h32[w]) and torch.equal(p16[w], p32[w]) and torch.equal(d16[w], d32[w]), w
+        delta = (w32[w][:n] - base).astype(np.float32) if with_base else w32[w][:n]
+        rows = orc.pack_nga(orc.quantize_i32(delta, 16), V, bitmaps[w], W, 1, seqs[w], num_slots=1000)
+        wh, wp = to_split(rows, V)
+        assert np.array_equal(host(h16[w]), wh) and np.array_equal(host(p16[w]), wp), w
+        assert np.array_equal(host(d16[w]), np.ascontiguousarray(rows[:, 4:12]).view(np.int64).ravel()), w
+
+
 # ---- 6. dequantise to 16-bit ------------------------------------------------------------------
 HAND32 = [257, 259, -257,                   # bf16 ties at k = 0 (8 significant bits): to even
           2049, 2051, -2049,                # fp16 ties at k = 0 (11 significant bits)

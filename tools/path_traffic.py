@@ -31,7 +31,7 @@ def main():
            "correction": ("read = 2 x FETCH_SIZE x 1024 (gfx950 half-count of 16B/lane streams); "
                           "write = WRITE_SIZE x 1024"),
            "kernels": {}}
-    for sub, algo_r, algo_w in (("k_qpack_nga_multi_split<8>", W * 4 * n + 4 * n, W * npk * (16 + 4 * V) + W * npk * 8),
+    for sub, algo_r, algo_w in (("k_qpack_nga_multi_split<ina::SrcQ32, 8>", W * 4 * n + 4 * n, W * npk * (16 + 4 * V) + W * npk * 8),
                                 ("k_switch_run2<true, false, true>", (W + 1) * npk * 16 + W * npk * 4 * V + 4 * n,
                                  None)):
         f, nf = med(f"{sess}/pathpmc_SPLIT_1_FETCH_SIZE/run_counter_collection.csv", sub)

@@ -288,6 +288,69 @@ def run_blk_packets(dev):
     return rows
 
 
+def run_blk_switch(dev):
+    """Per-block scales in the fused switch + PS step (include/ina_switch_blk.h) at the ResNet-50 size,
+    W = 8, V = 256 and 32, split rows, cold caches, median of 20, the whole set twice (run 1 / run 2), as
+    run_blk_packets.  The batch is the steady-state one -- last step's acks in front of the 8 workers'
+    packets, with descriptors, as bench.py's measure_packet_path builds it -- packed by the AUTO multi
+    split pack.  Row 1: the fused block-scaled step beside the global-k fused step on the same batch
+    (sibling timed before and after; bar = sibling time x bytes ratio + the sibling's spread; reported,
+    not gated).  Row 2: beside what a caller wrote before, process_split then apply_completed_blk."""
+    from ina_amd import ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(19)
+    n, k, W = 25_557_032, 16, 8
+    xs = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(W)]
+    glob = torch.randn(n, device=dev, generator=gen) * 1e-2
+    upd = torch.empty_like(glob)
+    bms = [w + 1 for w in range(W)]
+    ws = 1.0 / (W + 1)
+    for run in (1, 2):
+        for V in (256, 32):
+            npk = (n + V - 1) // V
+            slots = 1 << 17 if V == 256 else 1 << 20
+            hdr = torch.zeros(((W + 1) * npk, 16), dtype=torch.uint8, device=dev)      # [acks | workers]
+            pay = torch.zeros(((W + 1) * npk, 4 * V), dtype=torch.uint8, device=dev)
+            desc = torch.empty((W + 1) * npk, dtype=torch.int64, device=dev)
+            acts = torch.empty((W + 1) * npk, dtype=torch.uint8, device=dev)
+            kb = torch.empty(npk, dtype=torch.int8, device=dev)
+            sw = ops.Switch(V, num_slots=slots, switch_id=1, device=dev)
+            ops.quantize_pack_nga_multi_split_blk(xs, V, bms, W, 1, 1, base=glob, num_slots=slots, kblk_out=kb,
+                                                  hdrs=list(hdr[npk:].view(W, npk, 16).unbind(0)),
+                                                  pays=list(pay[npk:].view(W, npk, 4 * V).unbind(0)),
+                                                  descs=list(desc[npk:].view(W, npk).unbind(0)))
+            ops.nga_descriptors(hdr[:npk], out=desc[:npk])
+
+            def fused(kk):
+                sw.process_apply_split(hdr, pay, 1, glob, kk, ws, out=upd, ack_hdr=hdr[:npk], ack_desc=desc[:npk],
+                                       keep_forwarded=False, actions=acts, desc=desc)
+
+            def two_calls():
+                sw.process_split(hdr, pay, actions=acts, desc=desc)
+                ops.apply_completed_blk(hdr, acts, V, 1, glob, kb, ws, out=upd, acks=hdr[:npk], pay=pay)
+
+            fused(kb)                                       # the first step's ack rows are another switch's;
+            fused(kb)                                       # from the second on they are this one's
+            done = int((acts[npk:] == 1).sum()), int((acts[:npk] == 3).sum())        # ACT_FWD_AGG, ACT_FWD_ACK
+            assert done == (npk, npk), done
+            npk_all = W * npk
+            nb = (npk * 8 + (npk_all + npk) * (16 + 4 * V) + npk * (4 * V + 5) + npk_all + npk + 8 * n + 16 * npk)
+            ta, tb, tc = _time(lambda: fused(k)), _time(lambda: fused(kb)), _time(lambda: fused(k))
+            lo, hi = min(ta, tc), max(ta, tc)
+            bar = hi * (nb + npk) / nb + (hi - lo)
+            rows.append(_row(f"switch + PS fused, split rows W={W} V={V} [blk, run {run}]", tb, nb + npk,
+                             sibling_us=[round(ta * 1e6, 2), round(tc * 1e6, 2)],
+                             sibling_spread_us=round((hi - lo) * 1e6, 2), bar_us=round(bar * 1e6, 2),
+                             bar_met=bool(tb <= bar)))
+            t2 = _time(two_calls)
+            rows.append(_row(f"process_split + apply_completed_blk, split rows W={W} V={V} [run {run}]", t2, nb + npk,
+                             fused_blk_us=round(tb * 1e6, 2), sibling_spread_us=round((hi - lo) * 1e6, 2),
+                             fused_beats_two_calls_by_more_than_spread=bool(t2 - tb > hi - lo)))
+            del hdr, pay, desc, acts, sw
+    return rows
+
+
 DEFAULTS = {"max_blocks": 16384, "reduce_blocks": 0, "stream_blocks": 16384, "combine_blocks": 256,
             "combine_ina_blocks": 8192, "ew_blocks": 1 << 24}
 
@@ -665,4 +728,5 @@ def run_extra(dev):
     rows += run_x16(dev)
     rows += run_blk(dev)
     rows += run_blk_packets(dev)
+    rows += run_blk_switch(dev)
     return {"rows": rows, "sweep": sweep, "grid_sweeps": gsweep}

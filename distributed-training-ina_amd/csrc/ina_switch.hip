@@ -2173,7 +2173,18 @@ struct PsFuse {
     size_t ack_stride;
     int on, keep_fwd;   // keep_fwd = 0: completed packets are consumed, not written back
     uint2* ack_desc;    // the ack rows' descriptors (header bytes 4..11), or NULL
+    const int8_t* kblk; // per-block scales (ina_switch_blk): slot s takes 2^-kblk[s], inv is unread
 };
+
+// the dequantising factor of PS slot ps_slot.  kBlk (ina_switch_blk, a compile-time flag beside
+// kPs, so the global-k kernels stay the code they were): one byte per consumed packet, at one
+// address per wave (run_segment) or per 8-lane group; called where the slot's `local` row is
+// loaded, so the two loads travel together and the completing packet's chain gets no longer
+template <bool kBlk>
+__device__ __forceinline__ float ps_inv(const PsFuse& ps, uint32_t ps_slot) {
+    if constexpr (kBlk) return pow2f(-rd_k(ps.kblk, ps_slot));
+    else return ps.inv;
+}
 
 // the run kernel's work for waves wave, wave + nwaves, ... (k_switch_run2: every wave of
 // the grid; k_switch_tiny: the 16 waves of its one workgroup)
@@ -2192,7 +2203,7 @@ struct PsFuse {
 // 4V-byte payload rows: lane l loads payload chunk l (values 4l..4l+3, one byte swap each,
 // no neighbour lane), lane b < kB the header row of packet b, and a forwarded packet
 // rewrites only its payload row.
-template <bool kPs, bool kLat, bool kSplit, typename PidFn>
+template <bool kPs, bool kBlk, bool kLat, bool kSplit, typename PidFn>
 __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                             size_t stride, uint8_t* __restrict__ pay,
                                             uint8_t* __restrict__ actions, const PsFuse& ps,
@@ -2332,13 +2343,14 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
                     if (consumed) {                      // launch.py:46-50 with the switch's sum
                         {
                             const size_t e0 = (size_t)ps_slot * (size_t)V + 4 * (size_t)lane;
+                            const float inv = ps_inv<kBlk>(ps, ps_slot);     // (wave-uniform)
                             if (vl && e0 + 4 <= ps.n) {
                                 const f32x4s l = *reinterpret_cast<const f32x4s*>(ps.local + e0);
                                 f32x4s r;
-                                r.x = __fadd_rn(l.x, __fmul_rn(__fmul_rn((float)(int32_t)reg.x, ps.inv), ps.ws));
-                                r.y = __fadd_rn(l.y, __fmul_rn(__fmul_rn((float)(int32_t)reg.y, ps.inv), ps.ws));
-                                r.z = __fadd_rn(l.z, __fmul_rn(__fmul_rn((float)(int32_t)reg.z, ps.inv), ps.ws));
-                                r.w = __fadd_rn(l.w, __fmul_rn(__fmul_rn((float)(int32_t)reg.w, ps.inv), ps.ws));
+                                r.x = __fadd_rn(l.x, __fmul_rn(__fmul_rn((float)(int32_t)reg.x, inv), ps.ws));
+                                r.y = __fadd_rn(l.y, __fmul_rn(__fmul_rn((float)(int32_t)reg.y, inv), ps.ws));
+                                r.z = __fadd_rn(l.z, __fmul_rn(__fmul_rn((float)(int32_t)reg.z, inv), ps.ws));
+                                r.w = __fadd_rn(l.w, __fmul_rn(__fmul_rn((float)(int32_t)reg.w, inv), ps.ws));
                                 // nt: 249.9 -> 241.3 us for the fused pass, the
                                 // steady-state step 0.71 -> 0.70 ms (default policy;
                                 // write-through 247.8; profiles/r03/lab/psout_lab.log)
@@ -2347,7 +2359,7 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
                                 const uint32_t rv[4] = {reg.x, reg.y, reg.z, reg.w};
                                 for (int t = 0; t < 4 && e0 + t < ps.n; ++t)
                                     ps.out[e0 + t] = __fadd_rn(ps.local[e0 + t],
-                                        __fmul_rn(__fmul_rn((float)(int32_t)rv[t], ps.inv), ps.ws));
+                                        __fmul_rn(__fmul_rn((float)(int32_t)rv[t], inv), ps.ws));
                             }
                             if (lane == 0 && ps.acks) {      // the PS ack (fragcheck.p4:26-31)
                                 u32x4s hd = a[b];
@@ -2456,7 +2468,7 @@ __device__ __forceinline__ void narrow_load(const uint8_t* __restrict__ pkts, si
     }
 }
 
-template <bool kPs, bool kSplit, typename PidFn>
+template <bool kPs, bool kBlk, bool kSplit, typename PidFn>
 __device__ __forceinline__ void run_segment_narrow(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                    size_t stride, uint8_t* __restrict__ pay,
                                                    uint8_t* __restrict__ actions,
@@ -2613,19 +2625,20 @@ __device__ __forceinline__ void run_segment_narrow(const ina_switch_state_t& st,
             have_reg = true;
             if (kPs && ps_g) {                       // launch.py:46-50 with the switch's sum
                 const size_t e0 = (size_t)ps_slot_v * (size_t)V + 4 * (size_t)l;
+                const float inv = ps_inv<kBlk>(ps, ps_slot_v);   // (one address per group)
                 if (vl && e0 + 4 <= ps.n) {
                     const f32x4s lo = *reinterpret_cast<const f32x4s*>(ps.local + e0);
                     f32x4s r;
-                    r.x = __fadd_rn(lo.x, __fmul_rn(__fmul_rn((float)(int32_t)S.x, ps.inv), ps.ws));
-                    r.y = __fadd_rn(lo.y, __fmul_rn(__fmul_rn((float)(int32_t)S.y, ps.inv), ps.ws));
-                    r.z = __fadd_rn(lo.z, __fmul_rn(__fmul_rn((float)(int32_t)S.z, ps.inv), ps.ws));
-                    r.w = __fadd_rn(lo.w, __fmul_rn(__fmul_rn((float)(int32_t)S.w, ps.inv), ps.ws));
+                    r.x = __fadd_rn(lo.x, __fmul_rn(__fmul_rn((float)(int32_t)S.x, inv), ps.ws));
+                    r.y = __fadd_rn(lo.y, __fmul_rn(__fmul_rn((float)(int32_t)S.y, inv), ps.ws));
+                    r.z = __fadd_rn(lo.z, __fmul_rn(__fmul_rn((float)(int32_t)S.z, inv), ps.ws));
+                    r.w = __fadd_rn(lo.w, __fmul_rn(__fmul_rn((float)(int32_t)S.w, inv), ps.ws));
                     __builtin_nontemporal_store(r, reinterpret_cast<f32x4s*>(ps.out + e0));
                 } else if (vl) {
                     const uint32_t rv[4] = {S.x, S.y, S.z, S.w};
                     for (int t = 0; t < 4 && e0 + t < ps.n; ++t)
                         ps.out[e0 + t] = __fadd_rn(ps.local[e0 + t],
-                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], ps.inv), ps.ws));
+                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], inv), ps.ws));
                 }
                 if (l == 0 && ps.acks) {             // the PS ack (fragcheck.p4:26-31)
                     u32x4s hd = hw;
@@ -2708,7 +2721,7 @@ __device__ __forceinline__ void st_row16(uint8_t* p, const u32x4s& v) { __builti
 // same header): ack / collision / count / Processor add, the PS step, the rewritten packet
 // and its action byte.  m: this lane's payload chunk (packed rows: row chunk l + 1), h: the
 // header chunk / header row; ack_known: a PS ack by its sort key (then m and h are unread)
-template <bool kPs, bool kSplit, int kThr = kSwBlock>
+template <bool kPs, bool kBlk, bool kSplit, int kThr = kSwBlock>
 __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                              size_t stride, uint8_t* __restrict__ pay,
                                              uint8_t* __restrict__ actions, const PsFuse& ps, uint32_t slot,
@@ -2772,19 +2785,20 @@ __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8
             const bool consumed = kPs && act == INA_ACT_FWD_AGG && ps_slot < ps.nslots;
             if (kPs && consumed) {           // launch.py:46-50 with the switch's sum
                 const size_t e0 = (size_t)ps_slot * (size_t)V + 4 * (size_t)l;
+                const float inv = ps_inv<kBlk>(ps, ps_slot);     // (one address per group)
                 if (vl && e0 + 4 <= ps.n) {
                     const f32x4s lc = *reinterpret_cast<const f32x4s*>(ps.local + e0);
                     f32x4s o;
-                    o.x = __fadd_rn(lc.x, __fmul_rn(__fmul_rn((float)(int32_t)reg.x, ps.inv), ps.ws));
-                    o.y = __fadd_rn(lc.y, __fmul_rn(__fmul_rn((float)(int32_t)reg.y, ps.inv), ps.ws));
-                    o.z = __fadd_rn(lc.z, __fmul_rn(__fmul_rn((float)(int32_t)reg.z, ps.inv), ps.ws));
-                    o.w = __fadd_rn(lc.w, __fmul_rn(__fmul_rn((float)(int32_t)reg.w, ps.inv), ps.ws));
+                    o.x = __fadd_rn(lc.x, __fmul_rn(__fmul_rn((float)(int32_t)reg.x, inv), ps.ws));
+                    o.y = __fadd_rn(lc.y, __fmul_rn(__fmul_rn((float)(int32_t)reg.y, inv), ps.ws));
+                    o.z = __fadd_rn(lc.z, __fmul_rn(__fmul_rn((float)(int32_t)reg.z, inv), ps.ws));
+                    o.w = __fadd_rn(lc.w, __fmul_rn(__fmul_rn((float)(int32_t)reg.w, inv), ps.ws));
                     __builtin_nontemporal_store(o, reinterpret_cast<f32x4s*>(ps.out + e0));
                 } else if (vl) {
                     const uint32_t rv[4] = {reg.x, reg.y, reg.z, reg.w};
                     for (int t = 0; t < 4 && e0 + t < ps.n; ++t)
                         ps.out[e0 + t] = __fadd_rn(ps.local[e0 + t],
-                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], ps.inv), ps.ws));
+                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], inv), ps.ws));
                 }
                 if (l == 0 && ps.acks) {     // the PS ack (fragcheck.p4:26-31)
                     u32x4s hd = h;
@@ -2856,7 +2870,7 @@ static_assert(8 % kSeg8Flight == 0, "whole rounds of payload loads");
 // group_packet does).  ack_pid != ~0u (group-uniform): a PS ack leads the segment (the steady
 // state: step t's ack in front of step t+1's packets) -- it clears the slot's frag register
 // (fragcheck.p4:26-31), so the first packet's frag id is the slot's, and it is forwarded as is.
-template <bool kPs, bool kSplit>
+template <bool kPs, bool kBlk, bool kSplit>
 __device__ __forceinline__ bool seg8_fast(const ina_switch_state_t& st, uint8_t* __restrict__ pkts, size_t stride,
                                           uint8_t* __restrict__ pay, uint8_t* __restrict__ actions,
                                           const PsFuse& ps, bool has, uint32_t slot, uint32_t pidl, bool ackl,
@@ -2929,19 +2943,20 @@ __device__ __forceinline__ bool seg8_fast(const ina_switch_state_t& st, uint8_t*
         if constexpr (kPs) {
             if (consumed) {                                       // launch.py:46-50 with the switch's sum
                 const size_t e0 = (size_t)ps_slot * (size_t)V + 4 * (size_t)l;
+                const float inv = ps_inv<kBlk>(ps, ps_slot);     // (one address per group)
                 if (vl && e0 + 4 <= ps.n) {
                     const f32x4s lc = *reinterpret_cast<const f32x4s*>(ps.local + e0);
                     f32x4s o;
-                    o.x = __fadd_rn(lc.x, __fmul_rn(__fmul_rn((float)(int32_t)run.x, ps.inv), ps.ws));
-                    o.y = __fadd_rn(lc.y, __fmul_rn(__fmul_rn((float)(int32_t)run.y, ps.inv), ps.ws));
-                    o.z = __fadd_rn(lc.z, __fmul_rn(__fmul_rn((float)(int32_t)run.z, ps.inv), ps.ws));
-                    o.w = __fadd_rn(lc.w, __fmul_rn(__fmul_rn((float)(int32_t)run.w, ps.inv), ps.ws));
+                    o.x = __fadd_rn(lc.x, __fmul_rn(__fmul_rn((float)(int32_t)run.x, inv), ps.ws));
+                    o.y = __fadd_rn(lc.y, __fmul_rn(__fmul_rn((float)(int32_t)run.y, inv), ps.ws));
+                    o.z = __fadd_rn(lc.z, __fmul_rn(__fmul_rn((float)(int32_t)run.z, inv), ps.ws));
+                    o.w = __fadd_rn(lc.w, __fmul_rn(__fmul_rn((float)(int32_t)run.w, inv), ps.ws));
                     __builtin_nontemporal_store(o, reinterpret_cast<f32x4s*>(ps.out + e0));
                 } else if (vl) {
                     const uint32_t rv[4] = {run.x, run.y, run.z, run.w};
                     for (int t = 0; t < 4 && e0 + t < ps.n; ++t)
                         ps.out[e0 + t] = __fadd_rn(ps.local[e0 + t],
-                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], ps.inv), ps.ws));
+                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], inv), ps.ws));
                 }
                 if (l == 7 && ps.acks) {                          // the PS ack (fragcheck.p4:26-31): packet 7's header
                     static_assert(kSplit || !kPs, "packed rows' ack rows also carry value 0's first byte");
@@ -2962,7 +2977,7 @@ __device__ __forceinline__ bool seg8_fast(const ina_switch_state_t& st, uint8_t*
 // (group g: the g-th head), walking each segment's packets in position order (= arrival
 // order inside the slot, ngaa.p4:120-196) with kP positions' loads in flight.  Per packet the
 // same group_packet as the run-table path; a segment may run past the window's end.
-template <bool kPs, bool kSplit>
+template <bool kPs, bool kBlk, bool kSplit>
 __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                     uint8_t* __restrict__ pay, size_t npk, size_t stride,
                                                     const KeySrc keys, const uint32_t* __restrict__ ids,
@@ -3045,7 +3060,7 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
                             hint = ((kq & kAckBit) ? 1u : 0u) | ((kq & kPlainBit) ? 2u : 0u);
                         }
                     }
-                    if (seg8_fast<kPs, kSplit>(st, pkts, stride, pay, actions, ps, has, hslot, pidl, (hint & 1u) != 0u,
+                    if (seg8_fast<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, has, hslot, pidl, (hint & 1u) != 0u,
                                                drop_written, ~0u, (hint & 2u) != 0u, plB, plC))
                         continue;
                 }
@@ -3111,7 +3126,7 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
                 for (int j = 0; j < kP; ++j) {
                     if (!__ballot(in[j])) continue;
                     if (!in[j]) continue;
-                    group_packet<kPs, kSplit>(st, pkts, stride, pay, actions, ps, hslot, pid[j], m[j], h[j], acq[j],
+                    group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, hslot, pid[j], m[j], h[j], acq[j],
                                               cnt, frag, reg, have_reg, drop_written);
                 }
             }
@@ -3130,7 +3145,7 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
 // slots), lane group g slot s8 + g: its (first entry, length) from the slot table, its list's
 // first 8 packet ids one per lane (loaded beside the slot's count and frag), then the packets in
 // list order = arrival order (ngaa.p4:120-196) through group_packet, kP loads in flight.
-template <bool kPs, bool kSplit>
+template <bool kPs, bool kBlk, bool kSplit>
 __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                    size_t stride, uint8_t* __restrict__ pay,
                                                    uint8_t* __restrict__ actions, const PsFuse& ps,
@@ -3167,7 +3182,7 @@ __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st,
         if constexpr (kSplit && !kPs) {
             // every list of these 8 slots 8 packets long: the whole-segment path
             if (maxlen == 8u && !__ballot(has && hlen != 8u) &&
-                seg8_fast<kPs, kSplit>(st, pkts, stride, pay, actions, ps, has, slot, idl & ~kAckBit,
+                seg8_fast<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, has, slot, idl & ~kAckBit,
                                        (idl & kAckBit) != 0u, true)) {
                 id_nx = (uint32_t)l < e_nx.y ? ids[e_nx.x + (uint32_t)l] : 0u;   // the next step's first ids
                 continue;
@@ -3212,7 +3227,7 @@ __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st,
             for (int j = 0; j < kP; ++j) {
                 if (!__ballot(in[j])) continue;
                 if (!in[j]) continue;
-                group_packet<kPs, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], acq[j], cnt,
+                group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], acq[j], cnt,
                                           frag, reg, have_reg, true);
             }
         }
@@ -3226,7 +3241,7 @@ __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st,
     }
 }
 
-template <bool kPs, bool kLat = false, bool kNarrow = false, bool kSplit = false>
+template <bool kPs, bool kBlk, bool kLat = false, bool kNarrow = false, bool kSplit = false>
 __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                  uint8_t* __restrict__ pay, size_t npk, size_t stride,
                                                  const uint32_t* __restrict__ keys,
@@ -3240,7 +3255,7 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
     if constexpr (kNarrow) {
         // (kdesc: a batch in slot order whose keys come from its descriptors, see KeySrc)
         const KeySrc ks{keys, kdesc, st.num_slots, st.switch_id, kmask != 0xFFFFFFFFu};
-        window_slots_narrow<kPs, kSplit>(st, pkts, pay, npk, stride, ks, ids, actions, win, kmask, ps, wave,
+        window_slots_narrow<kPs, kBlk, kSplit>(st, pkts, pay, npk, stride, ks, ids, actions, win, kmask, ps, wave,
                                          nwaves, drop_written, plB, plC);
         return;
     }
@@ -3309,10 +3324,10 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
             }
         };
         if constexpr (kNarrow)
-            run_segment_narrow<kPs, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
+            run_segment_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
                                             pos + (ack_led ? 1 : 0), end, pids);
         else
-            run_segment<kPs, kLat, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
+            run_segment<kPs, kBlk, kLat, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
                                            pos + (ack_led ? 1 : 0), end, pids, drop_written);
         }
     }
@@ -3327,7 +3342,7 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
 // group at once on group-uniform VGPRs -- no per-packet scalar walk and no cross-group scan,
 // about a tenth of run_segment_narrow's instructions per packet.  kP runs' loads are in
 // flight together.  Same results as the per-slot walk, packet for packet.
-template <bool kPs, bool kSplit>
+template <bool kPs, bool kBlk, bool kSplit>
 __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                   size_t stride, uint8_t* __restrict__ pay,
                                                   uint8_t* __restrict__ actions, const PsFuse& ps,
@@ -3374,7 +3389,7 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
                                r0p = __builtin_amdgcn_readfirstlane(rpos);
                 const uint32_t aoff = slot - r0s;
                 if (!__ballot(sv && (off >= rll || (a && aoff >= r0l))) &&
-                    seg8_fast<kPs, kSplit>(st, pkts, stride, pay, actions, ps, sv, slot, rpl + off, ackl, drop_written,
+                    seg8_fast<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, sv, slot, rpl + off, ackl, drop_written,
                                            a ? r0p + aoff : ~0u))
                     continue;
             }
@@ -3455,7 +3470,7 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
                 if (!__ballot(in[j])) continue;          // no slot of this wave in run r0 + j
                 if (!in[j]) continue;
                 touched = true;
-                group_packet<kPs, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], ackr[j],
+                group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], ackr[j],
                                           cnt, frag, reg, have_reg, drop_written);
             }
         }
@@ -3473,7 +3488,7 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
 // slots (one pass of the grid) and runs slot s's segment -- the packets start_r + s -
 // first_r of the runs that hold s, in run order = arrival order -- through run_segment.
 // A PS ack leading its segment is done without reading it, as in switch_run2_body.
-template <bool kPs, bool kNarrow, bool kSplit>
+template <bool kPs, bool kBlk, bool kNarrow, bool kSplit>
 __device__ __forceinline__ void switch_runs_body(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                  size_t stride, uint8_t* __restrict__ pay,
                                                  uint8_t* __restrict__ actions,
@@ -3508,7 +3523,7 @@ __device__ __forceinline__ void switch_runs_body(const ina_switch_state_t& st, u
     const size_t s_end = s_begin + per < (size_t)hi ? s_begin + per : (size_t)hi;
 #if INA_SWITCH_NARROW_SLOTS
     if constexpr (kNarrow) {
-        runs_slots_narrow<kPs, kSplit>(st, pkts, stride, pay, actions, ps, R, rpos, rlen, rslot, rack, lo, hi,
+        runs_slots_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, R, rpos, rlen, rslot, rack, lo, hi,
                                        wave, nwaves, drop_written);
         return;
     }
@@ -3545,9 +3560,9 @@ __device__ __forceinline__ void switch_runs_body(const ina_switch_state_t& st, u
             }
         };
         if constexpr (kNarrow)
-            run_segment_narrow<kPs, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids);
+            run_segment_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids);
         else
-            run_segment<kPs, false, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids,
+            run_segment<kPs, kBlk, false, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids,
                                             drop_written);
     }
 }
@@ -3587,11 +3602,16 @@ __device__ __forceinline__ size_t switch_block_index() {
 #ifndef INA_SWITCH_WAVES_PS_NS
 #define INA_SWITCH_WAVES_PS_NS 8      // NGA-32 packet path: switch + PS 329.3 -> 297.6 us, step 636.9 -> 608.9 (r05y)
 #endif
-template <bool kPs, bool kNarrow, bool kSplit>
+// the same with per-block scales: the scale byte's address and factor do not fit the 64 VGPRs of
+// 8 waves (48 B/lane of scratch, 15 VGPRs spilled); 7 waves (72 VGPRs) hold them
+#ifndef INA_SWITCH_WAVES_PS_NS_BLK
+#define INA_SWITCH_WAVES_PS_NS_BLK 7
+#endif
+template <bool kPs, bool kBlk, bool kNarrow, bool kSplit>
 #ifndef INA_SWITCH_WAVES_RUN_NP
 #define INA_SWITCH_WAVES_RUN_NP 8     // narrow packed rows (with 1 packet in flight, see kSlotInFlight)
 #endif
-__global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? ((kNarrow && kSplit) ? INA_SWITCH_WAVES_PS_NS : INA_SWITCH_WAVES) : (kNarrow && kSplit) ? INA_SWITCH_WAVES_RUN_NS : kNarrow ? INA_SWITCH_WAVES_RUN_NP : INA_SWITCH_WAVES_RUN, 8))) void k_switch_run2(ina_switch_state_t st,
+__global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? ((kNarrow && kSplit) ? (kBlk ? INA_SWITCH_WAVES_PS_NS_BLK : INA_SWITCH_WAVES_PS_NS) : INA_SWITCH_WAVES) : (kNarrow && kSplit) ? INA_SWITCH_WAVES_RUN_NS : kNarrow ? INA_SWITCH_WAVES_RUN_NP : INA_SWITCH_WAVES_RUN, 8))) void k_switch_run2(ina_switch_state_t st,
                                                           uint8_t* __restrict__ pkts,
                                                           uint8_t* __restrict__ pay, size_t npk,
                                                           size_t stride,
@@ -3619,7 +3639,7 @@ __global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? 
                 // (the lists' slots XCD-contiguous: neighbouring slots' lists point into the same
                 // arrival windows, whose rows then come through one L2 -- the plain map cost
                 // jitter 4096 16 us)
-                lists_slots_narrow<kPs, kSplit>(st, pkts, stride, pay, actions, ps, loc_ids, loc_tab,
+                lists_slots_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, loc_ids, loc_tab,
                                                 unsorted[kLocKmin], unsorted[kLocSlots],
                                                 xcd_block_index() * (kSwBlock / 64) + wave_in_block(), nwaves);
             return;
@@ -3633,7 +3653,7 @@ __global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? 
             // has no table of this call and falls through to the in-order test; were one built,
             // switch_runs_body would take it, with the same results -- both walk a slot's packets
             // in arrival order (test_whole_segments_vs_oracle, order "one_sender")
-            switch_runs_body<kPs, kNarrow, kSplit>(st, pkts, stride, pay, actions, kmask, ps,
+            switch_runs_body<kPs, kBlk, kNarrow, kSplit>(st, pkts, stride, pay, actions, kmask, ps,
                                                    unsorted + (kCtlRuns - kCtlEpochs), wave, nwaves,
                                                    drop_prefill != 0);
             return;
@@ -3658,14 +3678,14 @@ __global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? 
     // bucket sort: the foreign packets' bucket was left unsorted at the END of the arrays;
     // the run kernel never processes foreign packets, so it stops before them
     if (nforeign) npk -= *nforeign;
-    switch_run2_body<kPs, false, kNarrow, kSplit>(st, pkts, pay, npk, stride, keys, ids, actions, win, kmask, ps,
+    switch_run2_body<kPs, kBlk, false, kNarrow, kSplit>(st, pkts, pay, npk, stride, keys, ids, actions, win, kmask, ps,
                                                   wave, nwaves, drop_prefill != 0, kdesc, plB, plC);
 }
 
 // batches of at most INA_SWITCH_TINY_MAX packets (latency, not bandwidth): ONE launch of
 // one 16-wave workgroup -- the bitonic (slot, packet id) sort in LDS, then the run
 // kernel's work on the same 16 waves with the sorted arrays read from LDS.
-template <bool kPs, typename T, int kIdBits, bool kSplit>
+template <bool kPs, bool kBlk, typename T, int kIdBits, bool kSplit>
 __global__ __launch_bounds__(kSmallBlock) void k_switch_tiny(ina_switch_state_t st, uint8_t* __restrict__ pkts,
                                                              uint8_t* __restrict__ pay, uint32_t npk, size_t stride,
                                                              uint8_t* __restrict__ actions, uint32_t win,
@@ -3675,7 +3695,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_switch_tiny(ina_switch_state_t 
     __shared__ uint32_t keys_s[INA_SWITCH_SMALL_MAX], ids_s[INA_SWITCH_SMALL_MAX];
     switch_sort_small_body<T, kIdBits>(pkts, npk, stride, st.num_slots, st.switch_id, actions, keys_s, ids_s);
     __syncthreads();
-    switch_run2_body<kPs, true, false, kSplit>(st, pkts, pay, npk, stride, keys_s, ids_s, actions, win,
+    switch_run2_body<kPs, kBlk, true, false, kSplit>(st, pkts, pay, npk, stride, keys_s, ids_s, actions, win,
                                                0xFFFFFFFFu, ps, wave_in_block(), kSmallBlock / 64);
 }
 
@@ -4001,11 +4021,15 @@ static uint32_t draw_sort_epoch() {
 
 static void launch_tiny(const SwitchBatch& b, const SwitchPlan& p) {
     const bool split = b.pay != nullptr;
-    auto* tiny = b.ps.on
-        ? (p.key32 ? (split ? &k_switch_tiny<true, uint32_t, 12, true> : &k_switch_tiny<true, uint32_t, 12, false>)
-                   : (split ? &k_switch_tiny<true, unsigned long long, 32, true> : &k_switch_tiny<true, unsigned long long, 32, false>))
-        : (p.key32 ? (split ? &k_switch_tiny<false, uint32_t, 12, true> : &k_switch_tiny<false, uint32_t, 12, false>)
-                   : (split ? &k_switch_tiny<false, unsigned long long, 32, true> : &k_switch_tiny<false, unsigned long long, 32, false>));
+    // (the kernel's flags: PS step, per-block scales, key type and bits, split rows)
+    auto pick = [&](auto ps_on, auto blk) {
+        constexpr bool P = decltype(ps_on)::value, B = decltype(blk)::value;
+        return p.key32 ? (split ? &k_switch_tiny<P, B, uint32_t, 12, true> : &k_switch_tiny<P, B, uint32_t, 12, false>)
+                       : (split ? &k_switch_tiny<P, B, unsigned long long, 32, true>
+                                : &k_switch_tiny<P, B, unsigned long long, 32, false>);
+    };
+    auto* tiny = !b.ps.on ? pick(std::false_type{}, std::false_type{})
+               : b.ps.kblk ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
     hipLaunchKernelGGL(tiny, dim3(1), dim3(kSmallBlock), 0, b.s, *b.st, b.pkts, b.pay, (uint32_t)b.npk, b.stride,
                        b.actions, p.win, b.ps);
 }
@@ -4132,10 +4156,14 @@ static void launch_run(const SwitchBatch& b, const SwitchPlan& p, const SwitchSc
     // bucket sort: the run kernel may read A's output, and stops before the bucket B left out
     const uint32_t* nforeign = p.skip != 0xFFFFFFFFu ? sc.nforeign : nullptr;
     const uint32_t* unsorted = bucket ? sc.unsorted : nullptr;
-    auto* run = split ? (b.ps.on ? (narrow ? &k_switch_run2<true, true, true> : &k_switch_run2<true, false, true>)
-                                 : (narrow ? &k_switch_run2<false, true, true> : &k_switch_run2<false, false, true>))
-                      : (b.ps.on ? (narrow ? &k_switch_run2<true, true, false> : &k_switch_run2<true, false, false>)
-                                 : (narrow ? &k_switch_run2<false, true, false> : &k_switch_run2<false, false, false>));
+    // (the kernel's flags: PS step, per-block scales, narrow rows, split rows)
+    auto pick = [&](auto ps_on, auto blk) {
+        constexpr bool P = decltype(ps_on)::value, B = decltype(blk)::value;
+        return split ? (narrow ? &k_switch_run2<P, B, true, true> : &k_switch_run2<P, B, false, true>)
+                     : (narrow ? &k_switch_run2<P, B, true, false> : &k_switch_run2<P, B, false, false>);
+    };
+    auto* run = !b.ps.on ? pick(std::false_type{}, std::false_type{})
+              : b.ps.kblk ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
     hipLaunchKernelGGL(run, dim3(p.gr), dim3(kSwBlock), 0, b.s, *b.st, b.pkts, b.pay, b.npk, b.stride, kc, vc, b.actions,
                        p.win, p.plain ? ~(kAckBit | kPlainBit) : p.ack_hint ? ~kAckBit : 0xFFFFFFFFu, b.ps, nforeign, kn, vn,
                        unsorted, sc.k_out, sc.tab,
@@ -4298,8 +4326,9 @@ static int switch_apply_impl(const ina_switch_state_t* st, uint8_t* pkts, size_t
                              uint32_t seq0, const float* local, int k, double weight_step,
                              float* out, size_t n, uint8_t* acks, size_t ack_stride,
                              ina_nga_desc_t* ack_desc, int keep_forwarded, ina_stream_t stream, int phase,
-                             uint8_t* pay) {
-    if (int rc = check_k(k)) return rc;
+                             uint8_t* pay, const int8_t* kblk = nullptr) {
+    // (kblk: ina_switch_blk's per-block scales; k is then unread)
+    if (int rc = kblk ? INA_OK : check_k(k)) return rc;
     if (npk == 0) return INA_OK;
     if (!local || !out) return set_error(INA_EINVAL, "null pointer%s", "");
     if (((uintptr_t)local & 15u) || ((uintptr_t)out & 15u))
@@ -4316,9 +4345,9 @@ static int switch_apply_impl(const ina_switch_state_t* st, uint8_t* pkts, size_t
         return set_error(INA_EINVAL,
                          "the PS step needs V %% 4 == 0 <= 256 and 16-byte aligned rows and registers%s", "");
     const size_t nslots = (n + (size_t)st->V - 1) / (size_t)st->V;
-    PsFuse ps{local, out, n, ldexpf(1.0f, -k), (float)weight_step, seq0,
+    PsFuse ps{local, out, n, kblk ? 0.0f : ldexpf(1.0f, -k), (float)weight_step, seq0,
               nslots > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)nslots, acks, ack_stride, 1,
-              keep_forwarded ? 1 : 0, reinterpret_cast<uint2*>(ack_desc)};
+              keep_forwarded ? 1 : 0, reinterpret_cast<uint2*>(ack_desc), kblk};
     bool fused = false;
     if (int rc = switch_process_impl(st, pkts, npk, stride, desc, actions, scratch, stream, ps, &fused, phase, pay))
         return rc;
@@ -4347,6 +4376,22 @@ int ina_switch(const ina_switch_state_t* st, const ina_switch_batch_t* b, const 
     bool fused = false;
     return switch_process_impl(st, b->rows, b->npkts, stride, b->desc, b->actions, b->scratch, stream, off, &fused,
                                phase, b->pay);
+}
+
+int ina_switch_blk(const ina_switch_state_t* st, const ina_switch_batch_t* b, const ina_switch_ps_t* ps,
+                   const int8_t* kblk, int phase, ina_stream_t stream) {
+    if (!b) return set_error(INA_EINVAL, "null batch%s", "");
+    if (phase != INA_SWITCH_ALL && phase != INA_SWITCH_SORT && phase != INA_SWITCH_RUN)
+        return set_error(INA_EINVAL, "phase must be INA_SWITCH_ALL, _SORT or _RUN%s", "");
+    if (!ps) return set_error(INA_EINVAL, "the block-scaled switch is the PS step: null ps%s", "");
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    const bool split = b->pay != nullptr;
+    if (split && ps->ack_stride != 16 && ps->ack_stride != 0)
+        return set_error(INA_EINVAL, "split rows: the ack rows are header rows (ack_stride 16)%s", "");
+    return switch_apply_impl(st, b->rows, b->npkts, split ? 16 : b->stride, b->desc, b->actions, b->scratch,
+                             ps->seq0, ps->local, 0, ps->weight_step, ps->out, ps->n, ps->acks,
+                             split ? 16 : ps->ack_stride, ps->ack_desc, ps->keep_forwarded, stream, phase, b->pay,
+                             kblk);
 }
 
 int ina_switch_process(const ina_switch_state_t* st, uint8_t* pkts, size_t npk, size_t stride,

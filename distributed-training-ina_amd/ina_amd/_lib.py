@@ -146,6 +146,10 @@ SIGNATURES_PKT_BLK = {
     "ina_quantize_pack_nga_multi_split_blk": [_vp, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "ina_apply_completed_nga_blk": [_vp, _vp, _sz, _i, _sz, _vp, _u32, _vp, _vp, _d, _vp, _sz, _vp, _sz, _vp],
 }
+# the fused switch + PS step with per-block scales (include/ina_switch_blk.h)
+SIGNATURES_SWITCH_BLK = {
+    "ina_switch_blk": [C.POINTER(SwitchState), C.POINTER(SwitchBatch), C.POINTER(SwitchPs), _vp, _i, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -160,7 +164,8 @@ def open_library(path: str) -> C.CDLL:
     if not os.path.exists(path):
         raise InaError(f"libina.so not built at {path}; run `make -C {CSRC}` or __graft_entry__.build()")
     lib = C.CDLL(path)
-    for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK}.items():
+    for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
+                       **SIGNATURES_SWITCH_BLK}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

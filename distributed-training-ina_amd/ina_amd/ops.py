@@ -15,7 +15,9 @@ These are the kernels that replace the reference's CPU / switch arithmetic:
   ps_combine                 aggregate() (launch.py:42-52)
   absmax / scale_for         per-bucket dynamic scale for the quantiser (build-defined)
   block_scales / *_blk       one scale per block of V values instead (include/ina_blk.h); on the
-                             packet path the block is the packet (include/ina_pkt_blk.h)
+                             packet path the block is the packet (include/ina_pkt_blk.h), and
+                             Switch.process_apply* / run_apply take the int8 scales for k
+                             (include/ina_switch_blk.h)
 """
 from __future__ import annotations
 
@@ -1087,20 +1089,35 @@ class Switch:
         self._done.record(ts)
         self._done_stream = ts.cuda_stream
 
-    def _call(self, ts, rows, pay, npk, stride, d, actions, scratch, phase, ps=None, what="switch"):
+    def _call(self, ts, rows, pay, npk, stride, d, actions, scratch, phase, ps=None, what="switch", kblk=None):
         """One ina_switch call (include/ina.h): the batch struct, the PS step (or None), the
-        phase -- ordered after the previous call on this switch's scratch."""
+        phase -- ordered after the previous call on this switch's scratch.  kblk (int8, one scale
+        per slot of the PS step's bucket): ina_switch_blk (include/ina_switch_blk.h) instead."""
         b = _lib.SwitchBatch(rows.data_ptr(), pay.data_ptr() if pay is not None else None, npk, stride,
                              d.data_ptr() if d is not None else None, actions.data_ptr(), scratch.data_ptr())
         st = self._begin(ts)
-        check(load().ina_switch(C.byref(self._state), C.byref(b), C.byref(ps) if ps is not None else None,
-                                phase, st), what)
+        if kblk is not None:
+            check(load().ina_switch_blk(C.byref(self._state), C.byref(b), C.byref(ps), kblk.data_ptr(), phase, st),
+                  what)
+        else:
+            check(load().ina_switch(C.byref(self._state), C.byref(b), C.byref(ps) if ps is not None else None,
+                                    phase, st), what)
         self._end(ts)
 
     @staticmethod
     def _ps(seq0, local, k, weight_step, out, ack_ptr, ack_stride, ack_desc_ptr, keep_forwarded):
         return _lib.SwitchPs(seq0 & 0xFFFFFFFF, k, weight_step, local.data_ptr(), out.data_ptr(), local.numel(),
                              ack_ptr, ack_stride, ack_desc_ptr, int(keep_forwarded))
+
+    def _ps_scale(self, local, k):
+        """The PS step's scale argument: an int k (one global 2^-k, fp32 local), or an int8 tensor
+        of per-block scales, one per slot of local (2^-k[slot]; fp32 buckets only).  Returns
+        (k for the struct, the scale tensor or None)."""
+        if isinstance(k, torch.Tensor):
+            _blk_f32(local, "local")
+            return 0, _blk_scales_arg(k, -(-local.numel() // self.V), local, given=True)
+        _req(local, torch.float32, "local")
+        return k, None
 
     def process(self, pkts: torch.Tensor, actions: torch.Tensor | None = None,
                 desc: torch.Tensor | None = None) -> torch.Tensor:
@@ -1207,12 +1224,13 @@ class Switch:
         return actions
 
     def run_apply(self, pkts: torch.Tensor, actions: torch.Tensor, seq0: int, local: torch.Tensor,
-                  k: int, weight_step: float, out: torch.Tensor | None = None,
+                  k: int | torch.Tensor, weight_step: float, out: torch.Tensor | None = None,
                   acks: torch.Tensor | None = None, keep_forwarded: bool = True,
                   ack_desc: torch.Tensor | None = None):
-        """Second phase of process_apply() after sort().  Returns (actions, out)."""
+        """Second phase of process_apply() after sort() (k: an int, or int8 per-block scales as
+        process_apply() takes them).  Returns (actions, out)."""
         _req(pkts, torch.uint8, "pkts")
-        _req(local, torch.float32, "local")
+        k, kblk = self._ps_scale(local, k)
         npk, stride = pkts.shape
         _req(actions, torch.uint8, "actions")
         out = torch.empty_like(local) if out is None else out
@@ -1223,10 +1241,10 @@ class Switch:
         scratch = self._take_sorted(pkts, actions)
         self._call(torch.cuda.current_stream(pkts.device), pkts, None, npk, stride, None, actions, scratch,
                    _lib.INA_SWITCH_RUN, self._ps(seq0, local, k, weight_step, out, ack_ptr, ack_stride, ad,
-                                                 keep_forwarded), what="switch_run_apply")
+                                                 keep_forwarded), what="switch_run_apply", kblk=kblk)
         return actions, out
 
-    def process_apply(self, pkts: torch.Tensor, seq0: int, local: torch.Tensor, k: int,
+    def process_apply(self, pkts: torch.Tensor, seq0: int, local: torch.Tensor, k: int | torch.Tensor,
                       weight_step: float, out: torch.Tensor | None = None,
                       acks: torch.Tensor | None = None, keep_forwarded: bool = True,
                       actions: torch.Tensor | None = None, desc: torch.Tensor | None = None,
@@ -1235,9 +1253,13 @@ class Switch:
         slots update out = local + weight_step * sum * 2^-k and write their PS ack rows.
         keep_forwarded=False leaves completed packets as they arrived (consumed here).
         ack_desc (int64 [ack rows]): also written beside every ack row -- its descriptor, as
-        nga_descriptors(acks) would give -- for the next batch's sort.  Returns (actions, out)."""
+        nga_descriptors(acks) would give -- for the next batch's sort.  k: an int, or an int8
+        tensor of per-block scales, one per slot of local (ceil(local.numel() / V)): slot s is
+        dequantised with 2^-k[s] (ina_switch_blk; what quantize_pack_nga_blk / ..._multi_split_blk
+        packed it with), the results those of process() + apply_completed_blk().
+        Returns (actions, out)."""
         _req(pkts, torch.uint8, "pkts")
-        _req(local, torch.float32, "local")
+        k, kblk = self._ps_scale(local, k)
         npk, stride = pkts.shape
         actions = torch.empty(npk, dtype=torch.uint8, device=pkts.device) if actions is None else actions
         _req(actions, torch.uint8, "actions")
@@ -1255,7 +1277,7 @@ class Switch:
         ad = _ack_desc_arg(ack_desc, acks)
         self._call(torch.cuda.current_stream(pkts.device), pkts, None, npk, stride, d, actions, self._scratch,
                    _lib.INA_SWITCH_ALL, self._ps(seq0, local, k, weight_step, out, ack_ptr, ack_stride, ad,
-                                                 keep_forwarded), what="switch_process_apply")
+                                                 keep_forwarded), what="switch_process_apply", kblk=kblk)
         return actions, out
 
 
@@ -1277,13 +1299,14 @@ class Switch:
         return actions
 
     def process_apply_split(self, hdr: torch.Tensor, pay: torch.Tensor, seq0: int, local: torch.Tensor,
-                            k: int, weight_step: float, out: torch.Tensor | None = None,
+                            k: int | torch.Tensor, weight_step: float, out: torch.Tensor | None = None,
                             ack_hdr: torch.Tensor | None = None, ack_desc: torch.Tensor | None = None,
                             keep_forwarded: bool = True, actions: torch.Tensor | None = None,
                             desc: torch.Tensor | None = None):
         """process_apply() over split rows (ina_switch with batch.pay and a PS step): the PS ack rows are
-        header rows (uint8 [slots, 16]) with their descriptors in ack_desc.  Returns (actions, out)."""
-        _req(local, torch.float32, "local")
+        header rows (uint8 [slots, 16]) with their descriptors in ack_desc; k as process_apply() takes
+        it (an int, or int8 per-block scales).  Returns (actions, out)."""
+        k, kblk = self._ps_scale(local, k)
         npk = hdr.shape[0]
         hdr, pay = _split_rows(npk, self.V, hdr.device, hdr, pay)
         actions = torch.empty(npk, dtype=torch.uint8, device=hdr.device) if actions is None else actions
@@ -1305,7 +1328,7 @@ class Switch:
         self._call(torch.cuda.current_stream(hdr.device), hdr, pay, npk, 16, d, actions, scratch,
                    _lib.INA_SWITCH_ALL,
                    self._ps(seq0, local, k, weight_step, out, ack_hdr.data_ptr() if ack_hdr is not None else None,
-                            16, ad, keep_forwarded), what="switch_process_apply_split")
+                            16, ad, keep_forwarded), what="switch_process_apply_split", kblk=kblk)
         return actions, out
 
 

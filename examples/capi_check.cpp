@@ -182,6 +182,42 @@ int main() {
         HK(hipMemcpy(act2.data(), d_act, act2.size(), hipMemcpyDeviceToHost));
         if (act2 != act) ++bad;
         for (size_t i = 0; i < n; ++i) bad += std::memcmp(&out[i], &f[i], 4) != 0;
+        // one scale per packet (ina_switch_blk): the fused step equals its own two-call form, the
+        // switch alone and then ina_apply_completed_nga_blk, bit for bit (the rows above were
+        // consumed: keep_forwarded = 0 left them as they arrived)
+        std::vector<int8_t> kb(npk);
+        for (size_t p = 0; p < npk; ++p) kb[p] = (int8_t)(p == 1 ? -128 : k - 3 + (int)(p % 7));
+        int8_t* d_kb;
+        float* d_out2;
+        HK(hipMalloc(&d_kb, npk));
+        HK(hipMalloc(&d_out2, n * 4));
+        HK(hipMemcpy(d_kb, kb.data(), npk, hipMemcpyHostToDevice));
+        std::vector<float> out2(n);
+        std::vector<uint8_t> act4(act.size());
+        for (int two_calls = 0; two_calls < 2; ++two_calls) {
+            HK(hipMemsetAsync(d_count, 0, slots, s));
+            HK(hipMemsetAsync(d_frag, 0, slots * 4, s));
+            HK(hipMemsetAsync(d_regs, 0, (size_t)slots * V * 4, s));
+            HK(hipMemsetAsync(two_calls ? d_out2 : d_out, 0xff, n * 4, s));
+            if (!two_calls) {
+                CK(ina_switch_blk(&st, &sb, &ps, d_kb, INA_SWITCH_ALL, s));
+            } else {
+                CK(ina_switch(&st, &sb, nullptr, INA_SWITCH_ALL, s));
+                CK(ina_apply_completed_nga_blk(d_hdr, d_pay, (size_t)W * npk, V, 16, d_act, 1, d_zero, d_kb, 1.0,
+                                               d_out2, n, nullptr, 0, s));
+            }
+            HK(hipStreamSynchronize(s));
+            HK(hipMemcpy(act4.data(), d_act, act4.size(), hipMemcpyDeviceToHost));
+            if (act4 != act) ++bad;
+        }
+        HK(hipMemcpy(out.data(), d_out, n * 4, hipMemcpyDeviceToHost));
+        HK(hipMemcpy(out2.data(), d_out2, n * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            const int kk = kb[i / V] < -126 ? -126 : kb[i / V];
+            bad += std::memcmp(&out[i], &out2[i], 4) != 0 || out[i] != (float)sum[i] * std::ldexp(1.0f, -kk);
+        }
+        HK(hipFree(d_kb));
+        HK(hipFree(d_out2));
         HK(hipFree(d_hdr));
         HK(hipFree(d_pay));
     }
@@ -232,6 +268,6 @@ int main() {
     // the error path: a bad argument returns a code, sets a message, never exits
     const int rc = ina_sum_reduce_i32((const int32_t* const*)d_q, 0, d_sum, n, s);
     if (rc != INA_EINVAL || std::strlen(ina_last_error_string()) == 0) ++bad;
-    std::printf("capi_check: %zu values x %d workers (bulk reduce, NGA-256 pack/unpack, one-launch worker packs, switch + fused PS step, packed and split rows, two-phase sort/run across a tuning change), %zu mismatches\n", n, W, bad);
+    std::printf("capi_check: %zu values x %d workers (bulk reduce, NGA-256 pack/unpack, one-launch worker packs, switch + fused PS step, packed and split rows, the block-scaled fused step, two-phase sort/run across a tuning change), %zu mismatches\n", n, W, bad);
     return bad ? 1 : 0;
 }

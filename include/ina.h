@@ -396,6 +396,9 @@ int ina_switch(const ina_switch_state_t* st, const ina_switch_batch_t* batch, co
 /* The common case in one line: packed rows, headers read by the sort, no PS step. */
 int ina_switch_process(const ina_switch_state_t* st, uint8_t* pkts, size_t npkts, size_t stride,
                        uint8_t* actions, void* scratch, ina_stream_t stream);
+/* The PS step with per-block scales (2^-kblk[slot] for 2^-k); the contract is stated in
+ * ina_switch_blk.h, included here (it needs the switch types above). */
+#include "ina_switch_blk.h"   /* ina_switch_blk */
 
 /* Diagnostic: which slot-sort path the last call over `scratch` took (a batch of npkts
  * packets, more than 768 of them; the one-workgroup small-batch paths do not record one; the

@@ -4,7 +4,9 @@ the switch pass (the 8 workers' fused quantise+packs in one launch, one ina_swit
 --stats for the per-kernel breakdown of bench_extra's last packet-path row).  The run kernel
 writes the ack rows' descriptors (ack_desc), as bench.py's packet_path does.  SPLIT=1: the
 same step over split rows (16-byte header rows + 1 KiB payload rows).  V=32: NGA-32 packets
-(8 x 819,200 + 819,200 acks, a 2^20-slot pool), bench.py's packet_path_v32."""
+(8 x 819,200 + 819,200 acks, a 2^20-slot pool), bench.py's packet_path_v32.  BLK=1 (with SPLIT=1):
+the step with one scale per packet -- the AUTO multi split pack, then the fused step with the scales it
+wrote (ina_switch_blk)."""
 import os
 import sys
 
@@ -24,6 +26,9 @@ params = torch.randn(n, device=dev, generator=g)
 npk = n // V
 stride = ops.nga_stride(V)
 split = os.environ.get("SPLIT", "0") == "1"
+blk = os.environ.get("BLK", "0") == "1"
+if blk and not split:
+    sys.exit("BLK=1 needs SPLIT=1: the multi-worker pack with block scales writes split rows")
 if split:
     hdr = torch.zeros(((W + 1) * npk, 16), dtype=torch.uint8, device=dev)      # [acks | workers]
     pay = torch.zeros(((W + 1) * npk, 4 * V), dtype=torch.uint8, device=dev)
@@ -39,7 +44,13 @@ out = torch.empty_like(params)
 sw = ops.Switch(V, num_slots=slots, switch_id=1, device=dev)
 ops.nga_descriptors(acks, out=desc_ack)          # the first step's ack rows are another switch's
 for step in range(int(os.environ.get("STEPS", 6))):
-    if split:
+    if blk:
+        _, _, _, kblk = ops.quantize_pack_nga_multi_split_blk(xs, V, [w + 1 for w in range(W)], W, 1, 1, base=params,
+                                                              num_slots=slots, hdrs=hdrs_w, pays=pays_w,
+                                                              descs=list(desc_w.unbind(0)))
+        sw.process_apply_split(hdr, pay, 1, params, kblk, 1.0 / (W + 1), out=out, ack_hdr=acks, ack_desc=desc_ack,
+                               keep_forwarded=False, actions=acts, desc=desc)
+    elif split:
         ops.quantize_pack_nga_multi_split(xs, 16, V, [w + 1 for w in range(W)], W, 1, 1, base=params,
                                           num_slots=slots, hdrs=hdrs_w, pays=pays_w, descs=list(desc_w.unbind(0)))
         sw.process_apply_split(hdr, pay, 1, params, 16, 1.0 / (W + 1), out=out, ack_hdr=acks, ack_desc=desc_ack,
@@ -51,4 +62,4 @@ for step in range(int(os.environ.get("STEPS", 6))):
                          actions=acts, desc=desc, ack_desc=desc_ack)
 torch.cuda.synchronize()
 assert int((acts[npk:] == 1).sum()) == npk and bool((acts[:npk] == 3).all())
-print("done", "split" if split else "packed", (W + 1) * npk)
+print("done", "split" if split else "packed", "block scales" if blk else "k=16", (W + 1) * npk)

@@ -2079,11 +2079,6 @@ static_assert(INA_SWITCH_WIN_NARROW >= 1 && INA_SWITCH_WIN_NARROW <= 64, "a narr
 #ifndef INA_SWITCH_GRID
 #define INA_SWITCH_GRID (1 << 20)
 #endif
-// the narrow (V <= 32) run over a run table: 8 slots side by side per wave, the runs walked in
-// order (1), or one slot's 8 packets side by side (0; a lab build's A/B switch)
-#ifndef INA_SWITCH_NARROW_SLOTS
-#define INA_SWITCH_NARROW_SLOTS 1
-#endif
 static_assert(INA_SWITCH_WIN_SMALL >= 1 && INA_SWITCH_WIN_SMALL <= 64 && INA_SWITCH_WIN_LARGE >= 1 &&
               INA_SWITCH_WIN_LARGE <= 64, "a window is at most one wave of keys");
 // occupancy target of k_switch_run2 without the PS step (72 VGPRs -> 7 waves per SIMD)
@@ -2100,64 +2095,23 @@ static_assert(INA_SWITCH_WIN_SMALL >= 1 && INA_SWITCH_WIN_SMALL <= 64 && INA_SWI
 // packet chunk loads of the run kernel carry the streaming (nt) hint: 294 -> 276 us for
 // 819,200 NGA-256 packets (tools/lab/switch_lab.py, r01 session log switch_lab_nt.log);
 // nt on the forwarded-packet stores or on the key pass's header loads cost 10 us each
-#ifndef INA_SWITCH_NT
-#define INA_SWITCH_NT 1
-#endif
-// the tail chunk (bytes 1024..1039 of an NGA-256 row) always lies in the 128-byte line
-// the packet shares with the next row; loading it with the default policy keeps that line
-// in L2 for the neighbour: run kernel HBM reads 975.7 -> 911.4 MB, switch 268 -> 265 us.
-// A default-policy touch of each packet's head chunk as well read 870 MB but ran 288 us
-// (profiles/r01/lab/switch_lab_tail.log)
-#ifndef INA_SWITCH_TAIL_NT
-#define INA_SWITCH_TAIL_NT 0
-#endif
-// the batch's action bytes leave in one store (lane b: packet b) instead of one per packet:
-// 241.7 -> 234.9 us for the switch alone (profiles/r02/lab/switch_lab_actbatch.log); with
-// the PS step fused, once that kernel sat at 75 VGPRs / 6 waves either way, 294.3 -> 291.0
-// us (fuse_lab_actbatch_ps.log; at the time of the first lab it cost an occupancy step)
-#ifndef INA_SWITCH_ACT_BATCH
-#define INA_SWITCH_ACT_BATCH 1
-#endif
-// forwarded packets: written once per call, never read back by it (lab knob: nt).  Not
-// stream_store: its buffer resource starts at the wave's first active lane, and the lists and
-// sorted paths scatter a wave's rows below it too -- a write-through build of sw_st lost those
-// stores (jitter 64 and shuffled differed from the default build; it was also no faster on the
-// structured orders: profiles/r06/lab/switch_store_sc1_ab.log)
-__device__ __forceinline__ void sw_st(u32x4s v, u32x4s* p) {
-#if INA_SWITCH_FWD_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ u32x4s sw_ld(const u32x4s* p) {
-#if INA_SWITCH_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ u32x4s sw_ld(const u32x4s* p) { return __builtin_nontemporal_load(p); }
+// forwarded packets: written once per call, never read back by it; a plain store (nt cost 10
+// us, above).  Not stream_store: its buffer resource starts at the wave's first active lane,
+// and the lists and sorted paths scatter a wave's rows below it too -- a write-through build of
+// sw_st lost those stores (jitter 64 and shuffled differed from the default build; it was also
+// no faster on the structured orders: profiles/r06/lab/switch_store_sc1_ab.log)
+__device__ __forceinline__ void sw_st(u32x4s v, u32x4s* p) { *p = v; }
 
 // byte shuffles of the NGA payload (values at byte 15 + 4j, big-endian) as one v_perm_b32
 // each (selector byte k: 0-3 = second operand's bytes, 4-7 = first operand's):
 //   dec_be(hi, lo) = the BE word at bytes {lo.b3, hi.b0, hi.b1, hi.b2}
 //   enc_lo(prev, v) = LE dword of BE bytes 1..3 of prev followed by BE byte 0 of v
-#ifndef INA_SWITCH_PERM
-#define INA_SWITCH_PERM 1
-#endif
 __device__ __forceinline__ uint32_t dec_be(uint32_t hi, uint32_t lo) {
-#if INA_SWITCH_PERM
     return __builtin_amdgcn_perm(hi, lo, 0x03040506u);
-#else
-    return __builtin_bswap32(__builtin_amdgcn_alignbyte(hi, lo, 3));
-#endif
 }
 __device__ __forceinline__ uint32_t enc_lo(uint32_t prev, uint32_t v) {
-#if INA_SWITCH_PERM
     return __builtin_amdgcn_perm(v, prev, 0x07000102u);
-#else
-    return (__builtin_bswap32(prev) >> 8) | (v & 0xFF000000u);
-#endif
 }
 
 // PS co-located with the switch (ina_switch with a PS step): a completed slot's sum goes
@@ -2210,7 +2164,6 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
                                             uint32_t slot, bool ack_led, size_t q_begin, size_t q_end,
                                             PidFn&& pid_batch, bool drop_written = false) {
     // (drop_written: the detection pass stored every packet's drop by position)
-    constexpr bool kActBatch = INA_SWITCH_ACT_BATCH;
     const int lane = threadIdx.x & 63;
     const int V = st.V;
     const int L = V >> 2;                       // lanes holding values
@@ -2247,7 +2200,10 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
         uint32_t mypid = pid[0];                 // lane b: packet b's id
 #pragma unroll
         for (int b = 1; b < kB; ++b) mypid = lane == b ? pid[b] : mypid;
-        uint32_t act_v = 0;                      // lane b: packet b's action (kActBatch)
+        // lane b: packet b's action.  The batch's action bytes leave in one store instead of
+        // one per packet: 241.7 -> 234.9 us for the switch alone, 294.3 -> 291.0 us with the PS
+        // step fused (profiles/r02/lab/switch_lab_actbatch.log, fuse_lab_actbatch_ps.log)
+        uint32_t act_v = 0;
         if constexpr (kSplit) {                  // lane b: packet b's header row
             tl = *reinterpret_cast<const u32x4s*>(pkts + (size_t)mypid * 16);
 #pragma unroll
@@ -2256,13 +2212,11 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
                 a[b] = sw_ld(pk + (vl ? lane : 0));
             }
         } else {
-        if (wide) {
-#if INA_SWITCH_TAIL_NT
-            tl = sw_ld(reinterpret_cast<const u32x4s*>(pkts + (size_t)mypid * stride) + 64);
-#else
-            tl = *(reinterpret_cast<const u32x4s*>(pkts + (size_t)mypid * stride) + 64);
-#endif
-        }
+        // the tail chunk (bytes 1024..1039 of an NGA-256 row) always lies in the 128-byte line
+        // the packet shares with the next row; the default policy, not nt, keeps that line in
+        // L2 for the neighbour: run kernel HBM reads 975.7 -> 911.4 MB, switch 268 -> 265 us
+        // (profiles/r01/lab/switch_lab_tail.log)
+        if (wide) tl = *(reinterpret_cast<const u32x4s*>(pkts + (size_t)mypid * stride) + 64);
 #pragma unroll
         for (int b = 0; b < kB; ++b) {
             const u32x4s* pk = reinterpret_cast<const u32x4s*>(pkts + (size_t)pid[b] * stride);
@@ -2405,11 +2359,10 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
                     }
                 }
             }
-            if constexpr (kActBatch) act_v = lane == b ? (uint32_t)act : act_v;
-            else if (lane == 0 && !(drop_written && act == INA_ACT_DROP)) actions[pid[b]] = act;
+            act_v = lane == b ? (uint32_t)act : act_v;
         }
-        if constexpr (kActBatch)                      // one store for the batch
-            if (lane < nb && !(drop_written && act_v == INA_ACT_DROP)) actions[mypid] = (uint8_t)act_v;
+        // one store for the batch
+        if (lane < nb && !(drop_written && act_v == INA_ACT_DROP)) actions[mypid] = (uint8_t)act_v;
     }
     if (lane == 0) {
         st.count[slot] = (uint8_t)cnt;
@@ -2424,267 +2377,9 @@ __device__ __forceinline__ void run_segment(const ina_switch_state_t& st, uint8_
 }
 
 // Narrow packets (V <= 32: NGA-32, the P4 program's own format, headers.p4:40-73): run_segment
-// above gives each packet the whole wave, so only V/4 + 1 of its 64 lanes work and a batch's
-// packets go one after another -- at 6.5 M NGA-32 packets the kernel was instruction-bound
-// (0.19 of the HBM roofline).  Here the wave takes a batch's 8 packets side by side: lane
-// group g = lane / 8 holds packet g, its lane l = lane % 8 chunk l (values 4l..4l+3; the
-// group's last value lane also loads the tail chunk V/4).  The count / frag state machine
-// still runs packet by packet in arrival order, in SGPRs (8 x 3 header words by readlane),
-// and leaves per-packet masks (adds, overwrites, forwards, collisions, PS consumption); the
-// Processor adds become ONE segmented inclusive scan over the 8 groups (resets at the
-// count_reg == 1 overwrites, processor.p4:16-21) -- 3 shuffle steps -- so each packet's
-// running sum, the value the P4 program writes into it (processor.p4:22), is in its group's
-// lanes at once.  Same results as run_segment, packet for packet.
-__device__ __forceinline__ uint32_t from_lane(uint32_t x, int src) {
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)x);
-}
-// DPP row_shl:1 / row_shr:1: lane i reads lane i+1 / i-1 inside its 16-lane row (a group of 8
-// never needs its neighbour group: chunk l+1 of the group's last lane is the loaded tail, and
-// lane 0 of a group encodes the header chunk without its predecessor)
-__device__ __forceinline__ uint32_t from_next_in_row(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x101, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t from_prev_in_row(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x111, 0xF, 0xF, false);
-}
+// above gives each packet the whole wave, so only V/4 + 1 of its 64 lanes work.  The narrow
+// drivers below split the wave into 8 lane groups of 8 lanes, one slot per group.
 constexpr int kNarrowMaxV = 32;
-static_assert(kB == 8, "the narrow run puts a batch of 8 packets in 8 lane groups");
-
-// packet group g's row loads (lanes past L re-read chunk 0; the tail chunk is one request per
-// group); the caller's mypid is packet g's id
-template <bool kSplit>
-__device__ __forceinline__ void narrow_load(const uint8_t* __restrict__ pkts, size_t stride,
-                                            const uint8_t* __restrict__ pay, int V, uint32_t mypid,
-                                            u32x4s& a, u32x4s& tl) {
-    const int l = threadIdx.x & 7, L = V >> 2;
-    const bool vl = l < L;
-    if constexpr (kSplit) {                           // payload chunk l; the group's header row
-        a = sw_ld(reinterpret_cast<const u32x4s*>(pay + (size_t)mypid * (size_t)(4 * V)) + (vl ? l : 0));
-        tl = *reinterpret_cast<const u32x4s*>(pkts + (size_t)mypid * 16);
-    } else {
-        const u32x4s* pk = reinterpret_cast<const u32x4s*>(pkts + (size_t)mypid * stride);
-        a = sw_ld(pk + (vl ? l : 0));
-        tl = *(pk + L);
-    }
-}
-
-template <bool kPs, bool kBlk, bool kSplit, typename PidFn>
-__device__ __forceinline__ void run_segment_narrow(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
-                                                   size_t stride, uint8_t* __restrict__ pay,
-                                                   uint8_t* __restrict__ actions,
-                                                   const PsFuse& ps, uint32_t slot, bool ack_led,
-                                                   size_t q_begin, size_t q_end, PidFn&& pid_batch) {
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 3, l = lane & 7;      // packet group, value lane
-    const int V = st.V;
-    const int L = V >> 2;                       // value lanes per group (<= 8)
-    const bool vl = l < L;
-    uint32_t cnt = __builtin_amdgcn_readfirstlane((uint32_t)st.count[slot]);
-    uint32_t frag = ack_led ? 0u : __builtin_amdgcn_readfirstlane(st.frag[slot]);
-    u32x4s reg = {0u, 0u, 0u, 0u};              // the slot's running registers, in every group
-    bool have_reg = false;
-    for (size_t q0 = q_begin; q0 < q_end; q0 += kB) {
-        const int nb = (int)((q_end - q0) < (size_t)kB ? (q_end - q0) : (size_t)kB);
-        uint32_t pid[kB];
-        pid_batch(q0, nb, pid);
-#pragma unroll
-        for (int b = 1; b < kB; ++b) pid[b] = b < nb ? pid[b] : pid[0];
-        uint32_t mypid = pid[0], lanepid = pid[0];   // group g's packet; lane b's (actions)
-#pragma unroll
-        for (int b = 1; b < kB; ++b) {
-            mypid = g == b ? pid[b] : mypid;
-            lanepid = lane == b ? pid[b] : lanepid;
-        }
-        u32x4s a, tl;
-        narrow_load<kSplit>(pkts, stride, pay, V, mypid, a, tl);
-        const u32x4s hw = kSplit ? tl : a;            // header words (lane 8b: packet b's)
-        // per-group outcome of the state machine: adds, overwrites, forwards, PS consumption,
-        // collisions (group g's packet, in every lane of the group)
-        bool add_g, first_g, fwd_g, ps_g, coll_g;
-        uint32_t act_v = 0, ps_slot_v = 0;
-        int lastb;                                    // the batch's last adding packet (-1: none)
-        bool before;                                  // an add before the batch's first overwrite
-        // header words of packet g in every lane of its group; lane b also packet b's
-        const uint32_t g1 = kSplit ? hw.y : from_lane(hw.y, 8 * g), g2 = kSplit ? hw.z : from_lane(hw.z, 8 * g),
-                       g3 = kSplit ? hw.w : from_lane(hw.w, 8 * g);
-        const uint32_t gfin = __builtin_bswap32((g2 >> 24) | (g3 << 8)), ghc = g1 & 0xFFu;
-        // the common batch -- no PS ack, every frag id the slot's (or the first packet's when
-        // the slot is free), one degree H with count < H -- needs no packet-by-packet walk:
-        // packet b's count is (count + b + 1) mod H (ngaa.p4:66-78), it completes the slot when
-        // that is 0 and overwrites the registers when it is 1
-        const uint32_t F = frag ? frag : (uint32_t)__builtin_amdgcn_readlane(gfin, 0);
-        const uint32_t H = (uint32_t)__builtin_amdgcn_readlane(ghc, 0);
-        const bool odd = g < nb && (((g1 >> 14) & 1u) || gfin != F || ghc != H);
-        if (__ballot(odd) == 0 && H >= 1u && cnt < H) {
-            frag = F;
-            const uint32_t cg = (cnt + (uint32_t)g + 1u) % H;
-            const uint32_t cl = (cnt + (uint32_t)lane + 1u) % H;   // lane b as packet b
-            const bool cons = kPs && F - ps.seq0 < ps.nslots;       // the PS takes this slot
-            add_g = g < nb;
-            first_g = add_g && cg == 1u;
-            ps_g = add_g && cons && cg == 0u;
-            fwd_g = add_g && (cg == 0u || st.write_dropped) && (!ps_g || ps.keep_fwd);
-            coll_g = false;
-            if (cons) ps_slot_v = F - ps.seq0;
-            act_v = cl == 0u ? INA_ACT_FWD_AGG : INA_ACT_DROP;
-            lastb = nb - 1;
-            before = !(H > 1u && cnt == 0u);          // count 0: packet 0 overwrites
-            cnt = __builtin_amdgcn_readfirstlane((cnt + (uint32_t)nb) % H);
-        } else {
-        // the state machine, packet by packet in arrival order (SGPRs, scalar branches)
-        uint32_t m_add = 0, m_first = 0, m_fwd = 0, m_coll = 0, m_ps = 0;
-#pragma unroll
-        for (int b = 0; b < kB; ++b) {
-            if (b >= nb) break;
-            const uint32_t h1 = __builtin_amdgcn_readlane(hw.y, 8 * b),
-                           h2 = __builtin_amdgcn_readlane(hw.z, 8 * b),
-                           h3 = __builtin_amdgcn_readlane(hw.w, 8 * b);
-            const uint32_t hcount = h1 & 0xFFu, flags = (h1 >> 8) & 0xFFu;
-            const uint32_t frag_in =
-                __builtin_amdgcn_readfirstlane(__builtin_bswap32((h2 >> 24) | (h3 << 8)));
-            uint32_t act;
-            if ((flags >> 6) & 1u) {                     // ack: reset_id (fragcheck.p4:26-31)
-                frag = 0;
-                act = INA_ACT_FWD_ACK;
-            } else {
-                if (frag == 0) frag = frag_in;           // write_read_id (fragcheck.p4:14-24)
-                if (frag != frag_in) {                   // collision (ngaa.p4:177-181)
-                    act = INA_ACT_FWD_COLLISION;
-                    m_coll |= 1u << b;
-                } else {
-                    cnt = (cnt + 1u) & 0xFFu;            // read_add_count (ngaa.p4:66-78)
-                    if (cnt == hcount) cnt = 0;
-                    cnt = __builtin_amdgcn_readfirstlane(cnt);
-                    m_add |= 1u << b;
-                    if (cnt == 1u) m_first |= 1u << b;   // processor.p4:16-21 overwrite
-                    act = cnt == 0 ? INA_ACT_FWD_AGG : INA_ACT_DROP;   // ngaa.p4:170-175
-                    const uint32_t ps_slot = frag_in - ps.seq0;
-                    const bool consumed = kPs && act == INA_ACT_FWD_AGG && ps_slot < ps.nslots;
-                    if (consumed) {
-                        m_ps |= 1u << b;
-                        ps_slot_v = g == b ? ps_slot : ps_slot_v;
-                    }
-                    if ((act != INA_ACT_DROP || st.write_dropped) && (!consumed || ps.keep_fwd))
-                        m_fwd |= 1u << b;
-                }
-            }
-            act_v = lane == b ? act : act_v;
-        }
-        add_g = (m_add >> g) & 1u;
-        first_g = (m_first >> g) & 1u;
-        fwd_g = (m_fwd >> g) & 1u;
-        ps_g = (m_ps >> g) & 1u;
-        coll_g = (m_coll >> g) & 1u;
-        lastb = m_add ? 31 - __builtin_clz(m_add) : -1;
-        // the stored registers count only before the batch's first overwrite
-        before = (m_first ? m_add & ((m_first & (0u - m_first)) - 1u) : m_add) != 0u;
-        }
-        if (lane < nb) actions[lanepid] = (uint8_t)act_v;   // one store for the batch
-        if (coll_g && l == 0)                              // only the flag byte changes
-            reinterpret_cast<uint32_t*>(pkts + (size_t)mypid * (kSplit ? 16 : stride))[1] =
-                g1 | ((uint32_t)INA_FLAG_COLLISION << 8);
-        if (lastb >= 0) {
-            // values 4l..4l+3 of packet g: chunk l and chunk l+1 (the neighbour lane, or the
-            // tail for the group's last value lane)
-            u32x4s x;
-            if constexpr (kSplit) {
-                x.x = __builtin_bswap32(a.x); x.y = __builtin_bswap32(a.y);
-                x.z = __builtin_bswap32(a.z); x.w = __builtin_bswap32(a.w);
-            } else {
-                u32x4s c;
-                c.x = from_next_in_row(a.x); c.y = from_next_in_row(a.y);
-                c.z = from_next_in_row(a.z); c.w = from_next_in_row(a.w);
-                if (l == L - 1) c = tl;
-                x.x = dec_be(c.x, a.w); x.y = dec_be(c.y, c.x); x.z = dec_be(c.z, c.y); x.w = dec_be(c.w, c.z);
-            }
-            uint32_t f = first_g ? 1u : 0u;
-            if (!add_g) x = u32x4s{0u, 0u, 0u, 0u};
-            // segmented inclusive scan over the groups (a reset at each overwrite)
-#pragma unroll
-            for (int d = 1; d < kB; d <<= 1) {
-                const int src = lane - 8 * d;
-                u32x4s y;
-                y.x = from_lane(x.x, src); y.y = from_lane(x.y, src);
-                y.z = from_lane(x.z, src); y.w = from_lane(x.w, src);
-                const uint32_t fy = from_lane(f, src);
-                if (g >= d && !f) {
-                    x += y;
-                    f |= fy;
-                }
-            }
-            // the stored registers count only before the batch's first overwrite; load them
-            // if an add comes before it and no earlier batch left them in registers
-            if (before && !have_reg)
-                reg = vl ? *reinterpret_cast<const u32x4s*>(st.regs + (size_t)slot * V + 4 * l)
-                         : u32x4s{0u, 0u, 0u, 0u};
-            const u32x4s S = f ? x : x + reg;        // packet g's running sum
-            // the registers after the batch: the last adding packet's running sum
-            const int src = 8 * lastb + l;
-            reg.x = from_lane(S.x, src); reg.y = from_lane(S.y, src);
-            reg.z = from_lane(S.z, src); reg.w = from_lane(S.w, src);
-            have_reg = true;
-            if (kPs && ps_g) {                       // launch.py:46-50 with the switch's sum
-                const size_t e0 = (size_t)ps_slot_v * (size_t)V + 4 * (size_t)l;
-                const float inv = ps_inv<kBlk>(ps, ps_slot_v);   // (one address per group)
-                if (vl && e0 + 4 <= ps.n) {
-                    const f32x4s lo = *reinterpret_cast<const f32x4s*>(ps.local + e0);
-                    f32x4s r;
-                    r.x = __fadd_rn(lo.x, __fmul_rn(__fmul_rn((float)(int32_t)S.x, inv), ps.ws));
-                    r.y = __fadd_rn(lo.y, __fmul_rn(__fmul_rn((float)(int32_t)S.y, inv), ps.ws));
-                    r.z = __fadd_rn(lo.z, __fmul_rn(__fmul_rn((float)(int32_t)S.z, inv), ps.ws));
-                    r.w = __fadd_rn(lo.w, __fmul_rn(__fmul_rn((float)(int32_t)S.w, inv), ps.ws));
-                    __builtin_nontemporal_store(r, reinterpret_cast<f32x4s*>(ps.out + e0));
-                } else if (vl) {
-                    const uint32_t rv[4] = {S.x, S.y, S.z, S.w};
-                    for (int t = 0; t < 4 && e0 + t < ps.n; ++t)
-                        ps.out[e0 + t] = __fadd_rn(ps.local[e0 + t],
-                                                   __fmul_rn(__fmul_rn((float)(int32_t)rv[t], inv), ps.ws));
-                }
-                if (l == 0 && ps.acks) {             // the PS ack (fragcheck.p4:26-31)
-                    u32x4s hd = hw;
-                    hd.y = (hd.y & ~0xFF00u) | ((uint32_t)INA_FLAG_ACK << 8);
-                    if constexpr (!kSplit) hd.w = (hd.w & 0x00FFFFFFu) | (S.x & 0xFF000000u);
-                    *reinterpret_cast<u32x4s*>(ps.acks + (size_t)ps_slot_v * ps.ack_stride) = hd;
-                    if (ps.ack_desc) ps.ack_desc[ps_slot_v] = uint2{hd.y, hd.z};
-                }
-            }
-            if (kSplit && fwd_g) {                   // out_value -> the payload row (processor.p4:22)
-                const u32x4s e{__builtin_bswap32(S.x), __builtin_bswap32(S.y), __builtin_bswap32(S.z),
-                               __builtin_bswap32(S.w)};
-                if (vl) sw_st(e, reinterpret_cast<u32x4s*>(pay + (size_t)mypid * (size_t)(4 * V)) + l);
-            } else if (fwd_g) {                      // out_value -> payload (processor.p4:22)
-                u32x4s p;                            // values of lane l-1
-                p.x = from_prev_in_row(S.x); p.y = from_prev_in_row(S.y);
-                p.z = from_prev_in_row(S.z); p.w = from_prev_in_row(S.w);
-                u32x4s e = a;
-                if (l == 0) {
-                    e.w = (e.w & 0x00FFFFFFu) | (S.x & 0xFF000000u);
-                } else {
-                    e.x = enc_lo(p.x, p.y);
-                    e.y = enc_lo(p.y, p.z);
-                    e.z = enc_lo(p.z, p.w);
-                    e.w = enc_lo(p.w, S.x);
-                }
-                u32x4s* dst = reinterpret_cast<u32x4s*>(pkts + (size_t)mypid * stride);
-                if (vl) sw_st(e, dst + l);
-                if (l == L - 1) {                    // the tail chunk from the last value lane
-                    u32x4s o;
-                    o.x = enc_lo(S.x, S.y);
-                    o.y = enc_lo(S.y, S.z);
-                    o.z = enc_lo(S.z, S.w);
-                    o.w = enc_lo(S.w, tl.w);
-                    sw_st(o, dst + L);
-                }
-            }
-        }
-    }
-    if (lane == 0) {
-        st.count[slot] = (uint8_t)cnt;
-        st.frag[slot] = frag;
-    }
-    if (have_reg && g == 0 && vl)
-        __builtin_nontemporal_store(reg, reinterpret_cast<u32x4s*>(st.regs + (size_t)slot * V + 4 * l));
-}
 
 // packets' loads in flight per lane group (the VGPRs buy occupancy): 1 for packed and for split
 // rows.  Interleaved A/Bs at NGA-32 C3 size (profiles/r04/lab/slot_inflight_ab_v32_*.log):
@@ -2697,9 +2392,6 @@ __device__ __forceinline__ void run_segment_narrow(const ina_switch_state_t& st,
 // worker-major and shuffled equal; 2 at 8 waves spills, profiles/r05/lab/packed_inflight_waves_ab_v32.log)
 #ifndef INA_SWITCH_SLOT_INFLIGHT
 #define INA_SWITCH_SLOT_INFLIGHT 1
-#endif
-#ifndef INA_PACKED_UNALIGNED
-#define INA_PACKED_UNALIGNED 1
 #endif
 #ifndef INA_SWITCH_SLOT_INFLIGHT_SPLIT
 #define INA_SWITCH_SLOT_INFLIGHT_SPLIT 1
@@ -2719,20 +2411,15 @@ __device__ __forceinline__ void st_row16(uint8_t* p, const u32x4s& v) { __builti
 
 // one packet of a lane group's slot (group-uniform: every lane of the group runs it with the
 // same header): ack / collision / count / Processor add, the PS step, the rewritten packet
-// and its action byte.  m: this lane's payload chunk (packed rows: row chunk l + 1), h: the
-// header chunk / header row; ack_known: a PS ack by its sort key (then m and h are unread)
-template <bool kPs, bool kBlk, bool kSplit, int kThr = kSwBlock>
+// and its action byte.  m: this lane's payload chunk (packed rows: the 16 bytes at 15 + 16 l), h:
+// the header chunk / header row; ack_known: a PS ack by its sort key (then m and h are unread)
+template <bool kPs, bool kBlk, bool kSplit>
 __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                              size_t stride, uint8_t* __restrict__ pay,
                                              uint8_t* __restrict__ actions, const PsFuse& ps, uint32_t slot,
                                              uint32_t pid, const u32x4s& m, const u32x4s& h, bool ack_known,
                                              uint32_t& cnt, uint32_t& frag, u32x4s& reg, bool& have_reg,
                                              bool drop_written = false) {
-    // neighbour lanes' words go through LDS, not DPP: a DPP move whose source lane is disabled
-    // returns its fallback, and the compiler may narrow EXEC around a DPP that feeds a per-lane
-    // select (it did: l == 0 ? h3 : row_shr(m.w) became a branch on l != 0).  Every lane of the
-    // group stores, then reads its neighbour's word (LDS executes one wave's ops in order)
-    __shared__ uint32_t s_xch[kThr];
     const int l = threadIdx.x & 7;
     const int V = st.V, L = V >> 2;
     const bool vl = l < L;
@@ -2755,22 +2442,9 @@ __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8
             cnt = (cnt + 1u) & 0xFFu;        // read_add_count (ngaa.p4:66-78)
             if (cnt == hcount) cnt = 0;
             const bool first = cnt == 1u;
-            u32x4s v;                        // values 4l..4l+3
-            if constexpr (kSplit || INA_PACKED_UNALIGNED) {
-                v.x = __builtin_bswap32(m.x); v.y = __builtin_bswap32(m.y);
-                v.z = __builtin_bswap32(m.z); v.w = __builtin_bswap32(m.w);
-            } else {
-                // value 4l starts at the last byte of chunk l: the previous lane's
-                // chunk, or the header chunk for the group's lane 0
-                s_xch[threadIdx.x] = m.w;
-                __builtin_amdgcn_wave_barrier();
-                const uint32_t pw = l == 0 ? h3 : s_xch[threadIdx.x - 1];
-                __builtin_amdgcn_wave_barrier();
-                v.x = dec_be(m.x, pw);
-                v.y = dec_be(m.y, m.x);
-                v.z = dec_be(m.z, m.y);
-                v.w = dec_be(m.w, m.z);
-            }
+            // values 4l..4l+3
+            const u32x4s v{__builtin_bswap32(m.x), __builtin_bswap32(m.y), __builtin_bswap32(m.z),
+                           __builtin_bswap32(m.w)};
             if (first) {                     // processor.p4:16-21
                 reg = v;
             } else {
@@ -2810,34 +2484,12 @@ __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8
             }
             if ((act != INA_ACT_DROP || st.write_dropped) && (!consumed || ps.keep_fwd)) {
                 // out_value -> the packet (processor.p4:22)
+                const u32x4s e{__builtin_bswap32(reg.x), __builtin_bswap32(reg.y),
+                               __builtin_bswap32(reg.z), __builtin_bswap32(reg.w)};
                 if constexpr (kSplit) {
-                    const u32x4s e{__builtin_bswap32(reg.x), __builtin_bswap32(reg.y),
-                                   __builtin_bswap32(reg.z), __builtin_bswap32(reg.w)};
                     if (vl) sw_st(e, reinterpret_cast<u32x4s*>(pay + (size_t)pid * (size_t)(4 * V)) + l);
-                } else if constexpr (INA_PACKED_UNALIGNED) {
-                    const u32x4s e{__builtin_bswap32(reg.x), __builtin_bswap32(reg.y),
-                                   __builtin_bswap32(reg.z), __builtin_bswap32(reg.w)};
-                    if (vl) st_row16(pkts + (size_t)pid * stride + 15 + 16 * l, e);
                 } else {
-                    // chunk l + 1: bytes 1..3 of values 4l..4l+3, then byte 0 of value
-                    // 4l + 4 (the next lane's; the group's last value lane keeps the
-                    // padding byte); lane 0 also rewrites the header chunk's byte 15
-                    u32x4s* dst = reinterpret_cast<u32x4s*>(pkts + (size_t)pid * stride);
-                    s_xch[threadIdx.x] = reg.x;
-                    __builtin_amdgcn_wave_barrier();
-                    const uint32_t nx = l < L - 1 ? s_xch[threadIdx.x + 1] : m.w;
-                    __builtin_amdgcn_wave_barrier();
-                    u32x4s e;
-                    e.x = enc_lo(reg.x, reg.y);
-                    e.y = enc_lo(reg.y, reg.z);
-                    e.z = enc_lo(reg.z, reg.w);
-                    e.w = enc_lo(reg.w, nx);
-                    if (vl) sw_st(e, dst + l + 1);
-                    if (l == 0) {
-                        u32x4s c0 = h;
-                        c0.w = (c0.w & 0x00FFFFFFu) | (reg.x & 0xFF000000u);
-                        sw_st(c0, dst);
-                    }
+                    if (vl) st_row16(pkts + (size_t)pid * stride + 15 + 16 * l, e);
                 }
             }
         }
@@ -2858,9 +2510,6 @@ __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8
 // other segment in the wave -> false, and the caller walks the wave's segments packet by packet
 // (the rows it reads then come from L2).  Lane l of group g: pidl = the id of packet l of group
 // g's segment, ackl its PS-ack hint (sort key bit 31); has = the group holds a segment.
-#ifndef INA_SWITCH_SEG8
-#define INA_SWITCH_SEG8 1
-#endif
 #ifndef INA_SEG8_FLIGHT
 #define INA_SEG8_FLIGHT 4
 #endif
@@ -2971,6 +2620,88 @@ __device__ __forceinline__ bool seg8_fast(const ina_switch_state_t& st, uint8_t*
     return true;
 }
 
+// ---- what the three narrow drivers below share ---------------------------------------------
+// one packet's row loads for lane l of its group, as group_packet takes them: the lane's payload
+// chunk (lanes past V/4 re-read chunk 0), and the header row (split rows) or header chunk
+// (packed rows)
+template <bool kSplit>
+__device__ __forceinline__ u32x4s row_payload(const uint8_t* __restrict__ pkts, size_t stride,
+                                              const uint8_t* __restrict__ pay, int V, uint32_t pid, int l, bool vl) {
+    if constexpr (kSplit)
+        return sw_ld(reinterpret_cast<const u32x4s*>(pay + (size_t)pid * (size_t)(4 * V)) + (vl ? l : 0));
+    else
+        return ld_row16(pkts + (size_t)pid * stride + 15 + 16 * (vl ? l : 0));
+}
+template <bool kSplit>
+__device__ __forceinline__ u32x4s row_header(const uint8_t* __restrict__ pkts, size_t stride, uint32_t pid) {
+    return *reinterpret_cast<const u32x4s*>(pkts + (size_t)pid * (kSplit ? 16 : stride));
+}
+
+// one loaded packet of the groups' slots through group_packet; a packet no group of the wave
+// holds (in false in every lane) is skipped by a scalar branch
+template <bool kPs, bool kBlk, bool kSplit>
+__device__ __forceinline__ void narrow_packet(const ina_switch_state_t& st, uint8_t* __restrict__ pkts, size_t stride,
+                                              uint8_t* __restrict__ pay, uint8_t* __restrict__ actions,
+                                              const PsFuse& ps, uint32_t slot, uint32_t pid, const u32x4s& m,
+                                              const u32x4s& h, bool in, bool ack, uint32_t& cnt, uint32_t& frag,
+                                              u32x4s& reg, bool& have_reg, bool drop_written) {
+    if (!__ballot(in)) return;
+    if (!in) return;
+    group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid, m, h, ack, cnt, frag, reg, have_reg,
+                                    drop_written);
+}
+
+// a group's slot state back to memory: count / frag by the group's lane 0 (wr: the group walked
+// a segment), the registers by its value lanes (nt, as in run_segment)
+__device__ __forceinline__ void narrow_store_state(const ina_switch_state_t& st, uint32_t slot, bool wr, uint32_t cnt,
+                                                   uint32_t frag, const u32x4s& reg, bool have_reg, int l, bool vl) {
+    if (wr && l == 0) {
+        st.count[slot] = (uint8_t)cnt;
+        st.frag[slot] = frag;
+    }
+    if (have_reg && vl)
+        __builtin_nontemporal_store(reg, reinterpret_cast<u32x4s*>(st.regs + (size_t)slot * st.V + 4 * l));
+}
+
+// a sorted key's hint bits (xm = ~kmask, the bits above the slot): bit 0 a PS ack, bit 1 a plain packet
+__device__ __forceinline__ uint32_t key_hints(uint32_t key, uint32_t xm) {
+    return ((key & xm & kAckBit) ? 1u : 0u) | ((key & xm & kPlainBit) ? 2u : 0u);
+}
+
+// the header fields group_packet reads of a plain packet (kPlainBit), made from its slot: words
+// 1-3 of the row (count, flags 0, index = slot, switch id, frag id, pad 0)
+__device__ __forceinline__ u32x4s plain_header(const ina_switch_state_t& st, uint32_t slot, uint32_t plB,
+                                               uint32_t plC) {
+    const uint32_t fr = slot + plB;
+    return u32x4s{0u, plC | (__builtin_bswap32(slot) & 0xFFFFu) << 16,
+                  (__builtin_bswap32(slot) >> 16) | ((uint32_t)(uint8_t)st.switch_id << 16) | (fr & 0xFF000000u),
+                  (__builtin_bswap32(fr) >> 8)};
+}
+
+// the end of a segment in sorted order: the first position after the head (lane hl of the
+// window at w0, whose masked keys are the lanes' ki) whose key is not `slot` -- in the window by
+// a ballot, past it by 64-wide strides over the keys (key(j): sorted position j's key)
+template <typename KeyFn>
+__device__ __forceinline__ size_t segment_end(const KeyFn& key, uint32_t kmask, uint32_t ki, uint32_t slot, int hl,
+                                              size_t w0, size_t npk) {
+    const int lane = threadIdx.x & 63;
+    size_t end;
+    const unsigned long long dm = __ballot(ki != slot) & ~((2ull << hl) - 1ull);
+    if (dm) {
+        end = w0 + (size_t)__builtin_ctzll(dm);
+    } else {
+        size_t j0 = w0 + 64;
+        for (;;) {
+            const size_t j = j0 + (size_t)lane;
+            const bool diff = j >= npk || (key(j) & kmask) != slot;
+            const unsigned long long mm = __ballot(diff);
+            if (mm) { end = j0 + (size_t)__builtin_ctzll(mm); break; }
+            j0 += 64;
+        }
+    }
+    return end;
+}
+
 // Narrow packets (V <= 32) in sorted order (the bucket sort's arrays, or a batch already in
 // slot order read in place), segment-parallel: each wave takes windows of `win` sorted
 // positions, and its 8 lane groups take the segments that START in the window, 8 at a time
@@ -2994,11 +2725,23 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
     const bool vl = l < L;
     const uint32_t NS = st.num_slots;
     const uint32_t xm = ~kmask;                           // the hint bits: PS ack, plain
-    // the window's packet ids and ack hints, for the lane groups to pick from (through LDS,
-    // written by every lane of the wave: see group_packet on DPP / permutes and EXEC)
+    // the window's packet ids and hints, for the lane groups to pick from.  Through LDS, written
+    // by every lane of the wave, not DPP or permutes: a DPP move whose source lane is disabled
+    // returns its fallback, and the compiler may narrow EXEC around one that feeds a per-lane select
     __shared__ uint32_t s_wid[kSwBlock], s_wack[kSwBlock];
     const int wb = (int)threadIdx.x & ~63;
     for (size_t w0 = wave * win; w0 < npk; w0 += nwaves * win) {
+        // id and hints of window-relative position q: the window's (LDS), past it from memory
+        auto entry = [&](uint32_t q, uint32_t& pid, uint32_t& hint) {
+            if (q < 64u) {
+                pid = s_wid[wb + (int)q];
+                hint = s_wack[wb + (int)q];
+            } else {
+                const size_t qa = w0 + (size_t)q;
+                pid = ids ? ids[qa] : (uint32_t)qa;
+                hint = key_hints(keys(qa), xm);
+            }
+        };
         const size_t i = w0 + (size_t)lane;
         const uint32_t kr = i < npk ? keys(i) : NS;
         const uint32_t ki = kr & kmask;                   // slot (bit 31: PS-ack hint)
@@ -3007,8 +2750,7 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
         const bool head = (uint32_t)lane < win && i < npk && ki < NS && (i == 0 || kp != ki);
         __builtin_amdgcn_wave_barrier();
         s_wid[threadIdx.x] = idw;
-        // bit 0: a PS ack by its key (with the hint); bit 1: a plain packet
-        s_wack[threadIdx.x] = ((kr & xm & kAckBit) ? 1u : 0u) | ((kr & xm & kPlainBit) ? 2u : 0u);
+        s_wack[threadIdx.x] = key_hints(kr, xm);
         __builtin_amdgcn_wave_barrier();
         unsigned long long hm = __ballot(head);
         while (hm) {
@@ -3020,20 +2762,7 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
                 const int hl = __builtin_ctzll(hm);
                 hm &= hm - 1;
                 const uint32_t slot_b = __builtin_amdgcn_readlane(ki, hl);
-                size_t end;
-                const unsigned long long dm = __ballot(ki != slot_b) & ~((2ull << hl) - 1ull);
-                if (dm) {
-                    end = w0 + (size_t)__builtin_ctzll(dm);
-                } else {
-                    size_t j0 = w0 + 64;
-                    for (;;) {
-                        const size_t j = j0 + (size_t)lane;
-                        const bool diff = j >= npk || (keys(j) & kmask) != slot_b;
-                        const unsigned long long mm = __ballot(diff);
-                        if (mm) { end = j0 + (size_t)__builtin_ctzll(mm); break; }
-                        j0 += 64;
-                    }
-                }
+                const size_t end = segment_end(keys, kmask, ki, slot_b, hl, w0, npk);
                 const uint32_t len_b = (uint32_t)(end - (w0 + (size_t)hl));
                 maxlen = len_b > maxlen ? len_b : maxlen;
                 if (g == b) {
@@ -3043,29 +2772,16 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
                 }
             }
             const bool has = hlen != 0;
-#if INA_SWITCH_SEG8
             if constexpr (kSplit && !kPs) {
                 // every segment of these heads 8 packets long: the whole-segment path
                 if (maxlen == 8u && !__ballot(has && hlen != 8u)) {
-                    const uint32_t q = hst + (uint32_t)l;
                     uint32_t pidl = 0u, hint = 0u;
-                    if (has) {
-                        if (q < 64u) {
-                            pidl = s_wid[wb + (int)q];
-                            hint = s_wack[wb + (int)q];
-                        } else {
-                            const size_t qa = w0 + (size_t)q;
-                            pidl = ids ? ids[qa] : (uint32_t)qa;
-                            const uint32_t kq = keys(qa) & xm;
-                            hint = ((kq & kAckBit) ? 1u : 0u) | ((kq & kPlainBit) ? 2u : 0u);
-                        }
-                    }
+                    if (has) entry(hst + (uint32_t)l, pidl, hint);
                     if (seg8_fast<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, has, hslot, pidl, (hint & 1u) != 0u,
                                                drop_written, ~0u, (hint & 2u) != 0u, plB, plC))
                         continue;
                 }
             }
-#endif
             uint32_t cnt = 0, frag = 0;
             if (has) {
                 cnt = st.count[hslot];
@@ -3080,62 +2796,23 @@ __device__ __forceinline__ void window_slots_narrow(const ina_switch_state_t& st
 #pragma unroll
                 for (int j = 0; j < kP; ++j) {
                     const uint32_t k = k0 + (uint32_t)j;
-                    const uint32_t q = hst + k;           // window-relative position
                     in[j] = has && k < hlen;
-                    // id and hints: the window's (LDS), past the window from memory
                     pid[j] = 0u;
                     uint32_t hint = 0u;
-                    if (in[j]) {
-                        if (q < 64u) {
-                            pid[j] = s_wid[wb + (int)q];
-                            hint = s_wack[wb + (int)q];
-                        } else {
-                            const size_t qa = w0 + (size_t)q;
-                            pid[j] = ids ? ids[qa] : (uint32_t)qa;
-                            const uint32_t kq = keys(qa) & xm;
-                            hint = ((kq & kAckBit) ? 1u : 0u) | ((kq & kPlainBit) ? 2u : 0u);
-                        }
-                    }
+                    if (in[j]) entry(hst + k, pid[j], hint);
                     acq[j] = (hint & 1u) != 0u;
                     if (in[j] && !acq[j]) {
-                        if constexpr (kSplit) {
-                            m[j] = sw_ld(reinterpret_cast<const u32x4s*>(pay + (size_t)pid[j] * (size_t)(4 * V)) +
-                                         (vl ? l : 0));
-                            if (kPlain && (hint & 2u)) {
-                                // the header fields group_packet reads, made from the slot: words 1-3
-                                // of the row (count, flags 0, index = slot, switch id, frag id, pad 0)
-                                const uint32_t fr = hslot + plB;
-                                h[j] = u32x4s{0u, plC | (__builtin_bswap32(hslot) & 0xFFFFu) << 16,
-                                              (__builtin_bswap32(hslot) >> 16) | ((uint32_t)(uint8_t)st.switch_id << 16) |
-                                                  (fr & 0xFF000000u),
-                                              (__builtin_bswap32(fr) >> 8)};
-                            } else {
-                                h[j] = *reinterpret_cast<const u32x4s*>(pkts + (size_t)pid[j] * 16);
-                            }
-                        } else {
-                            const u32x4s* pk = reinterpret_cast<const u32x4s*>(pkts + (size_t)pid[j] * stride);
-                            if constexpr (INA_PACKED_UNALIGNED)
-                                m[j] = ld_row16(pkts + (size_t)pid[j] * stride + 15 + 16 * (vl ? l : 0));
-                            else
-                                m[j] = sw_ld(pk + (vl ? l + 1 : 1));
-                            h[j] = *pk;
-                        }
+                        m[j] = row_payload<kSplit>(pkts, stride, pay, V, pid[j], l, vl);
+                        if (kPlain && (hint & 2u)) h[j] = plain_header(st, hslot, plB, plC);
+                        else h[j] = row_header<kSplit>(pkts, stride, pid[j]);
                     }
                 }
 #pragma unroll
-                for (int j = 0; j < kP; ++j) {
-                    if (!__ballot(in[j])) continue;
-                    if (!in[j]) continue;
-                    group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, hslot, pid[j], m[j], h[j], acq[j],
-                                              cnt, frag, reg, have_reg, drop_written);
-                }
+                for (int j = 0; j < kP; ++j)
+                    narrow_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, hslot, pid[j], m[j], h[j], in[j],
+                                                     acq[j], cnt, frag, reg, have_reg, drop_written);
             }
-            if (has && l == 0) {
-                st.count[hslot] = (uint8_t)cnt;
-                st.frag[hslot] = frag;
-            }
-            if (have_reg && vl)
-                __builtin_nontemporal_store(reg, reinterpret_cast<u32x4s*>(st.regs + (size_t)hslot * V + 4 * l));
+            narrow_store_state(st, hslot, has, cnt, frag, reg, have_reg, l, vl);
         }
     }
 }
@@ -3178,7 +2855,6 @@ __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st,
         }
         const uint32_t slot = kmin + (uint32_t)s8 + (uint32_t)g;
         const bool has = hlen != 0;
-#if INA_SWITCH_SEG8
         if constexpr (kSplit && !kPs) {
             // every list of these 8 slots 8 packets long: the whole-segment path
             if (maxlen == 8u && !__ballot(has && hlen != 8u) &&
@@ -3188,7 +2864,6 @@ __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st,
                 continue;
             }
         }
-#endif
         uint32_t cnt = 0, frag = 0;
         if (has) {
             cnt = st.count[slot];
@@ -3210,34 +2885,17 @@ __device__ __forceinline__ void lists_slots_narrow(const ina_switch_state_t& st,
                 pid[j] = en & ~kAckBit;
                 acq[j] = (en & kAckBit) != 0u;                     // a PS ack by its sort key
                 if (in[j] && !acq[j]) {
-                    if constexpr (kSplit) {
-                        m[j] = sw_ld(reinterpret_cast<const u32x4s*>(pay + (size_t)pid[j] * (size_t)(4 * V)) + (vl ? l : 0));
-                        h[j] = *reinterpret_cast<const u32x4s*>(pkts + (size_t)pid[j] * 16);
-                    } else {
-                        const u32x4s* pk = reinterpret_cast<const u32x4s*>(pkts + (size_t)pid[j] * stride);
-                        if constexpr (INA_PACKED_UNALIGNED)
-                            m[j] = ld_row16(pkts + (size_t)pid[j] * stride + 15 + 16 * (vl ? l : 0));
-                        else
-                            m[j] = sw_ld(pk + (vl ? l + 1 : 1));
-                        h[j] = *pk;
-                    }
+                    m[j] = row_payload<kSplit>(pkts, stride, pay, V, pid[j], l, vl);
+                    h[j] = row_header<kSplit>(pkts, stride, pid[j]);
                 }
             }
 #pragma unroll
-            for (int j = 0; j < kP; ++j) {
-                if (!__ballot(in[j])) continue;
-                if (!in[j]) continue;
-                group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], acq[j], cnt,
-                                          frag, reg, have_reg, true);
-            }
+            for (int j = 0; j < kP; ++j)
+                narrow_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], in[j],
+                                                 acq[j], cnt, frag, reg, have_reg, true);
         }
         id_nx = (uint32_t)l < e_nx.y ? ids[e_nx.x + (uint32_t)l] : 0u;   // the next step's first ids
-        if (has && l == 0) {
-            st.count[slot] = (uint8_t)cnt;
-            st.frag[slot] = frag;
-        }
-        if (have_reg && vl)
-            __builtin_nontemporal_store(reg, reinterpret_cast<u32x4s*>(st.regs + (size_t)slot * V + 4 * l));
+        narrow_store_state(st, slot, has, cnt, frag, reg, have_reg, l, vl);
     }
 }
 
@@ -3251,7 +2909,6 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
                                                  size_t nwaves, bool drop_written = false,
                                                  const uint2* __restrict__ kdesc = nullptr,
                                                  uint32_t plB = 0u, uint32_t plC = 0u) {
-#if INA_SWITCH_NARROW_SLOTS
     if constexpr (kNarrow) {
         // (kdesc: a batch in slot order whose keys come from its descriptors, see KeySrc)
         const KeySrc ks{keys, kdesc, st.num_slots, st.switch_id, kmask != 0xFFFFFFFFu};
@@ -3259,7 +2916,6 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
                                          nwaves, drop_written, plB, plC);
         return;
     }
-#endif
     const int lane = threadIdx.x & 63;
     const uint32_t NS = st.num_slots;
     // each wave takes windows of 64 sorted positions and processes the segments that
@@ -3290,23 +2946,7 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
         hm &= hm - 1;
         const size_t pos = w0 + (size_t)hl;
         const uint32_t slot = __builtin_amdgcn_readlane(ki, hl);
-        // segment end: first later position whose key differs (vector scan)
-        size_t end;
-        {
-            unsigned long long dm = __ballot(ki != slot) & ~((2ull << hl) - 1ull);
-            if (dm) {
-                end = w0 + (size_t)__builtin_ctzll(dm);
-            } else {
-                size_t j0 = w0 + 64;
-                for (;;) {
-                    const size_t j = j0 + (size_t)lane;
-                    const bool diff = j >= npk || (keys[j] & kmask) != slot;
-                    const unsigned long long m = __ballot(diff);
-                    if (m) { end = j0 + (size_t)__builtin_ctzll(m); break; }
-                    j0 += 64;
-                }
-            }
-        }
+        const size_t end = segment_end([&](size_t j) { return keys[j]; }, kmask, ki, slot, hl, w0, npk);
         const bool ack_led = (am >> hl) & 1ull;
         auto pids = [&](size_t q0, int nb, uint32_t (&pid)[kB]) {
             // packet ids first (no load in the common in-window case; one coalesced load
@@ -3323,12 +2963,8 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
                 for (int b = 0; b < kB; ++b) pid[b] = __builtin_amdgcn_readlane(my, b);
             }
         };
-        if constexpr (kNarrow)
-            run_segment_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
-                                            pos + (ack_led ? 1 : 0), end, pids);
-        else
-            run_segment<kPs, kBlk, kLat, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
-                                           pos + (ack_led ? 1 : 0), end, pids, drop_written);
+        run_segment<kPs, kBlk, kLat, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led,
+                                       pos + (ack_led ? 1 : 0), end, pids, drop_written);
         }
     }
 }
@@ -3339,9 +2975,10 @@ __device__ __forceinline__ void switch_run2_body(const ina_switch_state_t& st, u
 // wave instruction reads them contiguously (lane l: payload chunk l; packed rows: row chunk
 // l + 1, the header chunk 0 for every lane of the group).  The count / frag state machine
 // (ngaa.p4:64-82, fragcheck.p4:14-57) and the Processor add (processor.p4:14-24) run in every
-// group at once on group-uniform VGPRs -- no per-packet scalar walk and no cross-group scan,
-// about a tenth of run_segment_narrow's instructions per packet.  kP runs' loads are in
-// flight together.  Same results as the per-slot walk, packet for packet.
+// group at once on group-uniform VGPRs -- no per-packet scalar walk and no cross-group scan:
+// the whole switch ran 545 -> 274 us worker-major against a wave taking one slot's 8 packets
+// side by side, the form this replaced (profiles/r04/lab/narrow_slots_lab.log).  kP runs' loads
+// are in flight together.
 template <bool kPs, bool kBlk, bool kSplit>
 __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, uint8_t* __restrict__ pkts,
                                                   size_t stride, uint8_t* __restrict__ pay,
@@ -3372,7 +3009,6 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
     for (size_t s8 = s_begin; s8 < s_end; s8 += 8) {
         const uint32_t slot = (uint32_t)(s8 + (size_t)g);
         const bool sv = s8 + (size_t)g < s_end;
-#if INA_SWITCH_SEG8
         if constexpr (kSplit) {
             // 8 runs, each holding every slot of this group once -- or a run of PS acks and then
             // 8 such runs (the packet path's steady state): the whole-segment path (lane l of a
@@ -3394,7 +3030,6 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
                     continue;
             }
         }
-#endif
         uint32_t cnt = 0, frag = 0;
         if (sv) {
             cnt = st.count[slot];
@@ -3417,12 +3052,12 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
                 ackr[j] = __builtin_amdgcn_readlane(rack_u, rr) != 0u;
                 const uint32_t off = slot - rs;
                 in[j] = sv && off < rl;
+                touched |= in[j];
                 pid[j] = rp + off;
                 if constexpr (kSplit) {
                     if (in[j] && !ackr[j]) {              // a run of PS acks needs no read
-                        m[j] = sw_ld(reinterpret_cast<const u32x4s*>(pay + (size_t)pid[j] * (size_t)(4 * V)) +
-                                     (vl ? l : 0));
-                        h[j] = *reinterpret_cast<const u32x4s*>(pkts + (size_t)pid[j] * 16);
+                        m[j] = row_payload<kSplit>(pkts, stride, pay, V, pid[j], l, vl);
+                        h[j] = row_header<kSplit>(pkts, stride, pid[j]);
                     }
                 } else {
                     // the stretch of run r holding group gg's row: rows rp + (slot - rs)
@@ -3450,36 +3085,24 @@ __device__ __forceinline__ void runs_slots_narrow(const ina_switch_state_t& st, 
 #pragma unroll
                 for (int j = 0; j < kP; ++j) {
                     if (in[j] && !ackr[j]) {
-                        if constexpr (INA_PACKED_UNALIGNED) {
-                            // the lane's bytes 15 + 16 l .. 30 + 16 l (group_packet's packed-row
-                            // form): chunk l's last byte, then chunk l + 1's first fifteen
-                            const u32x4s c0 = s_stage[wb][j][g * cpr + (vl ? l : 0)];
-                            const u32x4s c1 = s_stage[wb][j][g * cpr + (vl ? l + 1 : 1)];
-                            m[j] = u32x4s{__builtin_amdgcn_alignbyte(c1.x, c0.w, 3), __builtin_amdgcn_alignbyte(c1.y, c1.x, 3),
-                                          __builtin_amdgcn_alignbyte(c1.z, c1.y, 3), __builtin_amdgcn_alignbyte(c1.w, c1.z, 3)};
-                        } else {
-                            m[j] = s_stage[wb][j][g * cpr + (vl ? l + 1 : 1)];
-                        }
+                        // the lane's bytes 15 + 16 l .. 30 + 16 l (group_packet's packed-row
+                        // form): chunk l's last byte, then chunk l + 1's first fifteen
+                        const u32x4s c0 = s_stage[wb][j][g * cpr + (vl ? l : 0)];
+                        const u32x4s c1 = s_stage[wb][j][g * cpr + (vl ? l + 1 : 1)];
+                        m[j] = u32x4s{__builtin_amdgcn_alignbyte(c1.x, c0.w, 3), __builtin_amdgcn_alignbyte(c1.y, c1.x, 3),
+                                      __builtin_amdgcn_alignbyte(c1.z, c1.y, 3), __builtin_amdgcn_alignbyte(c1.w, c1.z, 3)};
                         h[j] = s_stage[wb][j][g * cpr];
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
             }
+            // (a run that holds no slot of this wave is skipped)
 #pragma unroll
-            for (int j = 0; j < kP; ++j) {
-                if (!__ballot(in[j])) continue;          // no slot of this wave in run r0 + j
-                if (!in[j]) continue;
-                touched = true;
-                group_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], ackr[j],
-                                          cnt, frag, reg, have_reg, drop_written);
-            }
+            for (int j = 0; j < kP; ++j)
+                narrow_packet<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, pid[j], m[j], h[j], in[j],
+                                                 ackr[j], cnt, frag, reg, have_reg, drop_written);
         }
-        if (touched && l == 0) {
-            st.count[slot] = (uint8_t)cnt;
-            st.frag[slot] = frag;
-        }
-        if (have_reg && vl)
-            __builtin_nontemporal_store(reg, reinterpret_cast<u32x4s*>(st.regs + (size_t)slot * V + 4 * l));
+        narrow_store_state(st, slot, touched, cnt, frag, reg, have_reg, l, vl);
     }
 }
 
@@ -3521,13 +3144,11 @@ __device__ __forceinline__ void switch_runs_body(const ina_switch_state_t& st, u
     const size_t per = ((size_t)(hi - lo) + nwaves - 1) / nwaves;
     const size_t s_begin = (size_t)lo + wave * per;
     const size_t s_end = s_begin + per < (size_t)hi ? s_begin + per : (size_t)hi;
-#if INA_SWITCH_NARROW_SLOTS
     if constexpr (kNarrow) {
         runs_slots_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, R, rpos, rlen, rslot, rack, lo, hi,
                                        wave, nwaves, drop_written);
         return;
     }
-#endif
     for (size_t s = s_begin; s < s_end; ++s) {
         const uint32_t slot = (uint32_t)s;
         const uint32_t off = slot - rslot;
@@ -3559,11 +3180,8 @@ __device__ __forceinline__ void switch_runs_body(const ina_switch_state_t& st, u
                 }
             }
         };
-        if constexpr (kNarrow)
-            run_segment_narrow<kPs, kBlk, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids);
-        else
-            run_segment<kPs, kBlk, false, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids,
-                                            drop_written);
+        run_segment<kPs, kBlk, false, kSplit>(st, pkts, stride, pay, actions, ps, slot, ack_led, 0, nseg, pids,
+                                        drop_written);
     }
 }
 
@@ -3571,28 +3189,19 @@ __device__ __forceinline__ void switch_runs_body(const ina_switch_state_t& st, u
 // (b % 8) * G/8 + b / 8 gives each XCD one contiguous run of the logical index
 // (MI355X_MICROARCH.md "Workgroup dispatch, XCD placement"; speed only).  The digit pass's
 // chunks and the near-sorted lists' units use it (their neighbours share lines and windows);
-// the run kernel's windows and slot ranges do NOT since round 6 (INA_SWITCH_XCD = 0): each XCD
+// the run kernel's windows and slot ranges do NOT since round 6 (switch_block_index): each XCD
 // then streams from every part of the batch instead of one eighth of it, and every order ran
 // faster -- NGA-32 split worker-major 207.8 -> 202.5 us, round-robin 232.8 -> 228.0, jitter 64
 // 286.4 -> 281.5, shuffled 384.5 -> 374.8, packed worker-major 259.3 -> 236.2; NGA-256 packed
 // 4-7 us, split worker-major 195.3 -> 180.0; the NGA-256 packet path's switch + PS 219.4 ->
 // 204.1 us (profiles/r06/lab/run_block_map_ab.log).  The near-sorted lists keep the map, in
 // their build and in the run's walk of them: plain, jitter 4096 lost 15-16 us.
-#ifndef INA_SWITCH_XCD
-#define INA_SWITCH_XCD 0
-#endif
 __device__ __forceinline__ size_t xcd_block_index() {
     const uint32_t G = gridDim.x, b = blockIdx.x, x = b & 7u;
     const uint32_t per = G >> 3, rem = G & 7u;
     return (size_t)x * per + (x < rem ? x : rem) + (b >> 3);
 }
-__device__ __forceinline__ size_t switch_block_index() {
-#if INA_SWITCH_XCD
-    return xcd_block_index();
-#else
-    return blockIdx.x;
-#endif
-}
+__device__ __forceinline__ size_t switch_block_index() { return blockIdx.x; }
 
 // occupancy target of the narrow split-row run without the PS step: 8 waves per SIMD takes its
 // SGPRs to the 80 that admit 8 blocks per CU (8 spilled to VGPR lanes; 86 admitted 7)
@@ -3984,13 +3593,13 @@ static SwitchPlan switch_plan(const ina_switch_state_t& st, size_t npk, size_t s
         // at every size -- tools/lab/switch_lab.py, profiles/r01/lab/switch_lab_win.log:
         // 1,024 packets 52.9 -> 27.7 us (64 -> 8 positions), 819,200 packets 277 -> 266 us
         // (64 -> 16 positions, one pass of the grid)
-        // V <= 32 (NGA-32, the P4 program's format): 8 packets of a segment side by side per
-        // wave (run_segment_narrow); wider packets: a packet per wave instruction
+        // V <= 32 (NGA-32, the P4 program's format): 8 slots side by side per wave, one per
+        // lane group (the *_slots_narrow drivers); wider packets: a packet per wave instruction
         p.narrow = st.V <= kNarrowMaxV;
         p.win = npk <= 65536 ? (uint32_t)INA_SWITCH_WIN_SMALL : (uint32_t)INA_SWITCH_WIN_LARGE;
-        // a narrow wave moves a whole segment per batch: a window of 64 sorted positions
-        // (about 8 segments) keeps the grid at npk / 256 workgroups
-        if (p.narrow && (INA_SWITCH_NARROW_SLOTS || npk > 65536)) p.win = INA_SWITCH_WIN_NARROW;   // 8 lane groups: ~8 segments
+        // a narrow wave's 8 lane groups take 8 segments at a time: a window of 64 sorted
+        // positions (about 8 segments) keeps the grid at npk / 256 workgroups
+        if (p.narrow) p.win = INA_SWITCH_WIN_NARROW;
         if (const int wv = t.win) p.win = (uint32_t)wv;
         const size_t per_block = (size_t)p.win * (kSwBlock / 64);
         p.gr = (unsigned)std::min<size_t>((npk + per_block - 1) / per_block, INA_SWITCH_GRID);

@@ -691,6 +691,91 @@ def test_whole_segments_vs_oracle(case, order, write_dropped):
     _check_split_vs_oracle(o, V, batches, want, write_dropped)
 
 
+PAST_SEQ0, PAST_NSEG, PAST_FAR = 1, 180, 60000
+
+
+def past_window_batches(V, seed):
+    """Two shuffled batches of 1,513 packets from 8 workers: slot 1 receives 3 packets, slots 2 ..
+    181 one packet of each worker, slot 60,000 receives 70 (one frag id, degree 8: it completes 8
+    times).  Sorted, every 8-packet segment starts at 3 mod 8, so one per 64-position window runs 3
+    positions past the window's end, and the last slot's walk goes 67 positions past its window.
+    The far slot also spreads the keys over more slots than the near-sorted lists' scan budget
+    covers (local_decide: ceil(60,000 / 1,024) passes over the batch against 3), so the sort takes
+    the batch."""
+    W = 8
+    rng = np.random.default_rng(seed)
+    stride = ops().nga_stride(V)
+    specs = ([(PAST_SEQ0, 1, w) for w in range(3)] + [(PAST_SEQ0 + 1, PAST_NSEG, w) for w in range(W)] +
+             [(PAST_FAR, 1, i % W) for i in range(70)])
+    batches = []
+    for _ in range(2):
+        b = runs_batch(rng, V, specs, W, stride, collide=0.0, degree_mix=0.0)
+        batches.append(b[rng.permutation(len(b))].copy())
+    return batches
+
+
+@pytest.mark.parametrize("ps", [False, True])
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("V", [32, 8])
+def test_segments_past_window_vs_oracle(V, split, ps):
+    """The sorted windows' walk of a narrow segment past its window's end (window_slots_narrow:
+    ids and hints of window-relative positions >= 64 come from memory, not from the window's LDS
+    copy), on split and packed rows, with and without the fused PS step: actions, rewritten rows
+    (write_dropped: every row), count / frag / registers after each batch and, with the PS step,
+    `out` (sentinel where no slot of the bucket completed) against the P4 restatement.  The PS's
+    bucket is slots 1 .. 181 less 3 values (the last 8-packet slot takes the value-by-value tail);
+    the 70-packet slot lies past it, so its completions are forwarded, and no bucket slot
+    completes twice in a batch."""
+    o = ops()
+    batches = past_window_batches(V, 4000 + V)
+    stride = batches[0].shape[1]
+    assert 1024 <= len(batches[0]) <= 2048
+    sw = o.Switch(V, num_slots=POOL, switch_id=1, device=DEV, write_dropped=True)
+    ref = orc.Switch(V, num_slots=POOL, switch_id=1)
+    n, ws, k, sent = V * (PAST_NSEG + 1) - 3, 1.0 / 9, 16, np.float32(-777.5)
+    local = (np.random.default_rng(V).standard_normal(n) * 1e-2).astype(np.float32)
+    for i, stream in enumerate(batches):
+        want_pk, want_act = ref.run(stream, stride=stride)
+        d = dev(stream)
+        desc = o.nga_descriptors(d)
+        buf = torch.full((n + 5,), float(sent), device=DEV)
+        if split:
+            hdr = torch.zeros((d.shape[0], 16), dtype=torch.uint8, device=DEV)
+            hdr[:, :15] = d[:, :15]
+            pay = d[:, 15:15 + 4 * V].contiguous()
+            if ps:
+                act, _ = sw.process_apply_split(hdr, pay, PAST_SEQ0, dev(local), k, ws, out=buf[:n], desc=desc)
+            else:
+                act = sw.process_split(hdr, pay, desc=desc)
+            d[:, :15] = hdr[:, :15]
+            d[:, 15:15 + 4 * V] = pay
+        elif ps:
+            act, _ = sw.process_apply(d, PAST_SEQ0, dev(local), k, ws, out=buf[:n], desc=desc)
+        else:
+            act = sw.process(d, desc=desc)
+        assert sw.batch_path(len(stream)) == "sorted", (i, sw.batch_path(len(stream)))
+        assert np.array_equal(host(act), want_act), i
+        assert np.array_equal(host(d), want_pk), i
+        cnt, frag, regs = ref.registers()
+        assert np.array_equal(host(sw.count), cnt), i
+        assert np.array_equal(host(sw.frag).view(np.uint32), frag), i
+        assert np.array_equal(host(sw.regs).view(np.uint32), regs), i
+        done = want_act == orc.ACT_FWD_AGG
+        assert int(done.sum()) == PAST_NSEG + 8 + (i == 1)          # (slot 60,000: 70 + 70 = 17 x 8 + 4)
+        want_out = np.full(n + 5, sent, np.float32)
+        if ps:
+            f, vals = orc.unpack_nga(want_pk[done], V, stride)
+            slot = (f["frag_id"].astype(np.int64) - PAST_SEQ0) & 0xFFFFFFFF
+            take = slot < PAST_NSEG + 1
+            assert int(take.sum()) == PAST_NSEG and len(np.unique(slot[take])) == PAST_NSEG
+            idx = (slot[take][:, None] * V + np.arange(V)[None, :]).ravel()
+            sums = vals.reshape(-1, V)[take].ravel()
+            keep = idx < n
+            y = orc.dequantize_i32(sums[keep].astype(np.int32), k)
+            want_out[idx[keep]] = local[idx[keep]] + y * np.float32(ws)
+        assert np.array_equal(host(buf).view(np.uint32), want_out.view(np.uint32)), i
+
+
 @pytest.mark.parametrize("write_dropped", [False, True])
 @pytest.mark.parametrize("case", ["base", "base_b", "row0_foreign", "index_high", "flags", "refrag",
                                   "wrap", "degree4"])

@@ -250,7 +250,8 @@ def test_wide_rows(V, W, per, order, seq0, paths, split):
 @pytest.mark.parametrize("order,seq0,paths", ORDERS)
 @pytest.mark.parametrize("V,W,per,pool", [(32, 8, 3000, 1 << 13), (8, 8, 1000, 16384)])
 def test_narrow_rows(V, W, per, pool, order, seq0, paths, split):
-    """run_segment_narrow, group_packet and the whole segments of seg8_fast."""
+    """The narrow drivers (window_slots_narrow, runs_slots_narrow), their group_packet and the whole
+    segments of seg8_fast."""
     check_case(Case(V, W, per, order, pool, seq0, seed=V + W + len(order)), split, paths)
 
 

@@ -355,6 +355,45 @@ DEFAULTS = {"max_blocks": 16384, "reduce_blocks": 0, "stream_blocks": 16384, "co
             "combine_ina_blocks": 8192, "ew_blocks": 1 << 24}
 
 
+def run_blk_shard(dev):
+    """The block-scaled int16 wire (include/ina_shard_blk.h) at the ResNet-50 size, V = 256 and 32, cold
+    caches, median of 20, the whole set twice in this process (run 1 / run 2), as run_blk:
+    quantize_i16_wire_blk and i16_wire_finish_blk (y + out16 + flags), each beside its global-k sibling
+    timed twice.  Bar: sibling time x (bytes + n/V) / bytes + the spread of the sibling's two timings;
+    reported, not gated."""
+    from ina_amd import ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(18)
+    n, k = 25_557_032, 9
+    x = torch.randn(n, device=dev, generator=gen) * 1e-2
+    wire = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+
+    def given(run, name, V, nb_sib, f_blk, f_sib):
+        nblk = (n + V - 1) // V
+        ta, tb, tc = _time(f_sib), _time(f_blk), _time(f_sib)
+        lo, hi = min(ta, tc), max(ta, tc)
+        bar = hi * (nb_sib + nblk) / nb_sib + (hi - lo)
+        rows.append(_row(f"{name} V={V} [blk given, run {run}]", tb, nb_sib + nblk,
+                         sibling_us=[round(ta * 1e6, 2), round(tc * 1e6, 2)], sibling_spread_us=round((hi - lo) * 1e6, 2),
+                         bar_us=round(bar * 1e6, 2), bar_met=bool(tb <= bar)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = (n + V - 1) // V
+            f = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kb = ops.block_scales([x], V, bits=16, degree=64)          # the 64-rank wire's scales
+            given(run, "quantize_i16_wire", V, 8 * n, lambda: ops.quantize_i16_wire_blk(x, kb, V, out=wire),
+                  lambda: ops.quantize_i16_wire(x, k, out=wire))
+            ops.quantize_i16_wire(x, k, out=wire)                      # the same summed wire for both decodes
+            given(run, "i16_wire_finish (y + out16 + flags)", V, 10 * n + nblk,
+                  lambda: ops.i16_wire_finish_blk(wire, kb, V, out16=o16, y=y, overflow=f),
+                  lambda: ops.i16_wire_finish(wire, k, V, out16=o16, y=y, overflow=f))
+    return rows
+
+
 def _sweep(ops, rows, sweeps, name, knob, values, fn, nbytes):
     """Time fn at each grid cap of one knob; keep all points, restore the default.  The grid-cap
     knobs exist in lab builds only (make EXTRA=-DINA_LAB_KEYS=1): the product library refuses
@@ -729,4 +768,5 @@ def run_extra(dev):
     rows += run_blk(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)
+    rows += run_blk_shard(dev)
     return {"rows": rows, "sweep": sweep, "grid_sweeps": gsweep}

@@ -19,7 +19,8 @@
 //
 // Both kernels stream 16 B per lane (global_load_dwordx4, non-temporal: every byte is
 // touched once) over a grid-stride loop; HBM-bound at 8 B/value (quantise: 4 in, 4 out)
-// and 4 + 2 + 4 B/value (finish: wire in, int16 + fp32 out).
+// and 4 + 2 + 4 B/value (finish: wire in, int16 + fp32 out).  Each has a sibling that takes one
+// scale per block of V values (include/ina_shard_blk.h) and reads 1/V byte more per value.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -142,7 +143,128 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_scalar(const int32_t* 
     }
 }
 
+// ---------------------------------------------------------------------------
+// per-block scales (include/ina_shard_blk.h): the two kernels above with 2^kblk[e / V] for element
+// e.  Vector path: V a power of two in [8, 256], so a lane's 16-byte chunk i lies inside block
+// i >> shift (shift = log2 V - 2) and the scale is one byte load per chunk, one address per V/4
+// adjacent lanes.  The loops are the siblings': whole chunks first, the ragged tail value by value.
+// A scale is read only for an element below n, so nothing outside kblk[0 .. ceil(n / V)) is touched.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire_blk(const float* __restrict__ x,
+                                                                const int8_t* __restrict__ kblk,
+                                                                int32_t* __restrict__ wire, size_t n,
+                                                                int shift) {
+    const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * kBlk;
+    const size_t n4 = n / 4;
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+    u32x4* w4 = reinterpret_cast<u32x4*>(wire);
+    for (size_t i = tid; i < n4; i += stride) {
+        const float s = pow2f(rd_k(kblk, i >> shift));
+        const f32x4 v = __builtin_nontemporal_load(x4 + i);
+        u32x4 r;
+        r.x = (uint32_t)q16w(v.x, s); r.y = (uint32_t)q16w(v.y, s);
+        r.z = (uint32_t)q16w(v.z, s); r.w = (uint32_t)q16w(v.w, s);
+        stream_store(r, w4 + i);
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) wire[i] = q16w(x[i], pow2f(rd_k(kblk, i >> (shift + 2))));
+}
+
+// any alignment / any V
+__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire_blk_scalar(const float* __restrict__ x,
+                                                                       const int8_t* __restrict__ kblk,
+                                                                       int32_t* __restrict__ wire, size_t n,
+                                                                       int V) {
+    const size_t stride = (size_t)gridDim.x * kBlk;
+    for (size_t i = (size_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += stride)
+        wire[i] = q16w(x[i], pow2f(rd_k(kblk, i / (size_t)V)));
+}
+
+// one whole chunk of the finish: 4 wire words at element e -> out16 / y
+__device__ __forceinline__ void finish4(u32x4 w, float inv, size_t e, int16_t* __restrict__ out16,
+                                        float* __restrict__ y, bool& sat) {
+    const int32_t a = finish1(w.x, sat), b = finish1(w.y, sat);
+    const int32_t c = finish1(w.z, sat), d = finish1(w.w, sat);
+    if (out16) {
+        u32x2 o;
+        o.x = (uint32_t)(uint16_t)a | ((uint32_t)b << 16);
+        o.y = (uint32_t)(uint16_t)c | ((uint32_t)d << 16);
+        stream_store(o, reinterpret_cast<u32x2*>(out16 + e));
+    }
+    if (y) {
+        f32x4 f;
+        f.x = (float)a * inv; f.y = (float)b * inv; f.z = (float)c * inv; f.w = (float)d * inv;
+        stream_store(f, reinterpret_cast<f32x4*>(y + e));
+    }
+}
+
+// k_i16_wire_finish_vec's layout and one-writer ballot flags (V/4 = 1 << shift lanes per slot).  A
+// wave whose 64 chunks are all whole -- every wave but the bucket's last -- takes one wave-uniform
+// branch and no per-lane test against n; the last wave tests per lane and finishes the values past
+// the last whole chunk one by one.
+__global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_vec(const int32_t* __restrict__ wsum, size_t n,
+                                                                  const int8_t* __restrict__ kblk, int shift,
+                                                                  int16_t* __restrict__ out16,
+                                                                  float* __restrict__ y,
+                                                                  uint8_t* __restrict__ ovf) {
+    const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * kBlk;
+    const int lane = threadIdx.x & 63, lps = 1 << shift;
+    const size_t n4 = n / 4, nch = (n + 3) / 4;
+    const u32x4* w4 = reinterpret_cast<const u32x4*>(wsum);
+    for (size_t base = tid & ~(size_t)63; base < nch; base += stride) {
+        const size_t i = base + lane;
+        const size_t e = 4 * i;
+        bool sat = false;
+        if (base + 64 <= n4) {                                   // wave-uniform
+            const float inv = pow2f(-rd_k(kblk, i >> shift));
+            finish4(__builtin_nontemporal_load(w4 + i), inv, e, out16, y, sat);
+        } else if (e < n) {
+            const float inv = pow2f(-rd_k(kblk, i >> shift));
+            if (i < n4) {
+                finish4(__builtin_nontemporal_load(w4 + i), inv, e, out16, y, sat);
+            } else {
+                for (size_t j = e; j < n; ++j) {
+                    const int32_t r = finish1((uint32_t)wsum[j], sat);
+                    if (out16) out16[j] = (int16_t)r;
+                    if (y) y[j] = (float)r * inv;
+                }
+            }
+        }
+        const unsigned long long m = __ballot(sat);
+        if (ovf && e < n && (lane & (lps - 1)) == 0) {
+            const int g0 = lane & ~(lps - 1);
+            const unsigned long long gm = (lps == 64) ? ~0ull : (((1ull << lps) - 1ull) << g0);
+            ovf[i >> shift] = (m & gm) ? 1 : 0;
+        }
+    }
+}
+
+// any alignment / any V: flags pre-zeroed by the caller, saturating elements store 1
+__global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_scalar(const int32_t* __restrict__ wsum, size_t n,
+                                                                     const int8_t* __restrict__ kblk, int V,
+                                                                     int16_t* __restrict__ out16,
+                                                                     float* __restrict__ y,
+                                                                     uint8_t* __restrict__ ovf) {
+    const size_t stride = (size_t)gridDim.x * kBlk;
+    for (size_t i = (size_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += stride) {
+        const size_t s = i / (size_t)V;
+        bool sat = false;
+        const int32_t r = finish1((uint32_t)wsum[i], sat);
+        if (out16) out16[i] = (int16_t)r;
+        if (y) y[i] = (float)r * pow2f(-rd_k(kblk, s));
+        if (sat && ovf) ovf[s] = 1;
+    }
+}
+
 inline bool al(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }
+
+// the vector path's block sizes: V a power of two in [8, 256]; shift = log2(V) - 2
+inline bool vec_v(int V, int& shift) {
+    if (V < 8 || V > 256 || log2_exact((uint32_t)V) < 0) return false;
+    shift = log2_exact((uint32_t)V) - 2;
+    return true;
+}
 
 }  // namespace
 }  // namespace ina
@@ -183,6 +305,44 @@ int ina_i16_wire_finish(const int32_t* wire_sum, size_t n, int k, int V, int16_t
                            inv, V, out16, y, overflow_per_slot);
     }
     return check_launch("i16_wire_finish");
+}
+
+int ina_quantize_blk_f32_i16_wire(const float* x, const int8_t* kblk, int V, int32_t* wire, size_t n,
+                                  ina_stream_t stream) {
+    if (V < 1) return set_error(INA_EINVAL, "V must be >= 1%s", "");
+    if (n == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
+    int shift;
+    if (vec_v(V, shift) && al(x, 16) && al(wire, 16)) {
+        hipLaunchKernelGGL(k_quantize_i16_wire_blk, dim3(grid_of(n / 4 + 1, ew_grid_cap())), dim3(kBlk), 0,
+                           hs(stream), x, kblk, wire, n, shift);
+    } else {
+        hipLaunchKernelGGL(k_quantize_i16_wire_blk_scalar, dim3(grid_of(n, ew_grid_cap())), dim3(kBlk), 0,
+                           hs(stream), x, kblk, wire, n, V);
+    }
+    return check_launch("quantize_blk_i16_wire");
+}
+
+int ina_i16_wire_finish_blk(const int32_t* wire_sum, size_t n, const int8_t* kblk, int V, int16_t* out16,
+                            float* y, uint8_t* overflow_per_slot, ina_stream_t stream) {
+    if (V < 1) return set_error(INA_EINVAL, "V must be >= 1%s", "");
+    if (n == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (!wire_sum) return set_error(INA_EINVAL, "null pointer%s", "");
+    hipStream_t s = hs(stream);
+    int shift;
+    if (vec_v(V, shift) && al(wire_sum, 16) && (!out16 || al(out16, 8)) && (!y || al(y, 16))) {
+        hipLaunchKernelGGL(k_i16_wire_finish_blk_vec, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, s,
+                           wire_sum, n, kblk, shift, out16, y, overflow_per_slot);
+    } else {
+        if (overflow_per_slot &&
+            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        hipLaunchKernelGGL(k_i16_wire_finish_blk_scalar, dim3(grid_of(n, ew_grid_cap())), dim3(kBlk), 0, s,
+                           wire_sum, n, kblk, V, out16, y, overflow_per_slot);
+    }
+    return check_launch("i16_wire_finish_blk");
 }
 
 }  // extern "C"

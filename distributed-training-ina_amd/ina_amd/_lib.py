@@ -150,6 +150,11 @@ SIGNATURES_PKT_BLK = {
 SIGNATURES_SWITCH_BLK = {
     "ina_switch_blk": [C.POINTER(SwitchState), C.POINTER(SwitchBatch), C.POINTER(SwitchPs), _vp, _i, _vp],
 }
+# the block-scaled int16 wire of a sharded bucket (include/ina_shard_blk.h)
+SIGNATURES_SHARD_BLK = {
+    "ina_quantize_blk_f32_i16_wire": [_vp, _vp, _i, _vp, _sz, _vp],
+    "ina_i16_wire_finish_blk": [_vp, _sz, _vp, _i, _vp, _vp, _vp, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -165,7 +170,7 @@ def open_library(path: str) -> C.CDLL:
         raise InaError(f"libina.so not built at {path}; run `make -C {CSRC}` or __graft_entry__.build()")
     lib = C.CDLL(path)
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
-                       **SIGNATURES_SWITCH_BLK}.items():
+                       **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -35,6 +35,16 @@ is device-agnostic and covered on CPU with gloo; with a gloo group and device
 tensors the collectives stage through host memory (a test harness for several
 ranks on one GPU, never the RCCL path).  Quantise and decode are the device
 kernels (no CPU path).
+
+k="block" (both classes): one scale per block of V values (include/ina_blk.h) in place of the one
+global k.  Layout A: every rank takes ops.block_scales of its bucket for `world` summands, the
+ranks agree on the element-wise MIN (agree_block_scales: ceil(n / V) bytes), quantise with the
+agreed scales (on the i16 wire: ops.quantize_i16_wire_blk), run the same integer collective, and
+the owner decodes its shard with its slice of the scales (ops.i16_wire_finish_blk /
+ops.dequantize_blk).  Layout B: a rank holds all the summands of its range, so its fused AUTO
+reduce computes the scales and the all-gather carries them, one byte per block.  Either way the
+result equals one GPU's AUTO ops.quantize_reduce_blk / quantize_reduce_i16_blk over the same
+buckets, scales included; `kblk` holds the scales of the last call.
 """
 from __future__ import annotations
 
@@ -131,6 +141,37 @@ def all_reduce_sum(x: torch.Tensor, group=None):
     return x
 
 
+def agree_block_scales(kb: torch.Tensor, group=None) -> torch.Tensor:
+    """int8 [nblk] in place -> the element-wise MIN over ranks (nothing to do on one rank; host-staged
+    with gloo and a device tensor, like the other collectives here).
+
+    ina_scale_for is non-increasing in amax, so the MIN over ranks of each rank's
+    ops.block_scales(its buckets, V, bits, degree=world) is the scale of the block's max over ALL
+    ranks' buckets: block_scales of all the buckets taken together.  Quantising with the agreed
+    scales and summing therefore equals one GPU's AUTO quantize_reduce_blk / quantize_reduce_i16_blk
+    over the same buckets with degree = world, scales included."""
+    if kb.dtype != torch.int8:
+        raise TypeError(f"block scales are torch.int8, got {kb.dtype}")
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return kb
+    if kb.is_cuda and _host_staged(group):
+        h = kb.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.MIN, group=group)
+        kb.copy_(h)
+        return kb
+    dist.all_reduce(kb, op=dist.ReduceOp.MIN, group=group)
+    return kb
+
+
+def _block_k(k) -> bool:
+    """True for k="block"; an integer k is the global scale; any other string is refused."""
+    if isinstance(k, str):
+        if k != "block":
+            raise ValueError(f"k must be an integer or 'block', got {k!r}")
+        return True
+    return False
+
+
 def all_gather_shards(shard: torch.Tensor, plan: ShardPlan, group=None, out=None,
                       async_op: bool = False):
     """[count] per rank -> [world * count] (count = plan.shard values, or its slot flags).
@@ -177,6 +218,9 @@ class ShardedAggregator:
     reduce-scattered and all-gathered on its own (async RCCL work), so chunk c+1's
     quantise runs under chunk c's reduce-scatter and the decodes under the later
     collectives; same bits (integer sums are order-free, the decode is elementwise).
+    k="block": per-block scales (V values a block; the module docstring gives the sequence);
+    `kblk` then holds the agreed scales of the last call and `scale_bytes` the bytes of their
+    exchange.  Not with chunks > 1.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
@@ -187,14 +231,19 @@ class ShardedAggregator:
             raise ValueError("collective must be 'rs_ag', 'a2a' or 'allreduce'")
         if chunks < 1 or (chunks > 1 and collective != "rs_ag"):
             raise ValueError("chunks must be >= 1, and > 1 only with collective='rs_ag'")
+        self.blk = _block_k(k)
+        if self.blk and chunks > 1:
+            raise ValueError("k='block' takes chunks=1: the pipelined step would need the whole bucket's "
+                             "MIN of the block scales before it quantises its first chunk")
         self.collective = collective
         if V <= 0:
             raise ValueError("V must be > 0")
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         if wire == "i16" and self.world > _lib.I16_WIRE_MAX_RANKS:
             raise ValueError(f"the int16 wire sums at most {_lib.I16_WIRE_MAX_RANKS} ranks")
-        if wire == "i16":
-            align = align * V // math.gcd(align, V)        # shards hold whole slots
+        if wire == "i16" or self.blk:
+            align = align * V // math.gcd(align, V)        # shards hold whole slots / blocks
         self.plan = ShardPlan(n, self.world, align)
         self.k, self.group, self.wire, self.V = k, group, wire, V
         dev = device or torch.device("cuda", torch.cuda.current_device())
@@ -229,6 +278,10 @@ class ShardedAggregator:
                     self._shard_buf("s16", torch.int16)
                 self._s16buf = torch.empty(tot, dtype=torch.int16, device=dev)
                 self.s16_full = self._s16buf[: self.plan.padded]
+        if self.blk:
+            # one scale per block of the PADDED bucket, the pad blocks at 127: every rank's slice is
+            # whole even where its shard lies past n
+            self._kbuf = torch.full((self.plan.padded // V,), 127, dtype=torch.int8, device=dev)
         # the all-to-all's receive buffer (world slices of one shard each)
         self._recv = (torch.empty(self.plan.padded, dtype=torch.int32, device=dev)
                       if collective == "a2a" and self.world > 1 else None)
@@ -268,6 +321,23 @@ class ShardedAggregator:
         return self._obuf[: -(-self.plan.n // self.V)]
 
     @property
+    def kblk(self) -> torch.Tensor:
+        """k="block": the agreed scales of the last call (ceil(n / V) int8)."""
+        if not self.blk:
+            raise AttributeError("block scales exist only with k='block'")
+        return self._kbuf[: -(-self.plan.n // self.V)]
+
+    def _kshard(self) -> torch.Tensor:
+        """The scales of this rank's shard."""
+        b = self.plan.shard // self.V
+        return self._kbuf[self.rank * b:(self.rank + 1) * b]
+
+    @property
+    def scale_bytes(self) -> int:
+        """Bytes of the block-scale exchange (agree_block_scales) per step: one per block."""
+        return -(-self.plan.n // self.V) if self.blk and self.world > 1 else 0
+
+    @property
     def gather_bytes(self) -> int:
         """Bytes one all-gather step brings to each rank over xGMI (values + flags);
         with collective="allreduce" the all-reduce's gather half (int32 wire words)."""
@@ -301,6 +371,11 @@ class ShardedAggregator:
         bucket on every rank)."""
         if self.world == 1 or self.collective == "allreduce":
             self._decode(self.q, self.full, self.ovf_full if self.wire == "i16" else None)
+        elif self.blk and self.wire == "i32":
+            ops.dequantize_blk(self.sum_shard, self._kshard(), self.V, out=self.f_shard)
+        elif self.blk:
+            ops.i16_wire_finish_blk(self.sum_shard, self._kshard(), self.V, out16=self.s16_shard,
+                                    overflow=self.ovf_shard, want_y=False)
         elif self.wire == "i32":
             ops.dequantize(self.sum_shard, self.k, out=self.f_shard)
         else:
@@ -319,20 +394,37 @@ class ShardedAggregator:
     def phase_expand(self):
         """i16 wire at world > 1: dequantise the gathered int16 sums on every rank."""
         if self.world > 1 and self.wire == "i16" and self.collective != "allreduce":
-            ops.dequantize(self.s16_full, self.k, out=self.full)
+            if self.blk:
+                ops.dequantize_blk(self.s16_full, self._kbuf, self.V, out=self.full)
+            else:
+                ops.dequantize(self.s16_full, self.k, out=self.full)
 
     def _quantize(self, grad: torch.Tensor):
         n = self.plan.n
         if grad.numel() != n:
             raise ValueError("bucket size changed")
         x = grad.reshape(-1)
-        if self.wire == "i32":
+        if self.blk:
+            # this rank's scales for `world` summands, the MIN over ranks, then the wire
+            kb = self.kblk
+            ops.block_scales([x], self.V, bits=32 if self.wire == "i32" else 16, degree=self.world, out=kb)
+            agree_block_scales(kb, self.group)
+            if self.wire == "i32":
+                ops.quantize_blk(x, kb, self.V, out=self.q[:n])
+            else:
+                ops.quantize_i16_wire_blk(x, kb, self.V, out=self.q[:n])
+        elif self.wire == "i32":
             ops.quantize(x, self.k, out=self.q[:n])
         else:
             ops.quantize_i16_wire(x, self.k, out=self.q[:n])
 
     def _decode(self, src: torch.Tensor, y: torch.Tensor, ovf=None):
-        if self.wire == "i32":
+        """The whole (padded) bucket: one rank, or after an all-reduce."""
+        if self.blk and self.wire == "i32":
+            ops.dequantize_blk(src, self._kbuf, self.V, out=y)
+        elif self.blk:
+            ops.i16_wire_finish_blk(src, self._kbuf, self.V, y=y, overflow=ovf, want_out16=False)
+        elif self.wire == "i32":
             ops.dequantize(src, self.k, out=y)
         else:
             ops.i16_wire_finish(src, self.k, self.V, y=y, overflow=ovf, want_out16=False)
@@ -389,7 +481,7 @@ class ShardedAggregator:
     def aggregate_int(self, grad: torch.Tensor) -> torch.Tensor:
         """fp32 [n] -> this rank's integer shard of the aggregate (no gather): the
         int32 wrapped sum, or on the i16 wire the int16 saturated sum (its slot flags
-        in `ovf_shard`)."""
+        in `ovf_shard`).  k="block": the integers are scaled per block; read `kblk` next to them."""
         self._quantize(grad)
         if self.collective == "a2a":
             s = reduce_scatter_a2a(self.q, self.plan, self.group, out=self.sum_shard, recv=self._recv)
@@ -397,7 +489,10 @@ class ShardedAggregator:
             s = reduce_scatter_sum(self.q, self.plan, self.group, out=self.sum_shard)
         if self.wire == "i32":
             return s
-        out16, _, _ = ops.i16_wire_finish(s, self.k, self.V, overflow=self.ovf_shard, want_y=False)
+        if self.blk:
+            out16, _, _ = ops.i16_wire_finish_blk(s, self._kshard(), self.V, overflow=self.ovf_shard, want_y=False)
+        else:
+            out16, _, _ = ops.i16_wire_finish(s, self.k, self.V, overflow=self.ovf_shard, want_y=False)
         return out16
 
 
@@ -409,7 +504,9 @@ class RangeAggregator:
     per-slot overflow flags (headers.p4:30) -- dequantises, and all-gathers the fp32
     aggregate (and the flags) to every rank.  Each rank's shard is bit-identical to the
     single-GPU ina_quantize_reduce_f32_i32 / _i16_sat over the same W buckets, since the
-    ranges hold whole slots.
+    ranges hold whole slots.  k="block": the fused reduces in AUTO mode (ops.quantize_reduce_blk /
+    quantize_reduce_i16_blk, degree = W) with one scale per block of V values; the all-gather also
+    carries the shard's scales and `kblk` holds the bucket's after a call.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
@@ -418,10 +515,11 @@ class RangeAggregator:
             raise ValueError("wire must be 'i32' or 'i16'")
         if V <= 0:
             raise ValueError("V must be > 0")
+        self.blk = _block_k(k)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        if wire == "i16":
-            align = align * V // math.gcd(align, V)        # ranges hold whole slots
+        if wire == "i16" or self.blk:
+            align = align * V // math.gcd(align, V)        # ranges hold whole slots / blocks
         self.plan = ShardPlan(n, self.world, align)
         self.k, self.group, self.wire, self.V = k, group, wire, V
         dev = device or torch.device("cuda", torch.cuda.current_device())
@@ -439,6 +537,10 @@ class RangeAggregator:
                 self.slots_per_shard * self.world, dtype=torch.uint8, device=dev)
             if self.world > 1:        # the gather moves the int16 sums, decoded afterwards
                 self.s16_full = torch.empty(self.plan.padded, dtype=torch.int16, device=dev)
+        if self.blk:                  # one scale per block of the padded range, the pad blocks at 127
+            self.k_shard = torch.full((self.plan.shard // V,), 127, dtype=torch.int8, device=dev)
+            self.k_full = self.k_shard if self.world == 1 else torch.empty(self.plan.padded // V,
+                                                                          dtype=torch.int8, device=dev)
 
     @property
     def range(self):
@@ -452,6 +554,19 @@ class RangeAggregator:
             raise AttributeError("overflow flags exist only on the i16 wire")
         return self.ovf_full[: -(-self.plan.n // self.V)]
 
+    @property
+    def kblk(self) -> torch.Tensor:
+        """k="block": the scales of the last call's aggregate (ceil(n / V) int8)."""
+        if not self.blk:
+            raise AttributeError("block scales exist only with k='block'")
+        return self.k_full[: -(-self.plan.n // self.V)]
+
+    @property
+    def scale_bytes(self) -> int:
+        """No exchange before the reduce: a rank holds every summand of its range (the scales ride
+        in the all-gather, counted in gather_bytes)."""
+        return 0
+
     def _reduce(self, slices) -> int:
         m = self.hi - self.lo
         if isinstance(slices, torch.Tensor):
@@ -461,7 +576,13 @@ class RangeAggregator:
             raise ValueError(f"every worker slice must hold this rank's {m} values")
         if m == 0:                    # more ranks than ranges: nothing here, zeros gathered
             return 0
-        if self.wire == "i32":
+        nb = -(-m // self.V)
+        if self.blk and self.wire == "i32":
+            ops.quantize_reduce_blk(slices, self.V, out=self.sum_shard[:m], kblk_out=self.k_shard[:nb])
+        elif self.blk:
+            ops.quantize_reduce_i16_blk(slices, self.V, out=self.sum_shard[:m], overflow=self.ovf_shard[:nb],
+                                        kblk_out=self.k_shard[:nb])
+        elif self.wire == "i32":
             ops.quantize_reduce(slices, self.k, out=self.sum_shard[:m])
         else:
             ops.quantize_reduce_i16(slices, self.k, self.V, out=self.sum_shard[:m],
@@ -476,6 +597,8 @@ class RangeAggregator:
         per = self.plan.shard * (2 if self.wire == "i16" else 4)
         if self.wire == "i16":
             per += self.slots_per_shard
+        if self.blk:
+            per += self.plan.shard // self.V
         return (self.world - 1) * per
 
     # The step's phases, in order (bench.py times each one between HIP events).
@@ -483,7 +606,10 @@ class RangeAggregator:
         """Local fused quantise + reduce; on the i32 wire (or one rank) also the decode."""
         m = self._reduce(slices)
         if m and (self.wire == "i32" or self.world == 1):
-            ops.dequantize(self.sum_shard[:m], self.k, out=self.f_shard[:m])
+            if self.blk:
+                ops.dequantize_blk(self.sum_shard[:m], self.k_shard, self.V, out=self.f_shard[:m])
+            else:
+                ops.dequantize(self.sum_shard[:m], self.k, out=self.f_shard[:m])
         return m
 
     def phase_all_gather(self):
@@ -494,11 +620,16 @@ class RangeAggregator:
         else:
             all_gather_shards(self.sum_shard, self.plan, self.group, out=self.s16_full)
             all_gather_shards(self.ovf_shard, self.plan, self.group, out=self.ovf_full)
+        if self.blk:
+            all_gather_shards(self.k_shard, self.plan, self.group, out=self.k_full)
 
     def phase_expand(self):
         """i16 wire at world > 1: dequantise the gathered int16 sums on every rank."""
         if self.world > 1 and self.wire == "i16":
-            ops.dequantize(self.s16_full, self.k, out=self.full)
+            if self.blk:
+                ops.dequantize_blk(self.s16_full, self.k_full, self.V, out=self.full)
+            else:
+                ops.dequantize(self.s16_full, self.k, out=self.full)
 
     def __call__(self, slices) -> torch.Tensor:
         """W fp32 slices of this rank's range -> fp32 [n] aggregate on every rank."""
@@ -509,6 +640,7 @@ class RangeAggregator:
 
     def aggregate_int(self, slices) -> torch.Tensor:
         """W fp32 slices -> this rank's integer aggregate (int32 wrapped, or int16
-        saturated with its slot flags in `ovf_shard`), no gather."""
+        saturated with its slot flags in `ovf_shard`), no gather.  k="block": scaled per block, the
+        scales in `k_shard`."""
         m = self._reduce(slices)
         return self.sum_shard[:m]

@@ -17,7 +17,8 @@ These are the kernels that replace the reference's CPU / switch arithmetic:
   block_scales / *_blk       one scale per block of V values instead (include/ina_blk.h); on the
                              packet path the block is the packet (include/ina_pkt_blk.h), and
                              Switch.process_apply* / run_apply take the int8 scales for k
-                             (include/ina_switch_blk.h)
+                             (include/ina_switch_blk.h); quantize_i16_wire_blk / i16_wire_finish_blk
+                             are the sharded int16 wire's (include/ina_shard_blk.h)
 """
 from __future__ import annotations
 
@@ -928,6 +929,51 @@ def dequantize_blk(s: torch.Tensor, kblk: torch.Tensor, V: int, out: torch.Tenso
     fn = load().ina_dequantize_blk_i16_f32 if s.dtype == torch.int16 else load().ina_dequantize_blk_i32_f32
     check(fn(s.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), s.numel(), _stream(s)), "dequantize_blk")
     return out
+
+
+def quantize_i16_wire_blk(x: torch.Tensor, kblk: torch.Tensor, V: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """quantize_i16_wire() with block s scaled by 2^kblk[s] (include/ina_shard_blk.h): the wire of
+    dist.ShardedAggregator(wire="i16", k="block")."""
+    V = _blk_v(V)
+    _blk_f32(x, "x")
+    kblk = _blk_scales_arg(kblk, (x.numel() + V - 1) // V, x, given=True)
+    out = torch.empty(x.shape, dtype=torch.int32, device=x.device) if out is None else out
+    _fits(out, x.numel())
+    _req(out, torch.int32, "out")
+    _same_device(x, out)
+    check(load().ina_quantize_blk_f32_i16_wire(x.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), x.numel(),
+                                               _stream(x)), "quantize_i16_wire_blk")
+    return out
+
+
+def i16_wire_finish_blk(wire_sum: torch.Tensor, kblk: torch.Tensor, V: int, out16=None, y=None, overflow=None,
+                        want_out16: bool = True, want_y: bool = True):
+    """i16_wire_finish() with y scaled by 2^-kblk[block]; the flags are per block.  wire_sum may be
+    a rank's shard (starting on a block boundary) with kblk that shard's slice of the scales."""
+    V = _blk_v(V)
+    for t, name in ((wire_sum, "wire_sum"), (y, "y")):
+        if isinstance(t, torch.Tensor) and t.dtype in _X16:
+            raise ValueError(f"block scales take fp32 buckets: {name} is {t.dtype}")
+    _req(wire_sum, torch.int32, "wire_sum")
+    n, dev = wire_sum.numel(), wire_sum.device
+    nblk = (n + V - 1) // V
+    kblk = _blk_scales_arg(kblk, nblk, wire_sum, given=True)
+    if out16 is None and want_out16:
+        out16 = torch.empty(n, dtype=torch.int16, device=dev)
+    if y is None and want_y:
+        y = torch.empty(n, dtype=torch.float32, device=dev)
+    overflow = torch.empty(nblk, dtype=torch.uint8, device=dev) if overflow is None else overflow
+    for t, dt, cnt, name in ((out16, torch.int16, n, "out16"), (y, torch.float32, n, "y"),
+                             (overflow, torch.uint8, nblk, "overflow")):
+        if t is not None:
+            _fits(t, cnt, name)
+            _req(t, dt, name)
+            _same_device(wire_sum, t)
+    check(load().ina_i16_wire_finish_blk(wire_sum.data_ptr(), n, kblk.data_ptr(), V,
+                                         out16.data_ptr() if out16 is not None else None,
+                                         y.data_ptr() if y is not None else None, overflow.data_ptr(),
+                                         _stream(wire_sum)), "i16_wire_finish_blk")
+    return out16, y, overflow
 
 
 def ps_apply_blk(local: torch.Tensor, sum_int: torch.Tensor, kblk: torch.Tensor, V: int, weight_step: float,

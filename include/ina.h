@@ -399,6 +399,9 @@ int ina_switch_process(const ina_switch_state_t* st, uint8_t* pkts, size_t npkts
 /* The PS step with per-block scales (2^-kblk[slot] for 2^-k); the contract is stated in
  * ina_switch_blk.h, included here (it needs the switch types above). */
 #include "ina_switch_blk.h"   /* ina_switch_blk */
+/* Per-block scales on the int16 wire of a sharded bucket (the block-scaled wire quantiser and its
+ * decode); the contract is stated in ina_shard_blk.h. */
+#include "ina_shard_blk.h"   /* the block-scaled int16 wire */
 
 /* Diagnostic: which slot-sort path the last call over `scratch` took (a batch of npkts
  * packets, more than 768 of them; the one-workgroup small-batch paths do not record one; the

@@ -219,6 +219,86 @@ def run_blk(dev):
     return rows
 
 
+def run_blk_x16(dev, dtype=torch.bfloat16):
+    """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
+    caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
+    fp32 block-scaled sibling on the widened bucket, timed twice -- the two times' difference is the spread --
+    and (b) widen into a preallocated fp32 buffer, then the sibling.  The bar (run_x16's, relative only): the
+    16-bit call beats (b) and is no slower than (a) plus (a)'s spread."""
+    from ina_amd import blk, ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(18)
+    n, Wmax, Wp = 25_557_032, 16, 8
+    name16 = {torch.bfloat16: "bf16", torch.float16: "fp16"}[dtype]
+    b32 = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(Wmax)]
+    b16 = [b.to(dtype) for b in b32]
+    b32 = [b.float() for b in b16]                       # the widened buckets: the same values
+    wid = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(Wmax)]
+    base = torch.randn(n, device=dev, generator=gen) * 1e-2
+    q = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    y32 = torch.empty(n, dtype=torch.float32, device=dev)
+    y16 = torch.empty(n, dtype=dtype, device=dev)
+
+    def widen(W):
+        return lambda: [w.copy_(x) for w, x in zip(wid[:W], b16[:W])]
+
+    def trio(run, name, V, nb16, f16, f32, pre):
+        t32a = _time(f32)
+        t16 = _time(f16)
+        tw = _time(lambda: (pre(), f32()))
+        t32b = _time(f32)
+        lo, hi = min(t32a, t32b), max(t32a, t32b)
+        rows.append(_row(f"{name} V={V} [{name16} blk, run {run}]", t16, nb16,
+                         sibling_us=[round(t32a * 1e6, 2), round(t32b * 1e6, 2)],
+                         sibling_spread_us=round((hi - lo) * 1e6, 2), widen_then_sibling_us=round(tw * 1e6, 2),
+                         faster_than_widen_then_sibling=bool(t16 < tw),
+                         no_slower_than_sibling=bool(t16 <= hi + (hi - lo))))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = (n + V - 1) // V
+            f = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kb = torch.empty(nblk, dtype=torch.int8, device=dev)
+            kb32 = ops.block_scales(b32[:8], V, bits=32)
+            kb16 = ops.block_scales(b32, V, bits=16)
+            trio(run, "block_scales W=8", V, 16 * n + nblk, lambda: blk.block_scales(b16[:8], V, out=kb),
+                 lambda: ops.block_scales(b32[:8], V, out=kb), widen(8))
+            trio(run, "quantize", V, 6 * n + nblk, lambda: blk.quantize(b16[0], kb32, V, out=q),
+                 lambda: ops.quantize_blk(b32[0], kb32, V, out=q), widen(1))
+            trio(run, "quantize_i16", V, 4 * n + 2 * nblk, lambda: blk.quantize_i16(b16[0], kb16, V, out=o16, overflow=f),
+                 lambda: ops.quantize_i16_blk(b32[0], kb16, V, out=o16, overflow=f), widen(1))
+            trio(run, "quantize_reduce W=8 auto", V, 20 * n + nblk,
+                 lambda: blk.quantize_reduce(b16[:8], V, out=q, kblk_out=kb),
+                 lambda: ops.quantize_reduce_blk(b32[:8], V, out=q, kblk_out=kb), widen(8))
+            for W in (4, 16):
+                trio(run, f"quantize_reduce_i16 W={W} auto", V, (2 * W + 2) * n + 2 * nblk,
+                     lambda: blk.quantize_reduce_i16(b16[:W], V, out=o16, overflow=f, kblk_out=kb),
+                     lambda: ops.quantize_reduce_i16_blk(b32[:W], V, out=o16, overflow=f, kblk_out=kb), widen(W))
+            # decode: the 16-bit call against the fp32 decode, and against the fp32 decode + a narrowing copy
+            ops.quantize_reduce_blk(b32[:8], V, kblk=kb32, out=q)
+            ops.quantize_reduce_i16_blk(b32, V, kblk=kb16, out=o16, overflow=f)
+            trio(run, "dequantize_i32", V, 6 * n + nblk, lambda: blk.dequantize(q, kb32, V, out=y16),
+                 lambda: ops.dequantize_blk(q, kb32, V, out=y32), lambda: y16.copy_(y32))
+            trio(run, "dequantize_i16", V, 4 * n + nblk, lambda: blk.dequantize(o16, kb16, V, out=y16),
+                 lambda: ops.dequantize_blk(o16, kb16, V, out=y32), lambda: y16.copy_(y32))
+            # the 8 workers' split packs in one launch, against an fp32 base
+            npk = nblk
+            hdrs = [torch.zeros((npk, 16), dtype=torch.uint8, device=dev) for _ in range(Wp)]
+            pays = [torch.empty((npk, 4 * V), dtype=torch.uint8, device=dev) for _ in range(Wp)]
+            args = (V, list(range(1, Wp + 1)), Wp, 1, 1)
+            out_b = Wp * (npk * 16 + npk * 4 * V)
+            kbp = ops.block_scales(b32[:Wp], V, bits=32, base=base)
+            for mode, kw in (("auto", dict(kblk_out=kb)), ("given", dict(kblk=kbp))):
+                trio(run, f"quantize_pack_nga_multi_split W={Wp} {mode}", V, (2 * Wp + 4) * n + out_b + nblk,
+                     lambda: blk.quantize_pack_nga_multi_split(b16[:Wp], *args, base=base, hdrs=hdrs, pays=pays, **kw),
+                     lambda: ops.quantize_pack_nga_multi_split_blk(b32[:Wp], *args, base=base, hdrs=hdrs, pays=pays, **kw),
+                     widen(Wp))
+            del hdrs, pays
+    return rows
+
+
 def run_blk_packets(dev):
     """Per-block scales on the packet path (include/ina_pkt_blk.h) at the ResNet-50 size, W = 8, V = 256
     and 32, cold caches, median of 20, the whole set twice in this process (run 1 / run 2), as run_blk.
@@ -766,6 +846,7 @@ def run_extra(dev):
     del hosts, hout, dbuf, b3, o3
     rows += run_x16(dev)
     rows += run_blk(dev)
+    rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)
     rows += run_blk_shard(dev)

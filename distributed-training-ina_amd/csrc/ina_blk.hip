@@ -28,6 +28,13 @@
 //
 // Scalar path (any other V or alignment): one wave per block, lanes striding over the block,
 // the same helpers, identical results.
+//
+// bf16 / fp16 buckets (include/ina_x16_blk.h): every kernel that reads or writes a bucket takes its
+// element type X, float or h16<XT>.  Only the chunk's load (ld4: one 8-byte load, widened in
+// registers, exact) and the decode's store (st4: rounded once to nearest even, one 8-byte store)
+// differ; a lane still owns 4 values, a block is still V/4 lanes, and everything after the load is
+// the fp32 kernel's code on the widened chunk, so held chunks cost the fp32 kernel's registers.
+// The vector path needs the 16-bit side 8-byte aligned.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -68,6 +75,11 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
 // a lane's chunk of 4 values at element e; a chunk that crosses n is read and written value by
 // value (values past n read as 0)
 // ---------------------------------------------------------------------------
+// (X below: the element type of a call's buckets -- float, or h16<XT>, one bf16 / fp16 value)
+template <int XT>
+struct h16 {
+    uint16_t v;
+};
 template <bool NT = true>
 __device__ __forceinline__ f32x4 ld4(const float* p, size_t e, size_t n) {
     if (e + 4 <= n) {
@@ -80,6 +92,23 @@ __device__ __forceinline__ f32x4 ld4(const float* p, size_t e, size_t n) {
     if (e + 2 < n) v.z = p[e + 2];
     return v;
 }
+// a bf16 / fp16 bucket (include/ina_x16_blk.h): one 8-byte load, widened in registers (exact)
+template <int XT>
+__device__ __forceinline__ f32x4 ld4(const h16<XT>* p, size_t e, size_t n) {
+    if (e + 4 <= n) return widen16x4<XT>(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + e)));
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (e < n) v.x = widen16<XT>(p[e].v);
+    if (e + 1 < n) v.y = widen16<XT>(p[e + 1].v);
+    if (e + 2 < n) v.z = widen16<XT>(p[e + 2].v);
+    return v;
+}
+// one value of a bucket, and one decoded value into one (16-bit: rounded once to nearest even)
+__device__ __forceinline__ float ld1(const float* p, size_t j) { return p[j]; }
+template <int XT>
+__device__ __forceinline__ float ld1(const h16<XT>* p, size_t j) { return widen16<XT>(p[j].v); }
+__device__ __forceinline__ void st1(float v, float* p, size_t j) { p[j] = v; }
+template <int XT>
+__device__ __forceinline__ void st1(float v, h16<XT>* p, size_t j) { p[j].v = (uint16_t)rne16<XT>(v); }
 __device__ __forceinline__ u32x4 ld4i(const int32_t* p, size_t e, size_t n) {
     if (e + 4 <= n) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + e));
     u32x4 v = {0u, 0u, 0u, 0u};
@@ -116,6 +145,17 @@ __device__ __forceinline__ void st4(V4 v, T* p, size_t e, size_t n) {
         if (e < n) p[e] = bits_as<T>(v.x);
         if (e + 1 < n) p[e + 1] = bits_as<T>(v.y);
         if (e + 2 < n) p[e + 2] = bits_as<T>(v.z);
+    }
+}
+// 4 decoded values into a 16-bit buffer: one 8-byte store
+template <int XT>
+__device__ __forceinline__ void st4(f32x4 v, h16<XT>* p, size_t e, size_t n) {
+    if (e + 4 <= n) {
+        stream_store(u32x2{rne16x2<XT>(v.x, v.y), rne16x2<XT>(v.z, v.w)}, reinterpret_cast<u32x2*>(p + e));
+    } else {
+        if (e < n) st1(v.x, p, e);
+        if (e + 1 < n) st1(v.y, p, e + 1);
+        if (e + 2 < n) st1(v.z, p, e + 2);
     }
 }
 // 4 int16 (held widened) as one 8-byte store
@@ -158,7 +198,8 @@ __device__ __forceinline__ f32x4 upd4(f32x4 l, f32x4 y, float ws) {
     for (size_t base_ = tid_ & ~(size_t)63; base_ < (nq); base_ += stride_)
 
 // scales alone: W + 1 streams, 4 workers' loads in flight (k_absmax_multi_f32's loop)
-__global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<float> xs, int W, const float* __restrict__ base,
+template <typename X>
+__global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<X> xs, int W, const float* __restrict__ base,
                                                      size_t n, int shift, double lim,
                                                      int8_t* __restrict__ kblk) {
     const size_t nq = (n + 3) / 4;
@@ -185,8 +226,8 @@ __global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<float> xs, int W, c
 
 // fused quantise + W-way reduce to int32 (W = 1: the plain quantiser).  W > 0: compile-time worker
 // count, chunks held in registers; W = 0: runtime count, re-read under AUTO.
-template <int W, bool AUTO>
-__global__ __launch_bounds__(kBlk) void k_qr_blk_i32(PtrPack<float> in, int Wd, int8_t* __restrict__ kblk,
+template <typename X, int W, bool AUTO>
+__global__ __launch_bounds__(kBlk) void k_qr_blk_i32(PtrPack<X> in, int Wd, int8_t* __restrict__ kblk,
                                                      double lim, int32_t* out, size_t n, int shift) {
     const int nw = W > 0 ? W : Wd;
     constexpr bool HOLD = AUTO && W > 0;      // given scales: a chunk is quantised as it arrives
@@ -228,9 +269,9 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i32(PtrPack<float> in, int Wd, 
     }
 }
 
-template <typename T>
+template <typename T, typename Y>
 __global__ __launch_bounds__(kBlk) void k_dq_blk(const T* __restrict__ sv, const int8_t* __restrict__ kblk,
-                                                 float* __restrict__ y, size_t n, int shift) {
+                                                 Y* __restrict__ y, size_t n, int shift) {
     const size_t nq = (n + 3) / 4;
     const int lane = threadIdx.x & 63;
     INA_BLK_QUAD_LOOP(nq) {
@@ -299,9 +340,18 @@ __global__ __launch_bounds__(kBlk) void k_ps_combine_ina_blk(const float* local,
 // ---------------------------------------------------------------------------
 // vector path, int16 out: a wave owns 512 values, lane l the 4 at 4l of each 256-value half
 // ---------------------------------------------------------------------------
-template <int W, bool AUTO>
-__global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<float> in, int Wd, int8_t* __restrict__ kblk,
-                                                     double lim, int16_t* __restrict__ out, size_t n, int shift,
+// the int16 out: it may alias a 16-bit bucket (the same width), never an fp32 one
+template <typename X>
+struct Out16 {
+    using P = int16_t*;
+};
+template <>
+struct Out16<float> {
+    using P = int16_t* __restrict__;
+};
+template <typename X, int W, bool AUTO>
+__global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8_t* __restrict__ kblk,
+                                                     double lim, typename Out16<X>::P out, size_t n, int shift,
                                                      int V, uint8_t* __restrict__ ovf) {
     const int nw = W > 0 ? W : Wd;
     constexpr bool HOLD = AUTO && W > 0;
@@ -383,22 +433,23 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<float> in, int Wd, 
 // striding over the block's values; one kernel for every entry point.
 // ---------------------------------------------------------------------------
 enum { S_SCALES, S_Q32, S_Q16, S_DQ32, S_DQ16, S_APPLY, S_COMB };
+template <typename X>
 struct ScalarArgs {
-    PtrPack<float> in;     // worker buffers (S_SCALES, S_Q32, S_Q16, S_COMB)
+    PtrPack<X> in;         // worker buffers (S_SCALES, S_Q32, S_Q16, S_COMB)
     int W;
     const float* base;     // S_SCALES: base or null; S_APPLY, S_COMB: local
     const void* src;       // S_DQ32, S_DQ16, S_APPLY: the integers
     int8_t* kblk;          // read (GIVEN) or written (AUTO; may be null for S_COMB)
     double lim;
-    void* out;
+    void* out;             // S_DQ32, S_DQ16: X values; otherwise the mode's own type
     size_t n;
     size_t V;
     uint8_t* ovf;
     float ws;
 };
 
-template <int MODE, bool AUTO>
-__global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs a) {
+template <typename X, int MODE, bool AUTO>
+__global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<X> a) {
     const size_t wave = ((size_t)blockIdx.x * kBlk + threadIdx.x) >> 6;
     const size_t nwaves = ((size_t)gridDim.x * kBlk) >> 6;
     const int lane = threadIdx.x & 63;
@@ -411,7 +462,7 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs a) {
             uint32_t m = 0u;
             for (size_t j = j0 + lane; j < j1; j += 64)
                 for (int w = 0; w < a.W; ++w) {
-                    const float x = a.in.p[w][j];
+                    const float x = ld1(a.in.p[w], j);
                     m = umax(m, absbits((kDelta && a.base) ? __fsub_rn(x, a.base[j]) : x));
                 }
             m = group_max(m, 64);
@@ -426,23 +477,23 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs a) {
         for (size_t j = j0 + lane; j < j1; j += 64) {
             if constexpr (MODE == S_Q32) {
                 uint32_t acc = 0u;
-                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(a.in.p[w][j], sc);
+                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(ld1(a.in.p[w], j), sc);
                 static_cast<int32_t*>(a.out)[j] = (int32_t)acc;
             } else if constexpr (MODE == S_Q16) {
                 int32_t acc = 0;
-                for (int w = 0; w < a.W; ++w) acc += q16(a.in.p[w][j], sc, sat);
+                for (int w = 0; w < a.W; ++w) acc += q16(ld1(a.in.p[w], j), sc, sat);
                 static_cast<int16_t*>(a.out)[j] = (int16_t)sat16(acc, sat);
             } else if constexpr (MODE == S_DQ32) {
-                static_cast<float*>(a.out)[j] = __fmul_rn((float)static_cast<const int32_t*>(a.src)[j], inv);
+                st1(__fmul_rn((float)static_cast<const int32_t*>(a.src)[j], inv), static_cast<X*>(a.out), j);
             } else if constexpr (MODE == S_DQ16) {
-                static_cast<float*>(a.out)[j] = __fmul_rn((float)static_cast<const int16_t*>(a.src)[j], inv);
+                st1(__fmul_rn((float)static_cast<const int16_t*>(a.src)[j], inv), static_cast<X*>(a.out), j);
             } else if constexpr (MODE == S_APPLY) {
                 const float y = __fmul_rn((float)static_cast<const int32_t*>(a.src)[j], inv);
                 static_cast<float*>(a.out)[j] = __fadd_rn(a.base[j], __fmul_rn(y, a.ws));
             } else {
                 const float l = a.base[j];
                 uint32_t acc = 0u;
-                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(__fsub_rn(a.in.p[w][j], l), sc);
+                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(__fsub_rn(ld1(a.in.p[w], j), l), sc);
                 const float y = __fmul_rn((float)(int32_t)acc, inv);
                 static_cast<float*>(a.out)[j] = __fadd_rn(l, __fmul_rn(y, a.ws));
             }
@@ -476,10 +527,10 @@ int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) 
 }
 int launched() { return check_launch("block-scale kernel launch"); }
 
-template <int MODE, bool AUTO>
-void launch_scalar(const ScalarArgs& a, hipStream_t s) {
+template <int MODE, bool AUTO, typename X>
+void launch_scalar(const ScalarArgs<X>& a, hipStream_t s) {
     const size_t nblk = (a.n + a.V - 1) / a.V;
-    hipLaunchKernelGGL((k_blk_scalar<MODE, AUTO>), dim3(grid_of(nblk * 64, default_grid_cap())), dim3(kBlk), 0, s, a);
+    hipLaunchKernelGGL((k_blk_scalar<X, MODE, AUTO>), dim3(grid_of(nblk * 64, default_grid_cap())), dim3(kBlk), 0, s, a);
 }
 
 // compile-time worker counts of the fused kernels (others: the runtime-W instance)
@@ -493,63 +544,140 @@ void launch_scalar(const ScalarArgs& a, hipStream_t s) {
         default: LAUNCH(0);         \
     }
 
-int reduce_i32(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int32_t* out, size_t n,
+// the vector path reads a lane's 4 values in one load: 16 bytes of an fp32 bucket, 8 of a 16-bit one
+template <typename X>
+bool src_aligned(const PtrPack<X>& pk, int W) {
+    for (int w = 0; w < W; ++w)
+        if ((uintptr_t)pk.p[w] % (4 * sizeof(X))) return false;
+    return true;
+}
+using bf16_t = h16<INA_X16_BF16>;
+using fp16_t = h16<INA_X16_F16>;
+// F<h16<xtype>>(args) for a checked xtype
+#define INA_BLK_X16_CALL(xtype, F, ...) \
+    ((xtype) == INA_X16_BF16 ? F<bf16_t>(__VA_ARGS__) : F<fp16_t>(__VA_ARGS__))
+
+// X: float (B = float) or h16<XT> (B = void, include/ina_x16_blk.h)
+template <typename X, typename B>
+int block_scales(const B* const* xs, int W, const float* base, size_t n, int V, int degree, int bits, int8_t* kblk,
+                 ina_stream_t stream) {
+    double lim;
+    if (int rc = check_v(V)) return rc;
+    if (int rc = scale_lim(degree, bits, lim)) return rc;
+    if (n == 0) return INA_OK;
+    PtrPack<X> pk;
+    bool al;
+    if (int rc = fill_pack(pk, xs, W, al)) return rc;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    hipStream_t s = hs(stream);
+    int shift;
+    if (vec_v(V, shift) && src_aligned(pk, W) && (!base || aligned16(base))) {
+        hipLaunchKernelGGL(k_blk_scales<X>, dim3(grid_of((n + 3) / 4, stream_grid_cap())), dim3(kBlk), 0, s, pk, W, base,
+                           n, shift, lim, kblk);
+    } else {
+        ScalarArgs<X> a{pk, W, base, nullptr, kblk, lim, nullptr, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_SCALES, true>(a, s);
+    }
+    return launched();
+}
+
+template <typename X, typename B>
+int reduce_i32(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int32_t* out, size_t n,
                ina_stream_t stream) {
     double lim;
     if (int rc = check_v(V)) return rc;
     if (int rc = check_mode(mode, kblk, degree, 32, lim)) return rc;
     if (n == 0) return INA_OK;
-    PtrPack<float> pk;
+    PtrPack<X> pk;
     bool al;
     if (int rc = fill_pack(pk, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
-    if (vec_v(V, shift) && al && aligned16(out)) {
+    if (vec_v(V, shift) && src_aligned(pk, W) && aligned16(out)) {
         // the sibling's grids: covering for W <= 8, the streaming cap beyond
         const dim3 g(grid_of((n + 3) / 4, W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
-#define L(WW)                                                                                              \
-    do {                                                                                                   \
-        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<WW, true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift); \
-        else hipLaunchKernelGGL((k_qr_blk_i32<WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift);   \
+#define L(WW)                                                                                                 \
+    do {                                                                                                      \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<X, WW, true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift); \
+        else hipLaunchKernelGGL((k_qr_blk_i32<X, WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift);   \
     } while (0)
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
+        ScalarArgs<X> a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
         if (autok) launch_scalar<S_Q32, true>(a, s);
         else launch_scalar<S_Q32, false>(a, s);
     }
     return launched();
 }
 
-int reduce_i16(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int16_t* out, size_t n,
+template <typename X, typename B>
+int reduce_i16(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int16_t* out, size_t n,
                uint8_t* ovf, ina_stream_t stream) {
     double lim;
     if (int rc = check_v(V)) return rc;
     if (int rc = check_mode(mode, kblk, degree, 16, lim)) return rc;
     if (n == 0) return INA_OK;
-    PtrPack<float> pk;
+    PtrPack<X> pk;
     bool al;
     if (int rc = fill_pack(pk, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
-    if (vec_v(V, shift) && al && aligned16(out)) {
+    // (out is stored 8 bytes a lane; beside fp32 buckets it keeps the 16-byte rule it always had)
+    if (vec_v(V, shift) && src_aligned(pk, W) && (uintptr_t)out % (4 * sizeof(X)) == 0) {
         const dim3 g(grid_of((n + 511) / 512 * 64, default_grid_cap())), b(kBlk);
-#define L(WW)                                                                                                       \
-    do {                                                                                                            \
-        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<(WW <= 8 ? WW : 0), true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf); \
-        else hipLaunchKernelGGL((k_qr_blk_i16<WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf);    \
+#define L(WW)                                                                                                          \
+    do {                                                                                                               \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<X, (WW <= 8 ? WW : 0), true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf); \
+        else hipLaunchKernelGGL((k_qr_blk_i16<X, WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf);    \
     } while (0)
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
+        ScalarArgs<X> a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
         if (autok) launch_scalar<S_Q16, true>(a, s);
         else launch_scalar<S_Q16, false>(a, s);
+    }
+    return launched();
+}
+
+// one bucket with given scales: the reduce of one
+template <typename X, typename B>
+int quantize_i32(const B* x, const int8_t* kblk, int V, int32_t* q, size_t n, ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    const B* one[1] = {x};
+    return reduce_i32<X>(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, stream);
+}
+template <typename X, typename B>
+int quantize_i16(const B* x, const int8_t* kblk, int V, int16_t* q, size_t n, uint8_t* ovf, ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    const B* one[1] = {x};
+    return reduce_i16<X>(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, ovf, stream);
+}
+
+// T: int32_t or int16_t; Y: float or h16<YT>.  The vector path loads and stores a lane's 4 values at once.
+template <typename Y, typename T, typename B>
+int dequantize(const T* sv, const int8_t* kblk, int V, B* y, size_t n, ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (sizeof(Y) == 2 && ((uintptr_t)y & 1u)) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
+    int shift;
+    if (vec_v(V, shift) && (uintptr_t)sv % (4 * sizeof(T)) == 0 && (uintptr_t)y % (4 * sizeof(Y)) == 0) {
+        hipLaunchKernelGGL((k_dq_blk<T, Y>), dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
+                           kblk, static_cast<Y*>(y), n, shift);
+    } else {
+        ScalarArgs<Y> a{{}, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
+        if constexpr (sizeof(T) == 4) launch_scalar<S_DQ32, false>(a, hs(stream));
+        else launch_scalar<S_DQ16, false>(a, hs(stream));
     }
     return launched();
 }
@@ -563,83 +691,79 @@ extern "C" {
 
 int ina_block_scales_f32(const float* const* xs, int W, const float* base, size_t n, int V, int degree, int bits,
                          int8_t* kblk, ina_stream_t stream) {
-    double lim;
-    if (int rc = check_v(V)) return rc;
-    if (int rc = scale_lim(degree, bits, lim)) return rc;
-    if (n == 0) return INA_OK;
-    PtrPack<float> pk;
-    bool al;
-    if (int rc = fill_pack(pk, xs, W, al)) return rc;
-    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
-    hipStream_t s = hs(stream);
-    int shift;
-    if (vec_v(V, shift) && al && (!base || aligned16(base))) {
-        hipLaunchKernelGGL(k_blk_scales, dim3(grid_of((n + 3) / 4, stream_grid_cap())), dim3(kBlk), 0, s, pk, W, base,
-                           n, shift, lim, kblk);
-    } else {
-        ScalarArgs a{pk, W, base, nullptr, kblk, lim, nullptr, n, (size_t)V, nullptr, 0.f};
-        launch_scalar<S_SCALES, true>(a, s);
-    }
-    return launched();
+    return block_scales<float>(xs, W, base, n, V, degree, bits, kblk, stream);
 }
 
 int ina_quantize_blk_f32_i32(const float* x, const int8_t* kblk, int V, int32_t* q, size_t n, ina_stream_t stream) {
-    if (int rc = check_v(V)) return rc;
-    if (n == 0) return INA_OK;
-    if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
-    const float* one[1] = {x};
-    return reduce_i32(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, stream);
+    return quantize_i32<float>(x, kblk, V, q, n, stream);
 }
 
 int ina_quantize_blk_f32_i16_sat(const float* x, const int8_t* kblk, int V, int16_t* q, size_t n, uint8_t* ovf,
                                  ina_stream_t stream) {
-    if (int rc = check_v(V)) return rc;
-    if (n == 0) return INA_OK;
-    if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
-    const float* one[1] = {x};
-    return reduce_i16(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, ovf, stream);
+    return quantize_i16<float>(x, kblk, V, q, n, ovf, stream);
 }
 
 int ina_quantize_reduce_blk_f32_i32(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V,
                                     int32_t* out, size_t n, ina_stream_t stream) {
-    return reduce_i32(bufs, W, kblk, mode, degree, V, out, n, stream);
+    return reduce_i32<float>(bufs, W, kblk, mode, degree, V, out, n, stream);
 }
 
 int ina_quantize_reduce_blk_f32_i16_sat(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V,
                                         int16_t* out, size_t n, uint8_t* ovf, ina_stream_t stream) {
-    return reduce_i16(bufs, W, kblk, mode, degree, V, out, n, ovf, stream);
+    return reduce_i16<float>(bufs, W, kblk, mode, degree, V, out, n, ovf, stream);
 }
 
 int ina_dequantize_blk_i32_f32(const int32_t* sv, const int8_t* kblk, int V, float* y, size_t n,
                                ina_stream_t stream) {
-    if (int rc = check_v(V)) return rc;
-    if (n == 0) return INA_OK;
-    if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
-    int shift;
-    if (vec_v(V, shift) && aligned16(sv) && aligned16(y)) {
-        hipLaunchKernelGGL(k_dq_blk<int32_t>, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
-                           kblk, y, n, shift);
-    } else {
-        ScalarArgs a{{}, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
-        launch_scalar<S_DQ32, false>(a, hs(stream));
-    }
-    return launched();
+    return dequantize<float>(sv, kblk, V, y, n, stream);
 }
 
 int ina_dequantize_blk_i16_f32(const int16_t* sv, const int8_t* kblk, int V, float* y, size_t n,
                                ina_stream_t stream) {
-    if (int rc = check_v(V)) return rc;
-    if (n == 0) return INA_OK;
-    if (!sv || !y || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
-    int shift;
-    if (vec_v(V, shift) && ((uintptr_t)sv % 8 == 0) && aligned16(y)) {
-        hipLaunchKernelGGL(k_dq_blk<int16_t>, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
-                           kblk, y, n, shift);
-    } else {
-        ScalarArgs a{{}, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
-        launch_scalar<S_DQ16, false>(a, hs(stream));
-    }
-    return launched();
+    return dequantize<float>(sv, kblk, V, y, n, stream);
+}
+
+// ---- bf16 / fp16 buckets (include/ina_x16_blk.h): the type code first, then the fp32 sibling's checks ----
+int ina_block_scales_x16(const void* const* xs, int xtype, int W, const float* base, size_t n, int V, int degree,
+                         int bits, int8_t* kblk, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    return INA_BLK_X16_CALL(xtype, block_scales, xs, W, base, n, V, degree, bits, kblk, stream);
+}
+
+int ina_quantize_blk_x16_i32(const void* x, int xtype, const int8_t* kblk, int V, int32_t* q, size_t n,
+                             ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    return INA_BLK_X16_CALL(xtype, quantize_i32, x, kblk, V, q, n, stream);
+}
+
+int ina_quantize_blk_x16_i16_sat(const void* x, int xtype, const int8_t* kblk, int V, int16_t* q, size_t n,
+                                 uint8_t* ovf, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    return INA_BLK_X16_CALL(xtype, quantize_i16, x, kblk, V, q, n, ovf, stream);
+}
+
+int ina_quantize_reduce_blk_x16_i32(const void* const* bufs, int xtype, int W, int8_t* kblk, int mode, int degree,
+                                    int V, int32_t* out, size_t n, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    return INA_BLK_X16_CALL(xtype, reduce_i32, bufs, W, kblk, mode, degree, V, out, n, stream);
+}
+
+int ina_quantize_reduce_blk_x16_i16_sat(const void* const* bufs, int xtype, int W, int8_t* kblk, int mode, int degree,
+                                        int V, int16_t* out, size_t n, uint8_t* ovf, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    return INA_BLK_X16_CALL(xtype, reduce_i16, bufs, W, kblk, mode, degree, V, out, n, ovf, stream);
+}
+
+int ina_dequantize_blk_i32_x16(const int32_t* sv, const int8_t* kblk, int V, void* y, int ytype, size_t n,
+                               ina_stream_t stream) {
+    if (int rc = check_x16_type(ytype)) return rc;
+    return INA_BLK_X16_CALL(ytype, dequantize, sv, kblk, V, y, n, stream);
+}
+
+int ina_dequantize_blk_i16_x16(const int16_t* sv, const int8_t* kblk, int V, void* y, int ytype, size_t n,
+                               ina_stream_t stream) {
+    if (int rc = check_x16_type(ytype)) return rc;
+    return INA_BLK_X16_CALL(ytype, dequantize, sv, kblk, V, y, n, stream);
 }
 
 int ina_ps_apply_blk_i32(const float* local, const int32_t* sum_int, const int8_t* kblk, int V, double weight_step,
@@ -652,7 +776,7 @@ int ina_ps_apply_blk_i32(const float* local, const int32_t* sum_int, const int8_
         hipLaunchKernelGGL(k_ps_apply_blk, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), local,
                            sum_int, kblk, (float)weight_step, out, n, shift);
     } else {
-        ScalarArgs a{{}, 0, local, sum_int, const_cast<int8_t*>(kblk), 1.0, out, n, (size_t)V, nullptr,
+        ScalarArgs<float> a{{}, 0, local, sum_int, const_cast<int8_t*>(kblk), 1.0, out, n, (size_t)V, nullptr,
                      (float)weight_step};
         launch_scalar<S_APPLY, false>(a, hs(stream));
     }
@@ -678,7 +802,7 @@ int ina_ps_combine_ina_blk_f32(const float* local, const float* const* paras, in
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs a{pk, W, local, nullptr, kblk_out, lim, out, n, (size_t)V, nullptr, ws};
+        ScalarArgs<float> a{pk, W, local, nullptr, kblk_out, lim, out, n, (size_t)V, nullptr, ws};
         launch_scalar<S_COMB, true>(a, s);
     }
     return launched();

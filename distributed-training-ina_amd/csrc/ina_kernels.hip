@@ -817,12 +817,14 @@ struct LdF32 {
     using X = float;
     using Raw = f32x4;
     static __device__ __forceinline__ f32x4 widen4(Raw r) { return r; }
+    static __device__ __forceinline__ float widen1(X x) { return x; }
 };
 template <int XT>
 struct LdX16 {
     using X = uint16_t;
     using Raw = u32x2;
     static __device__ __forceinline__ f32x4 widen4(Raw r) { return widen16x4<XT>(r); }
+    static __device__ __forceinline__ float widen1(X x) { return widen16<XT>(x); }
 };
 struct SrcQ32 {
     using Ld = LdF32;
@@ -1317,9 +1319,10 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
 // registers, takes the packet's max |delta| with the butterfly of ina_blk.hip's AUTO reduce over
 // the packet's L adjacent lanes, writes kblk[packet] and quantises the held chunks: each bucket
 // is read once.  The loop is wave-uniform (t0 steps whole waves); lanes past the last chunk
-// contribute 0 to the butterfly and store nothing.
-template <int G, bool AUTO>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<float> a, const float* __restrict__ base,
+// contribute 0 to the butterfly and store nothing.  Ld: LdF32, or LdX16<XT> for bf16 / fp16 buckets
+// (include/ina_x16_blk.h): 8-byte worker loads widened in registers, the held deltas fp32 either way.
+template <typename Ld, int G, bool AUTO>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<typename Ld::X> a, const float* __restrict__ base,
                                                                       size_t n, int8_t* __restrict__ kblk,
                                                                       double lim, int shift, uint32_t L,
                                                                       uint32_t num_slots, size_t nch, size_t np) {
@@ -1343,7 +1346,8 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
             f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
             if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
 #pragma unroll
-            for (int g = 0; g < G; ++g) d[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
+            for (int g = 0; g < G; ++g)
+                d[g] = Ld::widen4(__builtin_nontemporal_load(reinterpret_cast<const typename Ld::Raw*>(a.x[g] + e0)));
             if (base) {                                // one test for the group, as the held registers were scheduled
 #pragma unroll
                 for (int g = 0; g < G; ++g) d[g] = delta4(d[g], b, true);
@@ -1356,9 +1360,13 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 d[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (e0 < n) d[g].x = base ? __fsub_rn(a.x[g][e0], base[e0]) : a.x[g][e0];
-                if (e0 + 1 < n) d[g].y = base ? __fsub_rn(a.x[g][e0 + 1], base[e0 + 1]) : a.x[g][e0 + 1];
-                if (e0 + 2 < n) d[g].z = base ? __fsub_rn(a.x[g][e0 + 2], base[e0 + 2]) : a.x[g][e0 + 2];
+                auto one = [&](size_t e) {
+                    const float x = Ld::widen1(a.x[g][e]);
+                    return base ? __fsub_rn(x, base[e]) : x;
+                };
+                if (e0 < n) d[g].x = one(e0);
+                if (e0 + 1 < n) d[g].y = one(e0 + 1);
+                if (e0 + 2 < n) d[g].z = one(e0 + 2);
                 if constexpr (!AUTO) put(g, d[g], k);
             }
         }
@@ -2081,6 +2089,52 @@ static int qpack_multi_split(const char* what, const XV* const* x, int W, const 
     return check_launch(what);
 }
 
+// the fp32 and 16-bit block-scaled split multi packs (xtype: 0 for fp32 buckets)
+template <typename Ld, typename XV>
+static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype, int W, const float* base, size_t n,
+                                 int8_t* kblk, int mode, int degree, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                 uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
+    using X = typename Ld::X;
+    if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
+        return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
+    double lim = 1.0;
+    if (mode == INA_BLK_AUTO) {
+        if (int rc = scale_lim(degree, 32, lim)) return rc;
+    }
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, true, kblk, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    const int V = prm[0].V;
+    const uint32_t L = (uint32_t)V / 4;
+    const int shift = log2_exact(L);                   // -1: L is no power of two
+    bool autok = mode == INA_BLK_AUTO;
+    // AUTO in the pack's own launch needs a packet to be adjacent lanes of one wave (V a power of
+    // two in [8, 256]) and every worker in one group; otherwise the scales kernel runs first and
+    // the pack reads what it wrote -- the same scales, so the same rows
+    if (autok && !(shift >= 1 && W <= kQpGroup)) {
+        int rc;
+        if constexpr (std::is_same_v<X, float>) rc = ina_block_scales_f32(x, W, base, n, V, degree, 32, kblk, stream);
+        else rc = ina_block_scales_x16(x, xtype, W, base, n, V, degree, 32, kblk, stream);
+        if (rc) return rc;
+        autok = false;
+    }
+    const size_t nch = npk * (size_t)V / 4;
+    // the default cap (tuning key 0, settable in the product build), not the siblings' ew_grid_cap() (key 14,
+    // lab build only): the geometry tests hold this wave-uniform loop and its AUTO butterfly under it
+    const dim3 grid(grid_for(std::max(nch, npk), 1)), blk(kBlock);
+    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
+        const int G = std::min(kQpGroup, W - w0);
+        const QPackRows<X> a = fill_rows<X>(w0, G, x, prm, hdr, pay, desc);
+        with_group(G, [&](auto g) {
+            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<Ld, g.value, true>
+                                 : &k_qpack_nga_multi_split_blk<Ld, g.value, false>;
+            hipLaunchKernelGGL(kernel, grid, blk, 0, hs(stream), a, base, n, kblk, lim, shift, L, prm[0].num_slots,
+                               nch, npk);
+        });
+    }
+    return check_launch(what);
+}
+
 extern "C" {
 
 const char* ina_version(void) { return "ina-mi355x 0.2 (gfx950)"; }
@@ -2626,40 +2680,21 @@ int ina_quantize_pack_nga_blk_desc(const float* x, const float* base, size_t n, 
 int ina_quantize_pack_nga_multi_split_blk(const float* const* x, int W, const float* base, size_t n, int8_t* kblk,
                                           int mode, int degree, const ina_nga_params_t* prm, uint8_t* const* hdr,
                                           uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
-    if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
-        return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
-    double lim = 1.0;
-    if (mode == INA_BLK_AUTO) {
-        if (int rc = scale_lim(degree, 32, lim)) return rc;
-    }
-    size_t npk;
-    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, true, kblk, npk)) return rc;
-    if (npk == 0) return INA_OK;
-    const int V = prm[0].V;
-    const uint32_t L = (uint32_t)V / 4;
-    const int shift = log2_exact(L);                   // -1: L is no power of two
-    bool autok = mode == INA_BLK_AUTO;
-    // AUTO in the pack's own launch needs a packet to be adjacent lanes of one wave (V a power of
-    // two in [8, 256]) and every worker in one group; otherwise the scales kernel runs first and
-    // the pack reads what it wrote -- the same scales, so the same rows
-    if (autok && !(shift >= 1 && W <= kQpGroup)) {
-        if (int rc = ina_block_scales_f32(x, W, base, n, V, degree, 32, kblk, stream)) return rc;
-        autok = false;
-    }
-    const size_t nch = npk * (size_t)V / 4;
-    // the default cap (tuning key 0, settable in the product build), not the siblings' ew_grid_cap() (key 14,
-    // lab build only): the geometry tests hold this wave-uniform loop and its AUTO butterfly under it
-    const dim3 grid(grid_for(std::max(nch, npk), 1)), blk(kBlock);
-    for (int w0 = 0; w0 < W; w0 += kQpGroup) {
-        const int G = std::min(kQpGroup, W - w0);
-        const QPackRows<float> a = fill_rows<float>(w0, G, x, prm, hdr, pay, desc);
-        with_group(G, [&](auto g) {
-            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<g.value, true> : &k_qpack_nga_multi_split_blk<g.value, false>;
-            hipLaunchKernelGGL(kernel, grid, blk, 0, hs(stream), a, base, n, kblk, lim, shift, L, prm[0].num_slots,
-                               nch, npk);
-        });
-    }
-    return check_launch("quantize_pack_nga_multi_split_blk");
+    return qpack_multi_split_blk<LdF32>("quantize_pack_nga_multi_split_blk", x, 0, W, base, n, kblk, mode, degree, prm,
+                                        hdr, pay, desc, stream);
+}
+
+int ina_quantize_pack_nga_multi_split_blk_x16(const void* const* x, int xtype, int W, const float* base, size_t n,
+                                              int8_t* kblk, int mode, int degree, const ina_nga_params_t* prm,
+                                              uint8_t* const* hdr, uint8_t* const* pay,
+                                              ina_nga_desc_t* const* desc, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    const char* what = "quantize_pack_nga_multi_split_blk_x16";
+    if (xtype == INA_X16_BF16)
+        return qpack_multi_split_blk<LdX16<INA_X16_BF16>>(what, x, xtype, W, base, n, kblk, mode, degree, prm, hdr, pay,
+                                                          desc, stream);
+    return qpack_multi_split_blk<LdX16<INA_X16_F16>>(what, x, xtype, W, base, n, kblk, mode, degree, prm, hdr, pay, desc,
+                                                     stream);
 }
 
 int ina_apply_completed_nga_blk(const uint8_t* rows, const uint8_t* pay, size_t npk, int V, size_t pstride,

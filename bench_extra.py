@@ -219,6 +219,108 @@ def run_blk(dev):
     return rows
 
 
+def run_ef(dev):
+    """Error feedback (include/ina_ef.h) at the ResNet-50 size, cold caches, median of 20, the whole
+    set twice in this process (run 1 / run 2).  Each EF call beside (a) the composition a caller
+    writes today -- torch add, the sibling quantiser, the sibling dequantiser, torch sub, every buffer
+    preallocated -- and (b) its non-EF sibling, timed twice (the two times' difference is the
+    spread).  The bar, relative only: the EF call beats (a) by more than the spread.  Its ratio to
+    sibling time x byte ratio is reported, not gated.  The packs against ef.quantize +
+    pack_nga_split per worker."""
+    from ina_amd import ef, ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(19)
+    n, k, V, W = 25_557_032, 16, 256, 8
+    nblk = (n + V - 1) // V
+    xs = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(W)]
+    rs = [torch.randn(n, device=dev, generator=gen) * 2.0 ** -(k + 2) for _ in range(W)]
+    x, r, x16 = xs[0], rs[0], xs[0].bfloat16()
+    v, d = torch.empty_like(x), torch.empty_like(x)
+    q = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    f = torch.empty(nblk, dtype=torch.uint8, device=dev)
+    kb32 = ops.block_scales([x], V, bits=32)
+    kb16 = ops.block_scales([x], V, bits=16)
+    kb = torch.empty(nblk, dtype=torch.int8, device=dev)
+    hdrs = [torch.zeros((nblk, 16), dtype=torch.uint8, device=dev) for _ in range(W)]
+    pays = [torch.empty((nblk, 4 * V), dtype=torch.uint8, device=dev) for _ in range(W)]
+    key = (V, list(range(1, W + 1)), W, 1, 1)
+
+    def row(run, name, nb_ef, nb_sib, f_ef, f_comp, f_sib):
+        ta, te, tc, tb = _time(f_sib), _time(f_ef), _time(f_comp), _time(f_sib)
+        lo, hi = min(ta, tb), max(ta, tb)
+        rows.append(_row(f"{name} [ef, run {run}]", te, nb_ef, composition_us=round(tc * 1e6, 2),
+                         sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], sibling_spread_us=round((hi - lo) * 1e6, 2),
+                         beats_composition_by_more_than_spread=bool(tc - te > hi - lo),
+                         ratio_to_sibling_x_bytes=round(te / (lo * nb_ef / nb_sib), 3)))
+
+    def comp(src, quant, deq):
+        def run():
+            torch.add(src, r, out=v)
+            quant()
+            deq()
+            torch.sub(v, d, out=r)
+        return run
+
+    def per_worker(quant):
+        def run():
+            for w in range(W):
+                ops.pack_nga_split(quant(w), V, w + 1, W, 1, 1, hdr=hdrs[w], pay=pays[w])
+        return run
+
+    for run in (1, 2):
+        row(run, "quantize fp32 -> int32", 16 * n, 8 * n, lambda: ef.quantize(x, r, k, out=q),
+            comp(x, lambda: ops.quantize(v, k, out=q), lambda: ops.dequantize(q, k, out=d)),
+            lambda: ops.quantize(x, k, out=q))
+        row(run, f"quantize_i16 fp32 -> int16 V={V}", 14 * n, 6 * n,
+            lambda: ef.quantize_i16(x, r, 13, V, out=o16, overflow=f),
+            comp(x, lambda: ops.quantize_i16(v, 13, V, out=o16, overflow=f), lambda: ops.dequantize(o16, 13, out=d)),
+            lambda: ops.quantize_i16(x, 13, V, out=o16, overflow=f))
+        row(run, "quantize bf16 -> int32", 14 * n, 6 * n, lambda: ef.quantize(x16, r, k, out=q),
+            comp(x16, lambda: ops.quantize(v, k, out=q), lambda: ops.dequantize(q, k, out=d)),
+            lambda: ops.quantize(x16, k, out=q))
+        row(run, f"quantize_i16 bf16 -> int16 V={V} (12 B a value; the issue's byte ratio is 10/4)", 10 * n, 4 * n,
+            lambda: ef.quantize_i16(x16, r, 13, V, out=o16, overflow=f),
+            comp(x16, lambda: ops.quantize_i16(v, 13, V, out=o16, overflow=f), lambda: ops.dequantize(o16, 13, out=d)),
+            lambda: ops.quantize_i16(x16, 13, V, out=o16, overflow=f))
+        row(run, f"quantize_blk given V={V}", 16 * n, 8 * n, lambda: ef.quantize_blk(x, r, V, kblk=kb32, out=q),
+            comp(x, lambda: ops.quantize_blk(v, kb32, V, out=q), lambda: ops.dequantize_blk(q, kb32, V, out=d)),
+            lambda: ops.quantize_blk(x, kb32, V, out=q))
+        row(run, f"quantize_blk auto V={V}", 16 * n, 12 * n, lambda: ef.quantize_blk(x, r, V, out=q, kblk_out=kb),
+            comp(x, lambda: ops.quantize_blk(v, ops.block_scales([v], V, degree=1, out=kb), V, out=q),
+                 lambda: ops.dequantize_blk(q, kb, V, out=d)),
+            lambda: ops.quantize_blk(x, ops.block_scales([x], V, degree=1, out=kb), V, out=q))
+        row(run, f"quantize_i16_blk given V={V}", 14 * n, 6 * n,
+            lambda: ef.quantize_i16_blk(x, r, V, kblk=kb16, out=o16, overflow=f),
+            comp(x, lambda: ops.quantize_i16_blk(v, kb16, V, out=o16, overflow=f),
+                 lambda: ops.dequantize_blk(o16, kb16, V, out=d)),
+            lambda: ops.quantize_i16_blk(x, kb16, V, out=o16, overflow=f))
+        row(run, f"quantize_i16_blk auto V={V}", 14 * n, 10 * n,
+            lambda: ef.quantize_i16_blk(x, r, V, out=o16, overflow=f, kblk_out=kb),
+            comp(x, lambda: ops.quantize_i16_blk(v, ops.block_scales([v], V, bits=16, degree=1, out=kb), V, out=o16,
+                                                 overflow=f), lambda: ops.dequantize_blk(o16, kb, V, out=d)),
+            lambda: ops.quantize_i16_blk(x, ops.block_scales([x], V, bits=16, degree=1, out=kb), V, out=o16,
+                                         overflow=f))
+        row(run, f"block_scales W={W} V={V}", 8 * W * n, 4 * W * n, lambda: ef.block_scales(xs, rs, V, out=kb),
+            lambda: ([torch.add(a, b, out=v) for a, b in zip(xs, rs)], ops.block_scales(xs, V, out=kb)),
+            lambda: ops.block_scales(xs, V, out=kb))
+        row(run, f"quantize_pack_nga_multi_split W={W} V={V}", 16 * W * n, 8 * W * n,
+            lambda: ef.quantize_pack_nga_multi_split(xs, rs, k, *key, hdrs=hdrs, pays=pays),
+            per_worker(lambda w: ef.quantize(xs[w], rs[w], k, out=q)),
+            lambda: ops.quantize_pack_nga_multi_split(xs, k, *key, hdrs=hdrs, pays=pays))
+        row(run, f"quantize_pack_nga_multi_split_blk given W={W} V={V}", 16 * W * n, 8 * W * n,
+            lambda: ef.quantize_pack_nga_multi_split(xs, rs, kb32, *key, hdrs=hdrs, pays=pays),
+            per_worker(lambda w: ef.quantize_blk(xs[w], rs[w], V, kblk=kb32, out=q)[0]),
+            lambda: ops.quantize_pack_nga_multi_split_blk(xs, *key, kblk=kb32, hdrs=hdrs, pays=pays))
+        row(run, f"quantize_pack_nga_multi_split_blk auto W={W} V={V}", 16 * W * n, 8 * W * n,
+            lambda: ef.quantize_pack_nga_multi_split(xs, rs, None, *key, kblk_out=kb, hdrs=hdrs, pays=pays),
+            lambda: (ef.block_scales(xs, rs, V, out=kb),
+                     per_worker(lambda w: ef.quantize_blk(xs[w], rs[w], V, kblk=kb, out=q)[0])()),
+            lambda: ops.quantize_pack_nga_multi_split_blk(xs, *key, kblk_out=kb, hdrs=hdrs, pays=pays))
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -846,6 +948,7 @@ def run_extra(dev):
     del hosts, hout, dbuf, b3, o3
     rows += run_x16(dev)
     rows += run_blk(dev)
+    rows += run_ef(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

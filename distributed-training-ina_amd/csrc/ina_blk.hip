@@ -508,12 +508,9 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<X> a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// the vector path's block sizes; shift = log2(V) - 2
-inline bool vec_v(int V, int& shift) {
-    if (V < 8 || V > 256 || log2_exact((uint32_t)V) < 0) return false;
-    shift = log2_exact((uint32_t)V) - 2;
-    return true;
-}
+// (vec_v, the vector path's block sizes, is in ina_internal.h; check_v and check_mode are declared
+// there for ina_ef.hip)
+}  // namespace
 int check_v(int V) { return V < 1 ? set_error(INA_EINVAL, "V must be >= 1%s", "") : INA_OK; }
 int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) {
     lim = 1.0;
@@ -525,6 +522,7 @@ int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) 
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     return INA_OK;
 }
+namespace {
 int launched() { return check_launch("block-scale kernel launch"); }
 
 template <int MODE, bool AUTO, typename X>

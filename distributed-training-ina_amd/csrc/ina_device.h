@@ -158,6 +158,20 @@ __device__ __forceinline__ void write_slot_flags8(unsigned long long m, bool act
     if (active && (lane & (lanes_per_slot - 1)) == 0) ovf[elem0 / (size_t)V] = (m & gm) ? 1 : 0;
 }
 
+// the same for the split layout of the int16 kernels (INA_Q16_SPLIT, ina_kernels.hip: a wave owns
+// 512 values, lane l holds 4 at 4l of each 256-value half): a slot is V/4 adjacent lanes of one
+// half, or both halves at V = 512
+__device__ __forceinline__ void write_slot_flags_split(unsigned long long ma, unsigned long long mb,
+                                                       size_t eA, size_t eB, size_t n, int V,
+                                                       uint8_t* __restrict__ ovf) {
+    if (V >= 512) {
+        write_slot_flags8(ma | mb, eA < n, eA, V, 64, ovf);
+    } else {
+        write_slot_flags8(ma, eA < n, eA, V, V / 4, ovf);
+        write_slot_flags8(mb, eB < n, eB, V, V / 4, ovf);
+    }
+}
+
 static inline bool slot_ballot_ok(int V) {
     if (V % 8) return false;
     int l = V / 8;

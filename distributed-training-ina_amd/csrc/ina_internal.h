@@ -34,6 +34,10 @@ int combine_ina_grid_cap();   // ina_kernels.hip: grid cap of the INA combines, 
 // ina_blk.hip: ina_scale_for's rule for `degree` summands at `bits` (16 or 32): lim = (2^(bits-1) - 1) /
 // degree - 1/2, INA_EINVAL when it is not positive
 int scale_lim(int degree, int bits, double& lim);
+// ina_blk.hip: the block-scaled calls' checks of V (>= 1) and of mode / degree / kblk (lim as above
+// under INA_BLK_AUTO, else 1)
+int check_v(int V);
+int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim);
 int check_x16_type(int xtype);   // ina_x16.hip: INA_OK for INA_X16_BF16 / INA_X16_F16, else INA_EINVAL
 // checked builds (INA_STORE_CHECK, ina_device.h): each source's stream_store contract
 // violations since the last read, cleared by the read
@@ -42,6 +46,7 @@ unsigned long long store_violations_shard();     // ina_shard.hip
 unsigned long long store_violations_switch();    // ina_switch.hip
 unsigned long long store_violations_x16();       // ina_x16.hip
 unsigned long long store_violations_blk();       // ina_blk.hip
+unsigned long long store_violations_ef();        // ina_ef.hip
 
 // ---------------------------------------------------------------------------
 // host helpers
@@ -73,6 +78,14 @@ inline int log2_exact(uint32_t v) {
     int s = 0;
     while ((1u << s) < v) ++s;
     return s;
+}
+
+// the block sizes of the block-scaled vector paths (a power of two in [8, 256]: a block is V/4
+// adjacent lanes of one wave); shift = log2(V) - 2
+inline bool vec_v(int V, int& shift) {
+    if (V < 8 || V > 256 || log2_exact((uint32_t)V) < 0) return false;
+    shift = log2_exact((uint32_t)V) - 2;
+    return true;
 }
 
 inline int check_k(int k) {

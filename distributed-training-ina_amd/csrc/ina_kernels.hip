@@ -124,19 +124,7 @@ __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32
 #ifndef INA_Q16_SPLIT
 #define INA_Q16_SPLIT 1
 #endif
-// the same for the split layout (a wave owns 512 values, lane l holds 4 at 4l of each
-// 256-value half): a slot is V/4 adjacent lanes of one half, or both halves at V = 512
-__device__ __forceinline__ void write_slot_flags_split(unsigned long long ma, unsigned long long mb,
-                                                       size_t eA, size_t eB, size_t n, int V,
-                                                       uint8_t* __restrict__ ovf) {
-    if (V >= 512) {
-        write_slot_flags8(ma | mb, eA < n, eA, V, 64, ovf);
-    } else {
-        write_slot_flags8(ma, eA < n, eA, V, V / 4, ovf);
-        write_slot_flags8(mb, eB < n, eB, V, V / 4, ovf);
-    }
-}
-
+// (write_slot_flags_split, the flags of that layout, is in ina_device.h: ina_ef.hip writes them too)
 
 // Cross-lane moves by one lane are DPP row moves (measured on gfx950, tools/lab/dpp_lab.hip):
 // update_dpp(old, x, 0x130 wave_shl:1) -> lane i reads lane i+1 (lane 63 gets `old`);
@@ -1266,7 +1254,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_split(Src src, size_t n, Ng
 // up to kQpGroup workers' fused quantise(x_w - base) + split pack in one launch: the base
 // chunk loaded once for every worker, each worker's payload stream coalesced.  X: float, or
 // uint16_t for bf16 / fp16 buckets (8-byte worker loads, the base still fp32).
-template <typename X>
+template <typename X, bool EF = false>
 struct QPackRows {
     const X* x[kQpGroup];
     u32x4* hdr[kQpGroup];
@@ -1274,9 +1262,42 @@ struct QPackRows {
     u32x2* desc[kQpGroup];          // all null or all set
     NgaKeys k;
 };
-// Src: SrcQ32, or SrcX16<XT>; its Ld loads and widens the worker chunks.
-template <typename Src, int G>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<typename Src::Ld::X> a, const float* __restrict__ base,
+// EF (include/ina_ef.h): the same rows and each worker's fp32 residual, read and written in place
+template <typename X>
+struct QPackRows<X, true> : QPackRows<X, false> {
+    float* resid[kQpGroup];
+};
+// The error-feedback step of the EF packs on one chunk: v = d + r (d: the worker's delta), and
+// r' = isfinite(v) ? v - float(q) * 2^-k : +0 once the chunk is quantised -- ina_ef.hip's arithmetic.
+__device__ __forceinline__ f32x4 ef_add4(f32x4 d, f32x4 r) {
+    return f32x4{__fadd_rn(d.x, r.x), __fadd_rn(d.y, r.y), __fadd_rn(d.z, r.z), __fadd_rn(d.w, r.w)};
+}
+__device__ __forceinline__ float ef_carry(float v, uint32_t q, float inv) {
+    const bool finite = (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u;
+    return finite ? __fsub_rn(v, __fmul_rn((float)(int32_t)q, inv)) : 0.0f;
+}
+__device__ __forceinline__ f32x4 ef_carry4(f32x4 v, u32x4 q, float inv) {
+    return f32x4{ef_carry(v.x, q.x, inv), ef_carry(v.y, q.y, inv), ef_carry(v.z, q.z, inv), ef_carry(v.w, q.w, inv)};
+}
+// the bucket's last chunk under EF, value by value: the words for the payload (0 past n), residuals
+// updated in place
+__device__ __forceinline__ u32x4 ef_tail4(const float* __restrict__ x, const float* __restrict__ base, float* resid,
+                                          size_t e0, size_t n, float s, float inv) {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (int j = 0; j < 3; ++j) {
+        const size_t e = e0 + j;
+        if (e < n) {
+            const float v = __fadd_rn(base ? __fsub_rn(x[e], base[e]) : x[e], resid[e]);
+            w[j] = (uint32_t)q32(v, s);
+            resid[e] = ef_carry(v, w[j], inv);
+        }
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+// Src: SrcQ32, or SrcX16<XT>; its Ld loads and widens the worker chunks.  EF (fp32 buckets): each
+// worker's residual chunk is one more 16-byte load and one 16-byte write-through store.
+template <typename Src, int G, bool EF = false>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<typename Src::Ld::X, EF> a, const float* __restrict__ base,
                                                                   size_t n, float s, uint32_t num_slots,
                                                                   size_t nch, size_t np) {
     using Ld = typename Src::Ld;
@@ -1284,6 +1305,32 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
     for (size_t t = tid; t < nch; t += gs) {
         const size_t e0 = 4 * t;
+        if constexpr (EF) {
+            // s = 2^k is normal for every k of the ABI: its exponent field gives k, and 2^-k exactly
+            const float inv = pow2f(127 - (int)(__float_as_uint(s) >> 23));
+            if (e0 + 4 <= n) {
+                f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
+                f32x4 x[G], r[G];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    x[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
+                    r[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.resid[g] + e0));
+                }
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const f32x4 v = ef_add4(delta4(x[g], b, base != nullptr), r[g]);
+                    const u32x4 q = quant4(v, s);
+                    packet_store(bswap4(q), a.pay[g] + t);
+                    stream_store(ef_carry4(v, q, inv), reinterpret_cast<f32x4*>(a.resid[g] + e0));
+                }
+            } else {
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    packet_store(bswap4(ef_tail4(a.x[g], base, a.resid[g], e0, n, s, inv)), a.pay[g] + t);
+            }
+            continue;
+        }
         if (e0 + 4 <= n) {
             f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
             if (base) b = *reinterpret_cast<const f32x4*>(base + e0);   // default policy: shared
@@ -1321,8 +1368,10 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
 // is read once.  The loop is wave-uniform (t0 steps whole waves); lanes past the last chunk
 // contribute 0 to the butterfly and store nothing.  Ld: LdF32, or LdX16<XT> for bf16 / fp16 buckets
 // (include/ina_x16_blk.h): 8-byte worker loads widened in registers, the held deltas fp32 either way.
-template <typename Ld, int G, bool AUTO>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<typename Ld::X> a, const float* __restrict__ base,
+// EF (include/ina_ef.h, fp32 buckets): the held chunks are v = delta + r, so AUTO takes the packet's
+// max over |v|, and each worker's r' goes back in place once its chunk is quantised.
+template <typename Ld, int G, bool AUTO, bool EF = false>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<typename Ld::X, EF> a, const float* __restrict__ base,
                                                                       size_t n, int8_t* __restrict__ kblk,
                                                                       double lim, int shift, uint32_t L,
                                                                       uint32_t num_slots, size_t nch, size_t np) {
@@ -1339,7 +1388,19 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
         if constexpr (!AUTO) k = rd_k(kblk, shift >= 0 ? t >> shift : t / L);
         // worker g's chunk of deltas, quantised with 2^kk, into its payload row
         auto put = [&](int g, f32x4 y, int kk) {
-            packet_store(bswap4(quant4(y, pow2f(kk))), a.pay[g] + t);
+            const u32x4 q = quant4(y, pow2f(kk));
+            packet_store(bswap4(q), a.pay[g] + t);
+            if constexpr (EF) {
+                const f32x4 r = ef_carry4(y, q, pow2f(-kk));
+                float* rp = a.resid[g] + e0;
+                if (e0 + 4 <= n) {
+                    stream_store(r, reinterpret_cast<f32x4*>(rp));
+                } else {                               // (at most 3 values of the last chunk)
+                    if (e0 < n) rp[0] = r.x;
+                    if (e0 + 1 < n) rp[1] = r.y;
+                    if (e0 + 2 < n) rp[2] = r.z;
+                }
+            }
         };
         f32x4 d[G];
         if (e0 + 4 <= n) {
@@ -1348,9 +1409,18 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
 #pragma unroll
             for (int g = 0; g < G; ++g)
                 d[g] = Ld::widen4(__builtin_nontemporal_load(reinterpret_cast<const typename Ld::Raw*>(a.x[g] + e0)));
+            [[maybe_unused]] f32x4 r[EF ? G : 1];
+            if constexpr (EF) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) r[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.resid[g] + e0));
+            }
             if (base) {                                // one test for the group, as the held registers were scheduled
 #pragma unroll
                 for (int g = 0; g < G; ++g) d[g] = delta4(d[g], b, true);
+            }
+            if constexpr (EF) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) d[g] = ef_add4(d[g], r[g]);
             }
             if constexpr (!AUTO) {                     // given scales: nothing to wait for
 #pragma unroll
@@ -1362,7 +1432,9 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
                 d[g] = f32x4{0.f, 0.f, 0.f, 0.f};
                 auto one = [&](size_t e) {
                     const float x = Ld::widen1(a.x[g][e]);
-                    return base ? __fsub_rn(x, base[e]) : x;
+                    const float y = base ? __fsub_rn(x, base[e]) : x;
+                    if constexpr (EF) return __fadd_rn(y, a.resid[g][e]);
+                    else return y;
                 };
                 if (e0 < n) d[g].x = one(e0);
                 if (e0 + 1 < n) d[g].y = one(e0 + 1);
@@ -2055,34 +2127,46 @@ static int check_multi_split(const X* const* x, int W, const float* base, size_t
     }
     return INA_OK;
 }
-// workers [w0, w0 + G) of a split multi call as one kernel argument
-template <typename X, typename XV>
-static QPackRows<X> fill_rows(int w0, int G, const XV* const* x, const ina_nga_params_t* prm, uint8_t* const* hdr,
-                              uint8_t* const* pay, ina_nga_desc_t* const* desc) {
-    QPackRows<X> a{};
+// the EF packs' residuals (include/ina_ef.h): W device pointers, 16-byte aligned like the buckets
+static int check_resid(float* const* resid, int W) {
+    if (!resid) return set_error(INA_EINVAL, "null resid%s", "");
+    for (int w = 0; w < W; ++w) {
+        if (!resid[w]) return set_error(INA_EINVAL, "null resid%s", "");
+        if (!aligned16(resid[w])) return set_error(INA_EINVAL, "worker buffers and rows must be 16-byte aligned%s", "");
+    }
+    return INA_OK;
+}
+// workers [w0, w0 + G) of a split multi call as one kernel argument (EF: with their residuals)
+template <typename X, bool EF = false, typename XV>
+static QPackRows<X, EF> fill_rows(int w0, int G, const XV* const* x, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                  uint8_t* const* pay, ina_nga_desc_t* const* desc, float* const* resid = nullptr) {
+    QPackRows<X, EF> a{};
     for (int g = 0; g < G; ++g) {
         a.x[g] = static_cast<const X*>(x[w0 + g]);
         a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
         a.pay[g] = reinterpret_cast<u32x4*>(pay[w0 + g]);
         a.desc[g] = desc ? reinterpret_cast<u32x2*>(desc[w0 + g]) : nullptr;
+        if constexpr (EF) a.resid[g] = resid[w0 + g];
         fill_keys(a.k, g, prm[w0 + g]);
     }
     return a;
 }
 // the fp32 and 16-bit split multi packs: groups of up to kQpGroup workers, a launch each
-template <typename Src, typename XV>
+// (EF: resid checked by the caller; the grid under the default cap, tuning key 0)
+template <typename Src, bool EF = false, typename XV>
 static int qpack_multi_split(const char* what, const XV* const* x, int W, const float* base, size_t n, int k,
                              const ina_nga_params_t* prm, uint8_t* const* hdr, uint8_t* const* pay,
-                             ina_nga_desc_t* const* desc, size_t npk, ina_stream_t stream) {
+                             ina_nga_desc_t* const* desc, size_t npk, ina_stream_t stream,
+                             float* const* resid = nullptr) {
     using X = typename Src::Ld::X;
     const float sc = ldexpf(1.0f, k);
     const size_t nch = npk * (size_t)prm[0].V / 4;
-    const dim3 grid(grid_for(std::max(nch, npk), 1, ew_grid_cap())), blk(kBlock);
+    const dim3 grid(grid_for(std::max(nch, npk), 1, EF ? 0 : ew_grid_cap())), blk(kBlock);
     for (int w0 = 0; w0 < W; w0 += kQpGroup) {
         const int G = std::min(kQpGroup, W - w0);
-        const QPackRows<X> a = fill_rows<X>(w0, G, x, prm, hdr, pay, desc);
+        const QPackRows<X, EF> a = fill_rows<X, EF>(w0, G, x, prm, hdr, pay, desc, resid);
         with_group(G, [&](auto g) {
-            hipLaunchKernelGGL((k_qpack_nga_multi_split<Src, g.value>), grid, blk, 0, hs(stream), a, base, n, sc,
+            hipLaunchKernelGGL((k_qpack_nga_multi_split<Src, g.value, EF>), grid, blk, 0, hs(stream), a, base, n, sc,
                                prm[0].num_slots, nch, npk);
         });
     }
@@ -2090,10 +2174,12 @@ static int qpack_multi_split(const char* what, const XV* const* x, int W, const 
 }
 
 // the fp32 and 16-bit block-scaled split multi packs (xtype: 0 for fp32 buckets)
-template <typename Ld, typename XV>
+// EF (fp32 buckets): with the workers' residuals; AUTO's two-step route takes its scales over |v|
+template <typename Ld, bool EF = false, typename XV>
 static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype, int W, const float* base, size_t n,
                                  int8_t* kblk, int mode, int degree, const ina_nga_params_t* prm, uint8_t* const* hdr,
-                                 uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
+                                 uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream,
+                                 float* const* resid = nullptr) {
     using X = typename Ld::X;
     if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
         return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
@@ -2104,6 +2190,9 @@ static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype
     size_t npk;
     if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, true, kblk, npk)) return rc;
     if (npk == 0) return INA_OK;
+    if constexpr (EF) {
+        if (int rc = check_resid(resid, W)) return rc;
+    }
     const int V = prm[0].V;
     const uint32_t L = (uint32_t)V / 4;
     const int shift = log2_exact(L);                   // -1: L is no power of two
@@ -2113,7 +2202,8 @@ static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype
     // the pack reads what it wrote -- the same scales, so the same rows
     if (autok && !(shift >= 1 && W <= kQpGroup)) {
         int rc;
-        if constexpr (std::is_same_v<X, float>) rc = ina_block_scales_f32(x, W, base, n, V, degree, 32, kblk, stream);
+        if constexpr (EF) rc = ina_block_scales_ef_f32(x, resid, W, base, n, V, degree, 32, kblk, stream);
+        else if constexpr (std::is_same_v<X, float>) rc = ina_block_scales_f32(x, W, base, n, V, degree, 32, kblk, stream);
         else rc = ina_block_scales_x16(x, xtype, W, base, n, V, degree, 32, kblk, stream);
         if (rc) return rc;
         autok = false;
@@ -2124,10 +2214,10 @@ static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype
     const dim3 grid(grid_for(std::max(nch, npk), 1)), blk(kBlock);
     for (int w0 = 0; w0 < W; w0 += kQpGroup) {
         const int G = std::min(kQpGroup, W - w0);
-        const QPackRows<X> a = fill_rows<X>(w0, G, x, prm, hdr, pay, desc);
+        const QPackRows<X, EF> a = fill_rows<X, EF>(w0, G, x, prm, hdr, pay, desc, resid);
         with_group(G, [&](auto g) {
-            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<Ld, g.value, true>
-                                 : &k_qpack_nga_multi_split_blk<Ld, g.value, false>;
+            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<Ld, g.value, true, EF>
+                                 : &k_qpack_nga_multi_split_blk<Ld, g.value, false, EF>;
             hipLaunchKernelGGL(kernel, grid, blk, 0, hs(stream), a, base, n, kblk, lim, shift, L, prm[0].num_slots,
                                nch, npk);
         });
@@ -2697,6 +2787,27 @@ int ina_quantize_pack_nga_multi_split_blk_x16(const void* const* x, int xtype, i
                                                      stream);
 }
 
+// ---- error feedback on the split worker packs (include/ina_ef.h; the quantisers are in ina_ef.hip) ----
+int ina_quantize_pack_nga_multi_split_ef(const float* const* x, float* const* resid, int W, const float* base,
+                                         size_t n, int k, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                         uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream) {
+    if (int rc = check_k(k)) return rc;
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, false, nullptr, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    if (int rc = check_resid(resid, W)) return rc;
+    return qpack_multi_split<SrcQ32, true>("quantize_pack_nga_multi_split_ef", x, W, base, n, k, prm, hdr, pay, desc, npk,
+                                           stream, resid);
+}
+
+int ina_quantize_pack_nga_multi_split_ef_blk(const float* const* x, float* const* resid, int W, const float* base,
+                                             size_t n, int8_t* kblk, int mode, int degree,
+                                             const ina_nga_params_t* prm, uint8_t* const* hdr, uint8_t* const* pay,
+                                             ina_nga_desc_t* const* desc, ina_stream_t stream) {
+    return qpack_multi_split_blk<LdF32, true>("quantize_pack_nga_multi_split_ef_blk", x, 0, W, base, n, kblk, mode,
+                                              degree, prm, hdr, pay, desc, stream, resid);
+}
+
 int ina_apply_completed_nga_blk(const uint8_t* rows, const uint8_t* pay, size_t npk, int V, size_t pstride,
                                 const uint8_t* actions, uint32_t seq0, const float* local, const int8_t* kblk,
                                 double weight_step, float* out, size_t n, uint8_t* acks, size_t ack_stride,
@@ -2832,7 +2943,7 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (!count) return INA_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
-             ina::store_violations_x16() + ina::store_violations_blk();
+             ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_ef();
     return INA_OK;
 }
 #endif

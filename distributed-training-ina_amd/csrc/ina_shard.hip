@@ -259,12 +259,7 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_scalar(const int32
 
 inline bool al(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }
 
-// the vector path's block sizes: V a power of two in [8, 256]; shift = log2(V) - 2
-inline bool vec_v(int V, int& shift) {
-    if (V < 8 || V > 256 || log2_exact((uint32_t)V) < 0) return false;
-    shift = log2_exact((uint32_t)V) - 2;
-    return true;
-}
+// (vec_v, the vector path's block sizes, is in ina_internal.h)
 
 }  // namespace
 }  // namespace ina

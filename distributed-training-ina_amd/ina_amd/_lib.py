@@ -166,6 +166,18 @@ SIGNATURES_BLK_X16 = {
     "ina_dequantize_blk_i16_x16": [_vp, _vp, _i, _vp, _i, _sz, _vp],
     "ina_quantize_pack_nga_multi_split_blk_x16": [_vp, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
 }
+# error feedback (include/ina_ef.h): the residual follows the base (the packs: the buckets)
+SIGNATURES_EF = {
+    "ina_quantize_ef_f32_i32": [_vp, _vp, _vp, _vp, _sz, _i, _vp],
+    "ina_quantize_ef_f32_i16_sat": [_vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp],
+    "ina_quantize_ef_x16_i32": [_vp, _i, _vp, _vp, _vp, _sz, _i, _vp],
+    "ina_quantize_ef_x16_i16_sat": [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp],
+    "ina_block_scales_ef_f32": [_vp, _vp, _i, _vp, _sz, _i, _i, _i, _vp, _vp],
+    "ina_quantize_ef_blk_f32_i32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp],
+    "ina_quantize_ef_blk_f32_i16_sat": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp],
+    "ina_quantize_pack_nga_multi_split_ef": [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp],
+    "ina_quantize_pack_nga_multi_split_ef_blk": [_vp, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -181,7 +193,8 @@ def open_library(path: str) -> C.CDLL:
         raise InaError(f"libina.so not built at {path}; run `make -C {CSRC}` or __graft_entry__.build()")
     lib = C.CDLL(path)
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
-                       **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16}.items():
+                       **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
+                       **SIGNATURES_EF}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

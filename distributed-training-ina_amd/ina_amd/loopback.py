@@ -23,7 +23,7 @@ import time
 
 import torch
 
-from . import _lib, control, ops, ps
+from . import _lib, control, ef, ops, ps
 from .nic import PacketRing, send_device_packets
 
 
@@ -100,11 +100,22 @@ class SwitchStandIn:
 
 
 def worker_send(sock, params: torch.Tensor, base: torch.Tensor, worker_id: int, W: int, V: int,
-                k, seq0: int, switch_id: int = 1, num_slots: int = _lib.NUM_REGISTER) -> int:
+                k, seq0: int, switch_id: int = 1, num_slots: int = _lib.NUM_REGISTER,
+                residual: torch.Tensor | None = None) -> int:
     """Worker data plane: quantise(params - base) + NGA-V pack in one GPU pass, then
     sendmmsg.  num_slots must be the aggregator's pool size (index = seq mod num_slots,
     DataManager.py:119).  k: the global exponent, or an int8 tensor of one exponent per packet
-    (agree_block_scales)."""
+    (agree_block_scales).  residual: the worker's error-feedback buffer (ef.new_residual), added
+    before the quantiser and updated in place (include/ina_ef.h) -- the EF quantiser, then the
+    pack: two launches, in a flow the socket bounds."""
+    if residual is not None:
+        x, b = params.reshape(-1).contiguous(), base.reshape(-1).contiguous()
+        if isinstance(k, torch.Tensor):
+            q, _ = ef.quantize_blk(x, residual, V, kblk=k, base=b)
+        else:
+            q = ef.quantize(x, residual, k, base=b)
+        pk = ops.pack_nga(q, V, bitmap=worker_id, count=W, switch_id=switch_id, seq0=seq0, num_slots=num_slots)
+        return send_device_packets(sock, pk, _lib.NGA_HDR_BYTES + 4 * V)
     pack = ops.quantize_pack_nga_blk if isinstance(k, torch.Tensor) else ops.quantize_pack_nga
     pk = pack(params.reshape(-1).contiguous(), k, V, bitmap=worker_id, count=W,
               switch_id=switch_id, seq0=seq0, base=base.reshape(-1).contiguous(),
@@ -186,8 +197,11 @@ def ps_serve(model, W: int, epochs: int, tcp_port: int, data_path: str, k=16,
 
 
 def worker_serve(idx: int, W: int, tcp_port: int, data_path: str, make_model, train_step,
-                 device="cuda"):
-    """Worker side (worker_loop, launch.py:248-322, with the INA data plane)."""
+                 device="cuda", error_feedback: bool = False):
+    """Worker side (worker_loop, launch.py:248-322, with the INA data plane).  error_feedback: the
+    worker keeps what its quantiser dropped in one residual buffer across the epochs and adds it to
+    the next update (include/ina_ef.h); under k = "block" the scales it offers are those of update +
+    residual."""
     ctl = socket.create_connection(("127.0.0.1", tcp_port))
     data = socket.socket(socket.AF_UNIX, socket.SOCK_DGRAM)
     data.connect(data_path)
@@ -198,14 +212,17 @@ def worker_serve(idx: int, W: int, tcp_port: int, data_path: str, make_model, tr
         glob = cfg["para"].to(device)
         torch.nn.utils.vector_to_parameters(glob, model.parameters())
         npk = -(-glob.numel() // V)
+        resid = ef.new_residual(glob) if error_feedback else None
         for epoch in range(epochs):
             train_step(model, idx, epoch)
             p = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
             ke = k
             if k == "block":
-                ke = agree_block_scales(ctl, ops.block_scales([p], V, bits=32, degree=W, base=glob))
+                mine = (ef.block_scales([p], [resid], V, bits=32, degree=W, base=glob) if error_feedback
+                        else ops.block_scales([p], V, bits=32, degree=W, base=glob))
+                ke = agree_block_scales(ctl, mine)
             worker_send(data, p, glob, idx + 1, W, V, ke, seq_base(epoch, npk),
-                        num_slots=cfg["num_slots"])
+                        num_slots=cfg["num_slots"], residual=resid)
             glob = ps.get_data(ctl).to(device)
             torch.nn.utils.vector_to_parameters(glob, model.parameters())
     finally:

@@ -97,7 +97,7 @@ def _worker(idx, W, port, path, args):
     ARGS = args
     sys.path.insert(0, os.path.join(REPO, "distributed-training-ina_amd"))
     from ina_amd.loopback import worker_serve
-    worker_serve(idx, W, port, path, ResNet50, train_step)
+    worker_serve(idx, W, port, path, ResNet50, train_step, error_feedback=args.error_feedback)
 
 
 def main():
@@ -111,6 +111,8 @@ def main():
     ap.add_argument("--k", type=lambda v: v if v == "block" else int(v), default=16,
                     help="the quantiser's global exponent, or 'block': one exponent per packet, "
                          "agreed by the workers each epoch")
+    ap.add_argument("--error-feedback", action="store_true",
+                    help="each worker keeps what its quantiser dropped and adds it to its next update")
     ARGS = args = ap.parse_args()
     from ina_amd.loopback import ps_serve
     torch.manual_seed(0)

@@ -492,6 +492,10 @@ int ina_recv_packets_split_fd(int fd, uint8_t* host_hdr, uint8_t* host_pay, size
 int ina_recv_packets_fd(int fd, uint8_t* host_pkts, size_t max_pkts, size_t stride, size_t skip,
                         int timeout_ms, uint32_t* lens);
 
+/* Error feedback: the quantisers and the split worker packs with a residual carried on the device
+ * from step to step; the contract is stated in ina_ef.h. */
+#include "ina_ef.h"   /* the ina_quantize_ef_* / ina_*_ef entry points */
+
 /* Per-block scales for bf16 / fp16 buckets (scales, quantisers, fused reduces, decode, the
  * one-launch worker pack); the contract is stated in ina_x16_blk.h, included last. */
 #include "ina_x16_blk.h"

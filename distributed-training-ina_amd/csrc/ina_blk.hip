@@ -35,13 +35,19 @@
 // differ; a lane still owns 4 values, a block is still V/4 lanes, and everything after the load is
 // the fp32 kernel's code on the widened chunk, so held chunks cost the fp32 kernel's registers.
 // The vector path needs the 16-bit side 8-byte aligned.
+//
+// Error feedback (include/ina_ef.h; entry points in ina_ef.hip): the same kernels at W = 1 with the
+// SrcEf value source, which reads v = (x - base) + r where the plain source reads x and stores r'
+// once v is quantised, and a third scale mode, the call's one k.  No kernel of its own.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "ina.h"
 #include "ina_internal.h"
 #include "ina_device.h"
+#include "ina_chunk.h"
 
 namespace ina {
 
@@ -56,136 +62,54 @@ int scale_lim(int degree, int bits, double& lim) {
 
 namespace {
 
-using u32x4 = u32x4_t;
-using u32x2 = u32x2_t;
-using f32x4 = f32x4_t;
-
 constexpr int kBlk = 256;
 
-// ---------------------------------------------------------------------------
-// scales
-// ---------------------------------------------------------------------------
-// (rd_k, pow2f, absbits, umax, fold4, scale_of and group_max are in ina_device.h: the block-scaled
-// packet kernels of ina_kernels.hip run the same ones)
-__device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
-    return f32x4{__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z), __fsub_rn(a.w, b.w)};
-}
+// (rd_k, pow2f, absbits, umax, fold4, scale_of and group_max are in ina_device.h, a lane's chunk of
+// 4 values -- ld4, st4, q32x4, ... -- in ina_chunk.h: the block-scaled packet kernels of
+// ina_kernels.hip run the same ones)
 
 // ---------------------------------------------------------------------------
-// a lane's chunk of 4 values at element e; a chunk that crosses n is read and written value by
-// value (values past n read as 0)
+// Value sources: what the quantising kernels read as worker w's chunk (four) or value (one) at an
+// element.  X: the element type of a call's buckets -- float, or h16<XT>.
 // ---------------------------------------------------------------------------
-// (X below: the element type of a call's buckets -- float, or h16<XT>, one bf16 / fp16 value)
-template <int XT>
-struct h16 {
-    uint16_t v;
+template <typename X>
+struct SrcPlain {
+    static constexpr bool kEf = false;
+    using Elem = X;
+    PtrPack<X> in;
+    __device__ __forceinline__ f32x4 four(int w, size_t e, size_t n) const { return ld4(in.p[w], e, n); }
+    __device__ __forceinline__ float one(int w, size_t j) const { return ld1(in.p[w], j); }
+    __device__ __forceinline__ void carry(int, f32x4, u32x4, float, size_t, size_t) const {}
+    __device__ __forceinline__ void carry1(int, float, int32_t, float, size_t) const {}
 };
-template <bool NT = true>
-__device__ __forceinline__ f32x4 ld4(const float* p, size_t e, size_t n) {
-    if (e + 4 <= n) {
-        if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + e));
-        else return *reinterpret_cast<const f32x4*>(p + e);
+// Error feedback (include/ina_ef.h): the value is v = (x - base) + r, and once it is quantised to q
+// the kernel hands it back (carry) for r' = v - float(q) * 2^-k to go where r was.  A lane reads its
+// r before it writes r' and no other lane touches those 16 bytes, so the update is in place.  x and
+// r are read once (non-temporal), the base is shared between a step's calls (default policy, as in
+// the packs).  N pointer pairs: 1 for the quantisers, INA_MAX_WORKERS for the scales.
+template <typename X, int N>
+struct SrcEf {
+    static constexpr bool kEf = true;
+    using Elem = X;
+    const X* x[N];
+    float* resid[N];
+    const float* base;     // may be null
+    __device__ __forceinline__ f32x4 four(int w, size_t e, size_t n) const {
+        if (e >= n) return f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 a = ld4(x[w], e, n), r = ld4(resid[w], e, n);
+        return ef_v4(base ? sub4(a, ld4<false>(base, e, n)) : a, r);
     }
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (e < n) v.x = p[e];
-    if (e + 1 < n) v.y = p[e + 1];
-    if (e + 2 < n) v.z = p[e + 2];
-    return v;
-}
-// a bf16 / fp16 bucket (include/ina_x16_blk.h): one 8-byte load, widened in registers (exact)
-template <int XT>
-__device__ __forceinline__ f32x4 ld4(const h16<XT>* p, size_t e, size_t n) {
-    if (e + 4 <= n) return widen16x4<XT>(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + e)));
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (e < n) v.x = widen16<XT>(p[e].v);
-    if (e + 1 < n) v.y = widen16<XT>(p[e + 1].v);
-    if (e + 2 < n) v.z = widen16<XT>(p[e + 2].v);
-    return v;
-}
-// one value of a bucket, and one decoded value into one (16-bit: rounded once to nearest even)
-__device__ __forceinline__ float ld1(const float* p, size_t j) { return p[j]; }
-template <int XT>
-__device__ __forceinline__ float ld1(const h16<XT>* p, size_t j) { return widen16<XT>(p[j].v); }
-__device__ __forceinline__ void st1(float v, float* p, size_t j) { p[j] = v; }
-template <int XT>
-__device__ __forceinline__ void st1(float v, h16<XT>* p, size_t j) { p[j].v = (uint16_t)rne16<XT>(v); }
-__device__ __forceinline__ u32x4 ld4i(const int32_t* p, size_t e, size_t n) {
-    if (e + 4 <= n) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + e));
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (e < n) v.x = (uint32_t)p[e];
-    if (e + 1 < n) v.y = (uint32_t)p[e + 1];
-    if (e + 2 < n) v.z = (uint32_t)p[e + 2];
-    return v;
-}
-// 4 int16 values, sign-extended
-__device__ __forceinline__ u32x4 ld4h(const int16_t* p, size_t e, size_t n) {
-    if (e + 4 <= n) {
-        const u32x2 h = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + e));
-        return u32x4{(uint32_t)(int32_t)(int16_t)(h.x & 0xFFFFu), (uint32_t)((int32_t)h.x >> 16),
-                     (uint32_t)(int32_t)(int16_t)(h.y & 0xFFFFu), (uint32_t)((int32_t)h.y >> 16)};
+    __device__ __forceinline__ float one(int w, size_t j) const {
+        const float a = ld1(x[w], j);
+        return ef_v(base ? __fsub_rn(a, base[j]) : a, resid[w][j]);
     }
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (e < n) v.x = (uint32_t)(int32_t)p[e];
-    if (e + 1 < n) v.y = (uint32_t)(int32_t)p[e + 1];
-    if (e + 2 < n) v.z = (uint32_t)(int32_t)p[e + 2];
-    return v;
-}
-// (the element is passed by value: __builtin_bit_cast applied to a vector element itself reads
-// element 0 whichever is named)
-template <typename T, typename S>
-__device__ __forceinline__ T bits_as(S s) {
-    return __builtin_bit_cast(T, s);
-}
-template <typename V4, typename T>
-__device__ __forceinline__ void st4(V4 v, T* p, size_t e, size_t n) {
-    static_assert(sizeof(V4) == 4 * sizeof(T), "4 values");
-    if (e + 4 <= n) {
-        stream_store(v, reinterpret_cast<V4*>(p + e));
-    } else {
-        if (e < n) p[e] = bits_as<T>(v.x);
-        if (e + 1 < n) p[e + 1] = bits_as<T>(v.y);
-        if (e + 2 < n) p[e + 2] = bits_as<T>(v.z);
+    __device__ __forceinline__ void carry(int w, f32x4 v, u32x4 q, float inv, size_t e, size_t n) const {
+        st4(ef_r4(v, q, inv), resid[w], e, n);
     }
-}
-// 4 decoded values into a 16-bit buffer: one 8-byte store
-template <int XT>
-__device__ __forceinline__ void st4(f32x4 v, h16<XT>* p, size_t e, size_t n) {
-    if (e + 4 <= n) {
-        stream_store(u32x2{rne16x2<XT>(v.x, v.y), rne16x2<XT>(v.z, v.w)}, reinterpret_cast<u32x2*>(p + e));
-    } else {
-        if (e < n) st1(v.x, p, e);
-        if (e + 1 < n) st1(v.y, p, e + 1);
-        if (e + 2 < n) st1(v.z, p, e + 2);
+    __device__ __forceinline__ void carry1(int w, float v, int32_t q, float inv, size_t j) const {
+        resid[w][j] = ef_r(v, q, inv);
     }
-}
-// 4 int16 (held widened) as one 8-byte store
-__device__ __forceinline__ void st4h(const int32_t* a, int16_t* p, size_t e, size_t n) {
-    if (e + 4 <= n) {
-        u32x2 o;
-        o.x = (uint32_t)(uint16_t)a[0] | ((uint32_t)a[1] << 16);
-        o.y = (uint32_t)(uint16_t)a[2] | ((uint32_t)a[3] << 16);
-        stream_store(o, reinterpret_cast<u32x2*>(p + e));
-    } else {
-        for (int j = 0; j < 3; ++j)
-            if (e + j < n) p[e + j] = (int16_t)a[j];
-    }
-}
-
-__device__ __forceinline__ u32x4 q32x4(f32x4 v, float s) {
-    return u32x4{(uint32_t)q32(v.x, s), (uint32_t)q32(v.y, s), (uint32_t)q32(v.z, s), (uint32_t)q32(v.w, s)};
-}
-__device__ __forceinline__ void q16x4_add(f32x4 v, float s, int32_t* a, bool& sat) {
-    a[0] += q16(v.x, s, sat); a[1] += q16(v.y, s, sat); a[2] += q16(v.z, s, sat); a[3] += q16(v.w, s, sat);
-}
-__device__ __forceinline__ f32x4 deq4(u32x4 q, float inv) {
-    return f32x4{__fmul_rn((float)(int32_t)q.x, inv), __fmul_rn((float)(int32_t)q.y, inv),
-                 __fmul_rn((float)(int32_t)q.z, inv), __fmul_rn((float)(int32_t)q.w, inv)};
-}
-// local + ws * y, the PS update's unfused fp32 sequence
-__device__ __forceinline__ f32x4 upd4(f32x4 l, f32x4 y, float ws) {
-    return f32x4{__fadd_rn(l.x, __fmul_rn(y.x, ws)), __fadd_rn(l.y, __fmul_rn(y.y, ws)),
-                 __fadd_rn(l.z, __fmul_rn(y.z, ws)), __fadd_rn(l.w, __fmul_rn(y.w, ws))};
-}
+};
 
 // ---------------------------------------------------------------------------
 // vector path, 32-bit side: chunk i = values 4i..4i+3, block of chunk i = i >> shift
@@ -197,9 +121,10 @@ __device__ __forceinline__ f32x4 upd4(f32x4 l, f32x4 y, float ws) {
     const size_t stride_ = (size_t)gridDim.x * kBlk;                               \
     for (size_t base_ = tid_ & ~(size_t)63; base_ < (nq); base_ += stride_)
 
-// scales alone: W + 1 streams, 4 workers' loads in flight (k_absmax_multi_f32's loop)
-template <typename X>
-__global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<X> xs, int W, const float* __restrict__ base,
+// scales alone: W + 1 streams, 4 workers' loads in flight (k_absmax_multi_f32's loop).  (An EF source
+// brings its own base and residuals, 2W + 1 streams; `base` is then null.)
+template <typename Src>
+__global__ __launch_bounds__(kBlk) void k_blk_scales(Src xs, int W, const float* __restrict__ base,
                                                      size_t n, int shift, double lim,
                                                      int8_t* __restrict__ kblk) {
     const size_t nq = (n + 3) / 4;
@@ -213,11 +138,11 @@ __global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<X> xs, int W, const
             for (; w + 4 <= W; w += 4) {
                 f32x4 a[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) a[u] = ld4(xs.p[w + u], e, n);
+                for (int u = 0; u < 4; ++u) a[u] = xs.four(w + u, e, n);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) m = fold4(m, sub4(a[u], b));
             }
-            for (; w < W; ++w) m = fold4(m, sub4(ld4(xs.p[w], e, n), b));
+            for (; w < W; ++w) m = fold4(m, sub4(xs.four(w, e, n), b));
         }
         m = group_max(m, 1 << shift);
         if (e < n && (lane & ((1 << shift) - 1)) == 0) kblk[i >> shift] = (int8_t)scale_of(m, lim);
@@ -225,45 +150,61 @@ __global__ __launch_bounds__(kBlk) void k_blk_scales(PtrPack<X> xs, int W, const
 }
 
 // fused quantise + W-way reduce to int32 (W = 1: the plain quantiser).  W > 0: compile-time worker
-// count, chunks held in registers; W = 0: runtime count, re-read under AUTO.
-template <typename X, int W, bool AUTO>
-__global__ __launch_bounds__(kBlk) void k_qr_blk_i32(PtrPack<X> in, int Wd, int8_t* __restrict__ kblk,
+// count, chunks held in registers; W = 0: runtime count, re-read under AUTO.  KM, where a block's k
+// comes from: K_GLOBAL (the call's kg for every block; the EF calls only), K_GIVEN (kblk read),
+// K_AUTO (the block's max |value|, kblk written).
+template <typename Src, int W, int KM>
+__global__ __launch_bounds__(kBlk) void k_qr_blk_i32(Src in, int Wd, int kg, int8_t* __restrict__ kblk,
                                                      double lim, int32_t* out, size_t n, int shift) {
+    constexpr bool AUTO = KM == K_AUTO;
+    static_assert(!Src::kEf || W == 1, "one residual: one bucket");
     const int nw = W > 0 ? W : Wd;
-    constexpr bool HOLD = AUTO && W > 0;      // given scales: a chunk is quantised as it arrives
+    // given scales: a chunk is quantised as it arrives (an EF source: held, so that its three loads
+    // are in flight beside the scale's and not behind it)
+    constexpr bool HOLD = (AUTO && W > 0) || Src::kEf;
     constexpr int UNR = W > 0 ? W : 1;
     const size_t nq = (n + 3) / 4;
     const int lane = threadIdx.x & 63;
     INA_BLK_QUAD_LOOP(nq) {
         const size_t i = base_ + lane, e = 4 * i;
+        if constexpr (Src::kEf && !AUTO) {
+            if (e >= n) continue;                  // no cross-lane step below: the loads wait once
+        }
         [[maybe_unused]] f32x4 v[HOLD ? W : 1];
         if constexpr (HOLD) {
 #pragma unroll
-            for (int w = 0; w < W; ++w) v[w] = ld4(in.p[w], e, n);
+            for (int w = 0; w < W; ++w) v[w] = in.four(w, e, n);
         }
-        int k = 0;
+        int k = KM == K_GLOBAL ? kg : 0;
         if constexpr (AUTO) {
             uint32_t m = 0u;
             if constexpr (HOLD) {
 #pragma unroll
                 for (int w = 0; w < W; ++w) m = fold4(m, v[w]);
             } else {
-                for (int w = 0; w < nw; ++w) m = fold4(m, ld4(in.p[w], e, n));
+                for (int w = 0; w < nw; ++w) m = fold4(m, in.four(w, e, n));
             }
             m = group_max(m, 1 << shift);
             k = scale_of(m, lim);
             if (e < n && (lane & ((1 << shift) - 1)) == 0) kblk[i >> shift] = (int8_t)k;
-        } else {
+        } else if constexpr (KM == K_GIVEN) {
             if (e < n) k = rd_k(kblk, i >> shift);
         }
         const float s = pow2f(k);
+        [[maybe_unused]] const float inv = pow2f(-k);         // the EF carry's
         u32x4 acc = {0u, 0u, 0u, 0u};
+        // worker w's chunk: quantised, summed, and handed back to the source
+        auto add = [&](int w, f32x4 x) {
+            const u32x4 q = q32x4(x, s);
+            acc += q;
+            in.carry(w, x, q, inv, e, n);
+        };
         if constexpr (HOLD) {
 #pragma unroll
-            for (int w = 0; w < W; ++w) acc += q32x4(v[w], s);
+            for (int w = 0; w < W; ++w) add(w, v[w]);
         } else {
 #pragma unroll UNR
-            for (int w = 0; w < nw; ++w) acc += q32x4(ld4(in.p[w], e, n), s);
+            for (int w = 0; w < nw; ++w) add(w, in.four(w, e, n));
         }
         if (e < n) st4(acc, out, e, n);
     }
@@ -349,12 +290,17 @@ template <>
 struct Out16<float> {
     using P = int16_t* __restrict__;
 };
-template <typename X, int W, bool AUTO>
-__global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8_t* __restrict__ kblk,
-                                                     double lim, typename Out16<X>::P out, size_t n, int shift,
+// (an EF source holds its chunks under every KM, as above: and both halves' loads are issued before
+// the first r' store, which they may not pass.  K_GLOBAL: V is any size with a ballot layout, up to a slot of both
+// halves at 512, and shift is unused)
+template <typename Src, int W, int KM>
+__global__ __launch_bounds__(kBlk) void k_qr_blk_i16(Src in, int Wd, int kg, int8_t* __restrict__ kblk, double lim,
+                                                     typename Out16<typename Src::Elem>::P out, size_t n, int shift,
                                                      int V, uint8_t* __restrict__ ovf) {
+    constexpr bool AUTO = KM == K_AUTO;
+    static_assert(!Src::kEf || W == 1, "one residual: one bucket");
     const int nw = W > 0 ? W : Wd;
-    constexpr bool HOLD = AUTO && W > 0;
+    constexpr bool HOLD = (AUTO && W > 0) || Src::kEf;
     constexpr int UNR = W > 0 ? W : 1;
     const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
     const size_t nwaves = ((size_t)gridDim.x * kBlk) >> 6;
@@ -366,11 +312,11 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8
         if constexpr (HOLD) {
 #pragma unroll
             for (int w = 0; w < W; ++w) {
-                u[w] = ld4(in.p[w], eA, n);
-                v[w] = ld4(in.p[w], eB, n);
+                u[w] = in.four(w, eA, n);
+                v[w] = in.four(w, eB, n);
             }
         }
-        int kA = 0, kB = 0;
+        int kA = KM == K_GLOBAL ? kg : 0, kB = kA;
         if constexpr (AUTO) {
             uint32_t mA = 0u, mB = 0u;
             if constexpr (HOLD) {
@@ -381,8 +327,8 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8
                 }
             } else {
                 for (int w = 0; w < nw; ++w) {
-                    mA = fold4(mA, ld4(in.p[w], eA, n));
-                    mB = fold4(mB, ld4(in.p[w], eB, n));
+                    mA = fold4(mA, in.four(w, eA, n));
+                    mB = fold4(mB, in.four(w, eB, n));
                 }
             }
             mA = group_max(mA, lanes);
@@ -393,11 +339,12 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8
                 if (eA < n) kblk[eA >> (shift + 2)] = (int8_t)kA;
                 if (eB < n) kblk[eB >> (shift + 2)] = (int8_t)kB;
             }
-        } else {
+        } else if constexpr (KM == K_GIVEN) {
             if (eA < n) kA = rd_k(kblk, eA >> (shift + 2));
             if (eB < n) kB = rd_k(kblk, eB >> (shift + 2));
         }
         const float sA = pow2f(kA), sB = pow2f(kB);
+        [[maybe_unused]] const float invA = pow2f(-kA), invB = pow2f(-kB);   // the EF carry's
         bool sa = false, sb = false;
         int32_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
         if constexpr (HOLD) {
@@ -409,21 +356,33 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8
         } else {
 #pragma unroll UNR
             for (int w = 0; w < nw; ++w) {
-                q16x4_add(ld4(in.p[w], eA, n), sA, a, sa);
-                q16x4_add(ld4(in.p[w], eB, n), sB, b, sb);
+                q16x4_add(in.four(w, eA, n), sA, a, sa);
+                q16x4_add(in.four(w, eB, n), sB, b, sb);
             }
         }
+        if constexpr (!Src::kEf) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = sat16(a[j], sa);
-            b[j] = sat16(b[j], sb);
+            for (int j = 0; j < 4; ++j) {
+                a[j] = sat16(a[j], sa);
+                b[j] = sat16(b[j], sb);
+            }
         }
+        // (an EF source, W = 1: the sums are the bucket's own q, in range as they are; clamping them
+        // again cost the EF instances 8 VGPRs and a wave per SIMD)
         if (eA < n) st4h(a, out, eA, n);
+        if constexpr (Src::kEf)
+            in.carry(0, u[0], u32x4{(uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3]}, invA, eA, n);
         if (eB < n) st4h(b, out, eB, n);
+        if constexpr (Src::kEf)
+            in.carry(0, v[0], u32x4{(uint32_t)b[0], (uint32_t)b[1], (uint32_t)b[2], (uint32_t)b[3]}, invB, eB, n);
         const unsigned long long ma = __ballot(sa), mb = __ballot(sb);   // wave-convergent
         if (ovf) {
-            write_slot_flags8(ma, eA < n, eA, V, lanes, ovf);
-            write_slot_flags8(mb, eB < n, eB, V, lanes, ovf);
+            if constexpr (KM == K_GLOBAL) {
+                write_slot_flags_split(ma, mb, eA, eB, n, V, ovf);
+            } else {
+                write_slot_flags8(ma, eA < n, eA, V, lanes, ovf);
+                write_slot_flags8(mb, eB < n, eB, V, lanes, ovf);
+            }
         }
     }
 }
@@ -433,10 +392,11 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(PtrPack<X> in, int Wd, int8
 // striding over the block's values; one kernel for every entry point.
 // ---------------------------------------------------------------------------
 enum { S_SCALES, S_Q32, S_Q16, S_DQ32, S_DQ16, S_APPLY, S_COMB };
-template <typename X>
+template <typename Src>
 struct ScalarArgs {
-    PtrPack<X> in;         // worker buffers (S_SCALES, S_Q32, S_Q16, S_COMB)
+    Src in;                // worker buffers (S_SCALES, S_Q32, S_Q16, S_COMB)
     int W;
+    int kg;                // K_GLOBAL: the call's k
     const float* base;     // S_SCALES: base or null; S_APPLY, S_COMB: local
     const void* src;       // S_DQ32, S_DQ16, S_APPLY: the integers
     int8_t* kblk;          // read (GIVEN) or written (AUTO; may be null for S_COMB)
@@ -448,8 +408,9 @@ struct ScalarArgs {
     float ws;
 };
 
-template <typename X, int MODE, bool AUTO>
-__global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<X> a) {
+template <typename Src, int MODE, int KM>
+__global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<Src> a) {
+    using X = typename Src::Elem;
     const size_t wave = ((size_t)blockIdx.x * kBlk + threadIdx.x) >> 6;
     const size_t nwaves = ((size_t)gridDim.x * kBlk) >> 6;
     const int lane = threadIdx.x & 63;
@@ -457,18 +418,18 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<X> a) {
     constexpr bool kDelta = MODE == S_SCALES || MODE == S_COMB;     // values are in[w][j] - base[j]
     for (size_t s = wave; s < nblk; s += nwaves) {                  // wave-uniform
         const size_t j0 = s * a.V, j1 = (j0 + a.V < a.n) ? j0 + a.V : a.n;
-        int k;
-        if constexpr (AUTO) {
+        int k = a.kg;
+        if constexpr (KM == K_AUTO) {
             uint32_t m = 0u;
             for (size_t j = j0 + lane; j < j1; j += 64)
                 for (int w = 0; w < a.W; ++w) {
-                    const float x = ld1(a.in.p[w], j);
+                    const float x = a.in.one(w, j);
                     m = umax(m, absbits((kDelta && a.base) ? __fsub_rn(x, a.base[j]) : x));
                 }
             m = group_max(m, 64);
             k = scale_of(m, a.lim);
             if (lane == 0 && a.kblk) a.kblk[s] = (int8_t)k;
-        } else {
+        } else if constexpr (KM == K_GIVEN) {
             k = rd_k(a.kblk, s);
         }
         if constexpr (MODE == S_SCALES) continue;
@@ -477,11 +438,21 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<X> a) {
         for (size_t j = j0 + lane; j < j1; j += 64) {
             if constexpr (MODE == S_Q32) {
                 uint32_t acc = 0u;
-                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(ld1(a.in.p[w], j), sc);
+                for (int w = 0; w < a.W; ++w) {
+                    const float x = a.in.one(w, j);
+                    const int32_t q = q32(x, sc);
+                    acc += (uint32_t)q;
+                    a.in.carry1(w, x, q, inv, j);
+                }
                 static_cast<int32_t*>(a.out)[j] = (int32_t)acc;
             } else if constexpr (MODE == S_Q16) {
                 int32_t acc = 0;
-                for (int w = 0; w < a.W; ++w) acc += q16(ld1(a.in.p[w], j), sc, sat);
+                for (int w = 0; w < a.W; ++w) {
+                    const float x = a.in.one(w, j);
+                    const int32_t q = q16(x, sc, sat);
+                    acc += q;
+                    a.in.carry1(w, x, q, inv, j);
+                }
                 static_cast<int16_t*>(a.out)[j] = (int16_t)sat16(acc, sat);
             } else if constexpr (MODE == S_DQ32) {
                 st1(__fmul_rn((float)static_cast<const int32_t*>(a.src)[j], inv), static_cast<X*>(a.out), j);
@@ -493,7 +464,7 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<X> a) {
             } else {
                 const float l = a.base[j];
                 uint32_t acc = 0u;
-                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(__fsub_rn(ld1(a.in.p[w], j), l), sc);
+                for (int w = 0; w < a.W; ++w) acc += (uint32_t)q32(__fsub_rn(a.in.one(w, j), l), sc);
                 const float y = __fmul_rn((float)(int32_t)acc, inv);
                 static_cast<float*>(a.out)[j] = __fadd_rn(l, __fmul_rn(y, a.ws));
             }
@@ -525,10 +496,10 @@ int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) 
 namespace {
 int launched() { return check_launch("block-scale kernel launch"); }
 
-template <int MODE, bool AUTO, typename X>
-void launch_scalar(const ScalarArgs<X>& a, hipStream_t s) {
+template <int MODE, int KM, typename Src>
+void launch_scalar(const ScalarArgs<Src>& a, hipStream_t s) {
     const size_t nblk = (a.n + a.V - 1) / a.V;
-    hipLaunchKernelGGL((k_blk_scalar<X, MODE, AUTO>), dim3(grid_of(nblk * 64, default_grid_cap())), dim3(kBlk), 0, s, a);
+    hipLaunchKernelGGL((k_blk_scalar<Src, MODE, KM>), dim3(grid_of(nblk * 64, default_grid_cap())), dim3(kBlk), 0, s, a);
 }
 
 // compile-time worker counts of the fused kernels (others: the runtime-W instance)
@@ -563,18 +534,18 @@ int block_scales(const B* const* xs, int W, const float* base, size_t n, int V, 
     if (int rc = check_v(V)) return rc;
     if (int rc = scale_lim(degree, bits, lim)) return rc;
     if (n == 0) return INA_OK;
-    PtrPack<X> pk;
+    SrcPlain<X> src;
     bool al;
-    if (int rc = fill_pack(pk, xs, W, al)) return rc;
+    if (int rc = fill_pack(src.in, xs, W, al)) return rc;
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     hipStream_t s = hs(stream);
     int shift;
-    if (vec_v(V, shift) && src_aligned(pk, W) && (!base || aligned16(base))) {
-        hipLaunchKernelGGL(k_blk_scales<X>, dim3(grid_of((n + 3) / 4, stream_grid_cap())), dim3(kBlk), 0, s, pk, W, base,
-                           n, shift, lim, kblk);
+    if (vec_v(V, shift) && src_aligned(src.in, W) && (!base || aligned16(base))) {
+        hipLaunchKernelGGL(k_blk_scales<SrcPlain<X>>, dim3(grid_of((n + 3) / 4, stream_grid_cap())), dim3(kBlk), 0, s,
+                           src, W, base, n, shift, lim, kblk);
     } else {
-        ScalarArgs<X> a{pk, W, base, nullptr, kblk, lim, nullptr, n, (size_t)V, nullptr, 0.f};
-        launch_scalar<S_SCALES, true>(a, s);
+        ScalarArgs<SrcPlain<X>> a{src, W, 0, base, nullptr, kblk, lim, nullptr, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_SCALES, K_AUTO>(a, s);
     }
     return launched();
 }
@@ -586,27 +557,27 @@ int reduce_i32(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, 
     if (int rc = check_v(V)) return rc;
     if (int rc = check_mode(mode, kblk, degree, 32, lim)) return rc;
     if (n == 0) return INA_OK;
-    PtrPack<X> pk;
+    SrcPlain<X> src;
     bool al;
-    if (int rc = fill_pack(pk, bufs, W, al)) return rc;
+    if (int rc = fill_pack(src.in, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
-    if (vec_v(V, shift) && src_aligned(pk, W) && aligned16(out)) {
+    if (vec_v(V, shift) && src_aligned(src.in, W) && aligned16(out)) {
         // the sibling's grids: covering for W <= 8, the streaming cap beyond
         const dim3 g(grid_of((n + 3) / 4, W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
 #define L(WW)                                                                                                 \
     do {                                                                                                      \
-        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<X, WW, true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift); \
-        else hipLaunchKernelGGL((k_qr_blk_i32<X, WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift);   \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<SrcPlain<X>, WW, K_AUTO>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift); \
+        else hipLaunchKernelGGL((k_qr_blk_i32<SrcPlain<X>, WW, K_GIVEN>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift); \
     } while (0)
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs<X> a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
-        if (autok) launch_scalar<S_Q32, true>(a, s);
-        else launch_scalar<S_Q32, false>(a, s);
+        ScalarArgs<SrcPlain<X>> a{src, W, 0, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
+        if (autok) launch_scalar<S_Q32, K_AUTO>(a, s);
+        else launch_scalar<S_Q32, K_GIVEN>(a, s);
     }
     return launched();
 }
@@ -618,27 +589,27 @@ int reduce_i16(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, 
     if (int rc = check_v(V)) return rc;
     if (int rc = check_mode(mode, kblk, degree, 16, lim)) return rc;
     if (n == 0) return INA_OK;
-    PtrPack<X> pk;
+    SrcPlain<X> src;
     bool al;
-    if (int rc = fill_pack(pk, bufs, W, al)) return rc;
+    if (int rc = fill_pack(src.in, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
     // (out is stored 8 bytes a lane; beside fp32 buckets it keeps the 16-byte rule it always had)
-    if (vec_v(V, shift) && src_aligned(pk, W) && (uintptr_t)out % (4 * sizeof(X)) == 0) {
+    if (vec_v(V, shift) && src_aligned(src.in, W) && (uintptr_t)out % (4 * sizeof(X)) == 0) {
         const dim3 g(grid_of((n + 511) / 512 * 64, default_grid_cap())), b(kBlk);
 #define L(WW)                                                                                                          \
     do {                                                                                                               \
-        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<X, (WW <= 8 ? WW : 0), true>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf); \
-        else hipLaunchKernelGGL((k_qr_blk_i16<X, WW, false>), g, b, 0, s, pk, W, kblk, lim, out, n, shift, V, ovf);    \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<SrcPlain<X>, (WW <= 8 ? WW : 0), K_AUTO>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift, V, ovf); \
+        else hipLaunchKernelGGL((k_qr_blk_i16<SrcPlain<X>, WW, K_GIVEN>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift, V, ovf); \
     } while (0)
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs<X> a{pk, W, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
-        if (autok) launch_scalar<S_Q16, true>(a, s);
-        else launch_scalar<S_Q16, false>(a, s);
+        ScalarArgs<SrcPlain<X>> a{src, W, 0, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
+        if (autok) launch_scalar<S_Q16, K_AUTO>(a, s);
+        else launch_scalar<S_Q16, K_GIVEN>(a, s);
     }
     return launched();
 }
@@ -673,14 +644,90 @@ int dequantize(const T* sv, const int8_t* kblk, int V, B* y, size_t n, ina_strea
         hipLaunchKernelGGL((k_dq_blk<T, Y>), dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), sv,
                            kblk, static_cast<Y*>(y), n, shift);
     } else {
-        ScalarArgs<Y> a{{}, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
-        if constexpr (sizeof(T) == 4) launch_scalar<S_DQ32, false>(a, hs(stream));
-        else launch_scalar<S_DQ16, false>(a, hs(stream));
+        ScalarArgs<SrcPlain<Y>> a{{}, 0, 0, nullptr, sv, const_cast<int8_t*>(kblk), 1.0, y, n, (size_t)V, nullptr, 0.f};
+        if constexpr (sizeof(T) == 4) launch_scalar<S_DQ32, K_GIVEN>(a, hs(stream));
+        else launch_scalar<S_DQ16, K_GIVEN>(a, hs(stream));
     }
     return launched();
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// error feedback (include/ina_ef.h): the EF instances of the kernels above, W = 1.  The entry
+// points and their checks are in ina_ef.hip.  Every launch is under the default grid cap.
+// ---------------------------------------------------------------------------
+namespace {
+int launched_ef() { return check_launch("error-feedback kernel launch"); }
+
+template <typename X, typename Q, int KM>
+int ef_launch(const EfQuant& c, hipStream_t s) {
+    using Src = SrcEf<X, 1>;
+    const Src src{{static_cast<const X*>(c.x)}, {c.resid}, c.base};
+    Q* q = static_cast<Q*>(c.q);
+    // the vector path where the lane layout fits V (global k: the slots of the int16 flags, if any
+    // are asked for), and a lane's 4 values of x, r, base and q are one load or store each
+    int shift = 0;
+    const bool fits = KM == K_GLOBAL ? (sizeof(Q) == 4 || !c.ovf || slot_ballot_ok(c.V)) : vec_v(c.V, shift);
+    if (fits && (uintptr_t)c.x % (4 * sizeof(X)) == 0 && aligned16(c.resid) && (!c.base || aligned16(c.base)) &&
+        (uintptr_t)q % (4 * sizeof(Q)) == 0) {
+        const dim3 b(kBlk);
+        if constexpr (sizeof(Q) == 4) {
+            hipLaunchKernelGGL((k_qr_blk_i32<Src, 1, KM>), dim3(grid_of((c.n + 3) / 4, default_grid_cap())), b, 0, s, src,
+                               1, c.k, c.kblk, c.lim, q, c.n, shift);
+        } else {
+            hipLaunchKernelGGL((k_qr_blk_i16<Src, 1, KM>), dim3(grid_of((c.n + 511) / 512 * 64, default_grid_cap())), b,
+                               0, s, src, 1, c.k, c.kblk, c.lim, q, c.n, shift, c.V, c.ovf);
+        }
+    } else {
+        ScalarArgs<Src> a{src, 1, c.k, nullptr, nullptr, c.kblk, c.lim, q, c.n, (size_t)c.V, c.ovf, 0.f};
+        launch_scalar<sizeof(Q) == 4 ? S_Q32 : S_Q16, KM>(a, s);
+    }
+    return launched_ef();
+}
+// block scales are for fp32 buckets only (include/ina_ef.h)
+template <typename X, typename Q>
+int ef_launch_km(const EfQuant& c, hipStream_t s) {
+    if constexpr (std::is_same_v<X, float>) {
+        if (c.km == K_GIVEN) return ef_launch<X, Q, K_GIVEN>(c, s);
+        if (c.km == K_AUTO) return ef_launch<X, Q, K_AUTO>(c, s);
+    }
+    return ef_launch<X, Q, K_GLOBAL>(c, s);
+}
+template <typename X>
+int ef_launch_q(const EfQuant& c, hipStream_t s) {
+    return c.bits == 32 ? ef_launch_km<X, int32_t>(c, s) : ef_launch_km<X, int16_t>(c, s);
+}
+}  // namespace
+
+int ef_quantize(const EfQuant& c, ina_stream_t stream) {
+    hipStream_t s = hs(stream);
+    if (c.xtype == INA_X16_BF16) return ef_launch_q<bf16_t>(c, s);
+    if (c.xtype == INA_X16_F16) return ef_launch_q<fp16_t>(c, s);
+    return ef_launch_q<float>(c, s);
+}
+
+int ef_block_scales(const PtrPack<float>& xs, const PtrPack<float>& rs, int W, bool aligned, const float* base,
+                    size_t n, int V, double lim, int8_t* kblk, ina_stream_t stream) {
+    using Src = SrcEf<float, INA_MAX_WORKERS>;
+    Src src;
+    for (int w = 0; w < INA_MAX_WORKERS; ++w) {
+        src.x[w] = xs.p[w];
+        src.resid[w] = const_cast<float*>(rs.p[w]);
+    }
+    src.base = base;
+    hipStream_t s = hs(stream);
+    int shift;
+    if (vec_v(V, shift) && aligned && (!base || aligned16(base))) {
+        hipLaunchKernelGGL(k_blk_scales<Src>, dim3(grid_of((n + 3) / 4, default_grid_cap())), dim3(kBlk), 0, s, src, W,
+                           nullptr, n, shift, lim, kblk);
+    } else {
+        ScalarArgs<Src> a{src, W, 0, nullptr, nullptr, kblk, lim, nullptr, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_SCALES, K_AUTO>(a, s);
+    }
+    return launched_ef();
+}
+
 }  // namespace ina
 
 using namespace ina;
@@ -774,9 +821,9 @@ int ina_ps_apply_blk_i32(const float* local, const int32_t* sum_int, const int8_
         hipLaunchKernelGGL(k_ps_apply_blk, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, hs(stream), local,
                            sum_int, kblk, (float)weight_step, out, n, shift);
     } else {
-        ScalarArgs<float> a{{}, 0, local, sum_int, const_cast<int8_t*>(kblk), 1.0, out, n, (size_t)V, nullptr,
-                     (float)weight_step};
-        launch_scalar<S_APPLY, false>(a, hs(stream));
+        ScalarArgs<SrcPlain<float>> a{{}, 0, 0, local, sum_int, const_cast<int8_t*>(kblk), 1.0, out, n, (size_t)V, nullptr,
+                                      (float)weight_step};
+        launch_scalar<S_APPLY, K_GIVEN>(a, hs(stream));
     }
     return launched();
 }
@@ -800,8 +847,8 @@ int ina_ps_combine_ina_blk_f32(const float* local, const float* const* paras, in
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs<float> a{pk, W, local, nullptr, kblk_out, lim, out, n, (size_t)V, nullptr, ws};
-        launch_scalar<S_COMB, true>(a, s);
+        ScalarArgs<SrcPlain<float>> a{{pk}, W, 0, local, nullptr, kblk_out, lim, out, n, (size_t)V, nullptr, ws};
+        launch_scalar<S_COMB, K_AUTO>(a, s);
     }
     return launched();
 }

@@ -38,6 +38,31 @@ int scale_lim(int degree, int bits, double& lim);
 // under INA_BLK_AUTO, else 1)
 int check_v(int V);
 int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim);
+// ina_blk.hip: where a block kernel's k comes from -- the call's one k (the error-feedback calls only),
+// kblk[block] read, or the block's max |value| in the launch with kblk[block] written
+enum { K_GLOBAL, K_GIVEN, K_AUTO };
+// ina_blk.hip: the error-feedback launches (include/ina_ef.h; ina_ef.hip checks the arguments).  One
+// bucket quantised: x is fp32 (xtype 0) or INA_X16_*, q int32 or int16 (bits); V is the block of
+// K_GIVEN / K_AUTO, the slot of the int16 flags under K_GLOBAL (256 for int32 out).
+struct EfQuant {
+    const void* x;
+    int xtype;
+    const float* base;     // may be null
+    float* resid;          // read, then written
+    void* q;
+    int bits;
+    size_t n;
+    int km;
+    int k;                 // K_GLOBAL
+    int8_t* kblk;          // K_GIVEN: read; K_AUTO: written
+    double lim;            // K_AUTO
+    int V;
+    uint8_t* ovf;          // int16 out: may be null
+};
+int ef_quantize(const EfQuant& c, ina_stream_t stream);
+// the scales alone over |(xs[w] - base) + rs[w]|; aligned: every xs[w] and rs[w] is 16-byte aligned
+int ef_block_scales(const PtrPack<float>& xs, const PtrPack<float>& rs, int W, bool aligned, const float* base,
+                    size_t n, int V, double lim, int8_t* kblk, ina_stream_t stream);
 int check_x16_type(int xtype);   // ina_x16.hip: INA_OK for INA_X16_BF16 / INA_X16_F16, else INA_EINVAL
 // checked builds (INA_STORE_CHECK, ina_device.h): each source's stream_store contract
 // violations since the last read, cleared by the read
@@ -46,7 +71,6 @@ unsigned long long store_violations_shard();     // ina_shard.hip
 unsigned long long store_violations_switch();    // ina_switch.hip
 unsigned long long store_violations_x16();       // ina_x16.hip
 unsigned long long store_violations_blk();       // ina_blk.hip
-unsigned long long store_violations_ef();        // ina_ef.hip
 
 // ---------------------------------------------------------------------------
 // host helpers

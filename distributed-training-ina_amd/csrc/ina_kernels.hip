@@ -26,12 +26,9 @@
 #include "ina.h"
 #include "ina_internal.h"
 #include "ina_device.h"
+#include "ina_chunk.h"
 
 namespace ina {
-
-using u32x4 = u32x4_t;
-using u32x2 = u32x2_t;
-using f32x4 = f32x4_t;
 
 constexpr int kBlock = kHostBlock;
 
@@ -787,18 +784,8 @@ struct SrcI32 {
         return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(v + e));
     }
 };
-// The quantise step of every fused pack: the worker's delta x - b where the call has a base (the
-// fp32 op sequence of the PS update, no FMA), then q32 of its four values.
-__device__ __forceinline__ f32x4 delta4(f32x4 x, f32x4 b, bool has_base) {
-    if (has_base) {
-        x.x = __fsub_rn(x.x, b.x); x.y = __fsub_rn(x.y, b.y);
-        x.z = __fsub_rn(x.z, b.z); x.w = __fsub_rn(x.w, b.w);
-    }
-    return x;
-}
-__device__ __forceinline__ u32x4 quant4(f32x4 y, float s) {
-    return u32x4{(uint32_t)q32(y.x, s), (uint32_t)q32(y.y, s), (uint32_t)q32(y.z, s), (uint32_t)q32(y.w, s)};
-}
+// The quantise step of every fused pack (ina_chunk.h): the worker's delta sub4(x, b) where the call
+// has a base (the fp32 op sequence of the PS update, no FMA), then q32x4 of its four values.
 // How the split multi pack reads 4 worker values: fp32 as they are, or bf16 / fp16 (ina.h
 // INA_X16_*) widened in registers from one 8-byte load
 struct LdF32 {
@@ -830,9 +817,9 @@ struct SrcQ32 {
             // same vector, so it is loaded with the default policy and stays in the
             // Infinity Cache between them (nt: the steady-state 8-worker step 0.690 ->
             // 0.661 ms; one cold pack unchanged; profiles/r03/lab/qpack_base_lab.log)
-            a = delta4(a, *reinterpret_cast<const f32x4*>(base + e), true);
+            a = sub4(a, *reinterpret_cast<const f32x4*>(base + e));
         }
-        return quant4(a, s);
+        return q32x4(a, s);
     }
 };
 
@@ -852,9 +839,9 @@ struct SrcX16 {
     __device__ __forceinline__ u32x4 four(size_t e) const {
         f32x4 a = widen16x4<XT>(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(x + e)));
         if (base) {                                    // shared: default policy, as in SrcQ32
-            a = delta4(a, *reinterpret_cast<const f32x4*>(base + e), true);
+            a = sub4(a, *reinterpret_cast<const f32x4*>(base + e));
         }
-        return quant4(a, s);
+        return q32x4(a, s);
     }
 };
 // SrcQ32 with one scale per packet (include/ina_pkt_blk.h): element e belongs to packet e / V and is
@@ -1083,7 +1070,7 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi(QPackGroup a, const 
             v[g] = u32x4{0u, 0u, 0u, 0u};
             if (full) {
                 const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
-                v[g] = quant4(delta4(x, b, base != nullptr), s);
+                v[g] = q32x4(base ? sub4(x, b) : x, s);
             } else if (body) {                         // last packet of the bucket: zero tail
                 v[g] = tail4<3>(SrcQ32{a.x[g], base, s}, e0, n);
             }
@@ -1179,7 +1166,7 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_v256(QPackGroup a, c
             v[g] = u32x4{0u, 0u, 0u, 0u};
             if (full) {
                 const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.x[g] + e0));
-                v[g] = quant4(delta4(x, b, base != nullptr), s);
+                v[g] = q32x4(base ? sub4(x, b) : x, s);
             } else {
                 v[g] = tail4<3>(SrcQ32{a.x[g], base, s}, e0, n);
             }
@@ -1267,18 +1254,8 @@ template <typename X>
 struct QPackRows<X, true> : QPackRows<X, false> {
     float* resid[kQpGroup];
 };
-// The error-feedback step of the EF packs on one chunk: v = d + r (d: the worker's delta), and
-// r' = isfinite(v) ? v - float(q) * 2^-k : +0 once the chunk is quantised -- ina_ef.hip's arithmetic.
-__device__ __forceinline__ f32x4 ef_add4(f32x4 d, f32x4 r) {
-    return f32x4{__fadd_rn(d.x, r.x), __fadd_rn(d.y, r.y), __fadd_rn(d.z, r.z), __fadd_rn(d.w, r.w)};
-}
-__device__ __forceinline__ float ef_carry(float v, uint32_t q, float inv) {
-    const bool finite = (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u;
-    return finite ? __fsub_rn(v, __fmul_rn((float)(int32_t)q, inv)) : 0.0f;
-}
-__device__ __forceinline__ f32x4 ef_carry4(f32x4 v, u32x4 q, float inv) {
-    return f32x4{ef_carry(v.x, q.x, inv), ef_carry(v.y, q.y, inv), ef_carry(v.z, q.z, inv), ef_carry(v.w, q.w, inv)};
-}
+// (the error-feedback step of the EF packs on one chunk is ina_chunk.h's: ef_v4, then ef_r4 once the
+// chunk is quantised)
 // the bucket's last chunk under EF, value by value: the words for the payload (0 past n), residuals
 // updated in place
 __device__ __forceinline__ u32x4 ef_tail4(const float* __restrict__ x, const float* __restrict__ base, float* resid,
@@ -1289,7 +1266,7 @@ __device__ __forceinline__ u32x4 ef_tail4(const float* __restrict__ x, const flo
         if (e < n) {
             const float v = __fadd_rn(base ? __fsub_rn(x[e], base[e]) : x[e], resid[e]);
             w[j] = (uint32_t)q32(v, s);
-            resid[e] = ef_carry(v, w[j], inv);
+            resid[e] = ef_r(v, (int32_t)w[j], inv);
         }
     }
     return u32x4{w[0], w[1], w[2], w[3]};
@@ -1319,10 +1296,10 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
                 }
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
-                    const f32x4 v = ef_add4(delta4(x[g], b, base != nullptr), r[g]);
-                    const u32x4 q = quant4(v, s);
+                    const f32x4 v = ef_v4(base ? sub4(x[g], b) : x[g], r[g]);
+                    const u32x4 q = q32x4(v, s);
                     packet_store(bswap4(q), a.pay[g] + t);
-                    stream_store(ef_carry4(v, q, inv), reinterpret_cast<f32x4*>(a.resid[g] + e0));
+                    stream_store(ef_r4(v, q, inv), reinterpret_cast<f32x4*>(a.resid[g] + e0));
                 }
             } else {
 #pragma unroll
@@ -1339,7 +1316,8 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
             for (int g = 0; g < G; ++g) x[g] = __builtin_nontemporal_load(reinterpret_cast<const typename Ld::Raw*>(a.x[g] + e0));
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                const u32x4 q = quant4(delta4(Ld::widen4(x[g]), b, base != nullptr), s);
+                const f32x4 y = Ld::widen4(x[g]);
+                const u32x4 q = q32x4(base ? sub4(y, b) : y, s);
                 packet_store(bswap4(q), a.pay[g] + t);
             }
         } else {                                       // the bucket's last chunk: zero tail
@@ -1388,10 +1366,10 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
         if constexpr (!AUTO) k = rd_k(kblk, shift >= 0 ? t >> shift : t / L);
         // worker g's chunk of deltas, quantised with 2^kk, into its payload row
         auto put = [&](int g, f32x4 y, int kk) {
-            const u32x4 q = quant4(y, pow2f(kk));
+            const u32x4 q = q32x4(y, pow2f(kk));
             packet_store(bswap4(q), a.pay[g] + t);
             if constexpr (EF) {
-                const f32x4 r = ef_carry4(y, q, pow2f(-kk));
+                const f32x4 r = ef_r4(y, q, pow2f(-kk));
                 float* rp = a.resid[g] + e0;
                 if (e0 + 4 <= n) {
                     stream_store(r, reinterpret_cast<f32x4*>(rp));
@@ -1416,11 +1394,11 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
             }
             if (base) {                                // one test for the group, as the held registers were scheduled
 #pragma unroll
-                for (int g = 0; g < G; ++g) d[g] = delta4(d[g], b, true);
+                for (int g = 0; g < G; ++g) d[g] = sub4(d[g], b);
             }
             if constexpr (EF) {
 #pragma unroll
-                for (int g = 0; g < G; ++g) d[g] = ef_add4(d[g], r[g]);
+                for (int g = 0; g < G; ++g) d[g] = ef_v4(d[g], r[g]);
             }
             if constexpr (!AUTO) {                     // given scales: nothing to wait for
 #pragma unroll
@@ -2943,7 +2921,7 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (!count) return INA_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
-             ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_ef();
+             ina::store_violations_x16() + ina::store_violations_blk();
     return INA_OK;
 }
 #endif

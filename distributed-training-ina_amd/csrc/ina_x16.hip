@@ -28,19 +28,12 @@
 #include "ina.h"
 #include "ina_internal.h"
 #include "ina_device.h"
+#include "ina_chunk.h"
 
 namespace ina {
 namespace {
 
-using u32x4 = u32x4_t;
-using u32x2 = u32x2_t;
-using f32x4 = f32x4_t;
-
 constexpr int kBlk = kHostBlock;
-
-__device__ __forceinline__ u32x4 q32x4(f32x4 v, float s) {
-    return u32x4{(uint32_t)q32(v.x, s), (uint32_t)q32(v.y, s), (uint32_t)q32(v.z, s), (uint32_t)q32(v.w, s)};
-}
 
 // ---------------------------------------------------------------------------
 // quantise

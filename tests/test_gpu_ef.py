@@ -104,8 +104,10 @@ def test_replay_global_i32(off, with_base):
 
 
 @pytest.mark.parametrize("off", [0, 1])
-@pytest.mark.parametrize("V", VS)
+@pytest.mark.parametrize("V", VS + (512, 1024))
 def test_replay_global_i16(V, off):
+    """512: one slot is both 256-value halves of a wave; 1024: no ballot layout, the scalar path with
+    a block larger than a wave's 512 values.  At both the expected flags at n = 4099 hold 0s and 1s."""
     ef, _ = _ops()
     for n in SIZES:
         for with_base in (False, True):

@@ -321,6 +321,57 @@ def run_ef(dev):
     return rows
 
 
+def run_ef_shard(dev):
+    """Error feedback on the sharded int16 wire (include/ina_shard_ef.h) at the ResNet-50 size, cold
+    caches, median of 20, the set twice in this process (run 1 / run 2), V = 256 and 32.  Each EF wire
+    quantiser (16 B a value: x, r, word, r') beside (a) its non-EF wire sibling (8 B a value) timed
+    twice -- the bar is sibling time x 16/8 plus the spread of the sibling's two timings -- and (b)
+    the composition a caller would otherwise write, every buffer preallocated: torch add, the
+    sibling, q16 out of the word and q16 * 2^-k in torch (two shifts and a multiply; the per-value
+    2^-k of the block form is made once, outside the timing), torch sub.  Nothing is gated."""
+    from ina_amd import ef, ops
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(23)
+    n, k = 25_557_032, 9
+    x = torch.randn(n, device=dev, generator=gen) * 1e-2
+    r = torch.randn(n, device=dev, generator=gen) * 2.0 ** -(k + 2)
+    v, d = torch.empty_like(x), torch.empty_like(x)
+    w = torch.empty(n, dtype=torch.int32, device=dev)
+    t = torch.empty(n, dtype=torch.int32, device=dev)
+
+    def comp(quant, inv):
+        def run():
+            torch.add(x, r, out=v)
+            quant()
+            torch.bitwise_left_shift(w, 10, out=t)
+            torch.bitwise_right_shift(t, 10, out=t)          # the word's low 22 bits, sign-extended
+            torch.mul(t, inv, out=d)
+            torch.sub(v, d, out=r)
+        return run
+
+    def row(run, name, f_ef, f_comp, f_sib):
+        ta, te, tc, tb = _time(f_sib), _time(f_ef), _time(f_comp), _time(f_sib)
+        lo, hi = min(ta, tb), max(ta, tb)
+        rows.append(_row(f"{name} [ef wire, run {run}]", te, 16 * n, composition_us=round(tc * 1e6, 2),
+                         composition_over_ef=round(tc / te, 2),
+                         sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], sibling_spread_us=round((hi - lo) * 1e6, 2),
+                         bar_us=round((2 * lo + hi - lo) * 1e6, 2), within_bar=bool(te <= 2 * lo + hi - lo),
+                         ratio_to_sibling_x_bytes=round(te / (2 * lo), 3)))
+
+    for run in (1, 2):
+        row(run, f"quantize_i16_wire k={k}", lambda: ef.quantize_i16_wire(x, r, k, out=w),
+            comp(lambda: ops.quantize_i16_wire(v, k, out=w), 2.0 ** -k), lambda: ops.quantize_i16_wire(x, k, out=w))
+        for V in (256, 32):
+            kb = ops.block_scales([x], V, bits=16, degree=64)
+            inv = torch.exp2(-kb.float()).repeat_interleave(V)[:n].contiguous()
+            row(run, f"quantize_i16_wire_blk V={V}", lambda: ef.quantize_i16_wire_blk(x, r, kb, V, out=w),
+                comp(lambda: ops.quantize_i16_wire_blk(v, kb, V, out=w), inv),
+                lambda: ops.quantize_i16_wire_blk(x, kb, V, out=w))
+            del inv
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -949,6 +1000,7 @@ def run_extra(dev):
     rows += run_x16(dev)
     rows += run_blk(dev)
     rows += run_ef(dev)
+    rows += run_ef_shard(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

@@ -38,7 +38,9 @@
 //
 // Error feedback (include/ina_ef.h; entry points in ina_ef.hip): the same kernels at W = 1 with the
 // SrcEf value source, which reads v = (x - base) + r where the plain source reads x and stores r'
-// once v is quantised, and a third scale mode, the call's one k.  No kernel of its own.
+// once v is quantised, and a third scale mode, the call's one k.  No kernel of its own.  The EF
+// quantisers of the sharded int16 wire (include/ina_shard_ef.h) are the int32 instances with the
+// SrcEfWire source: the wire word q16 + (sat << 22) where those run q32, q16 into the carry.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -75,6 +77,7 @@ constexpr int kBlk = 256;
 template <typename X>
 struct SrcPlain {
     static constexpr bool kEf = false;
+    static constexpr bool kWire = false;
     using Elem = X;
     PtrPack<X> in;
     __device__ __forceinline__ f32x4 four(int w, size_t e, size_t n) const { return ld4(in.p[w], e, n); }
@@ -90,6 +93,7 @@ struct SrcPlain {
 template <typename X, int N>
 struct SrcEf {
     static constexpr bool kEf = true;
+    static constexpr bool kWire = false;
     using Elem = X;
     const X* x[N];
     float* resid[N];
@@ -109,6 +113,12 @@ struct SrcEf {
     __device__ __forceinline__ void carry1(int w, float v, int32_t q, float inv, size_t j) const {
         resid[w][j] = ef_r(v, q, inv);
     }
+};
+// Error feedback on the sharded int16 wire (include/ina_shard_ef.h): the same source, and the int32
+// kernels quantise what it reads to the wire word q16 + (sat << 22) (q16w) where they run q32.  The
+// carry is handed the word's q16, never the word with its count bits.
+struct SrcEfWire : SrcEf<float, 1> {
+    static constexpr bool kWire = true;
 };
 
 // ---------------------------------------------------------------------------
@@ -195,9 +205,15 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i32(Src in, int Wd, int kg, int
         u32x4 acc = {0u, 0u, 0u, 0u};
         // worker w's chunk: quantised, summed, and handed back to the source
         auto add = [&](int w, f32x4 x) {
-            const u32x4 q = q32x4(x, s);
-            acc += q;
-            in.carry(w, x, q, inv, e, n);
+            if constexpr (Src::kWire) {
+                const u32x4 word = q16wx4(x, s);
+                acc += word;
+                in.carry(w, x, wire_q16x4(word), inv, e, n);
+            } else {
+                const u32x4 q = q32x4(x, s);
+                acc += q;
+                in.carry(w, x, q, inv, e, n);
+            }
         };
         if constexpr (HOLD) {
 #pragma unroll
@@ -440,9 +456,15 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<Src> a) {
                 uint32_t acc = 0u;
                 for (int w = 0; w < a.W; ++w) {
                     const float x = a.in.one(w, j);
-                    const int32_t q = q32(x, sc);
-                    acc += (uint32_t)q;
-                    a.in.carry1(w, x, q, inv, j);
+                    if constexpr (Src::kWire) {
+                        const int32_t word = q16w(x, sc);
+                        acc += (uint32_t)word;
+                        a.in.carry1(w, x, wire_q16(word), inv, j);
+                    } else {
+                        const int32_t q = q32(x, sc);
+                        acc += (uint32_t)q;
+                        a.in.carry1(w, x, q, inv, j);
+                    }
                 }
                 static_cast<int32_t*>(a.out)[j] = (int32_t)acc;
             } else if constexpr (MODE == S_Q16) {
@@ -660,10 +682,15 @@ int dequantize(const T* sv, const int8_t* kblk, int V, B* y, size_t n, ina_strea
 namespace {
 int launched_ef() { return check_launch("error-feedback kernel launch"); }
 
-template <typename X, typename Q, int KM>
+// WIRE: q holds the sharded int16 wire's int32 words (fp32 bucket, no base)
+template <typename X, typename Q, int KM, bool WIRE = false>
 int ef_launch(const EfQuant& c, hipStream_t s) {
-    using Src = SrcEf<X, 1>;
-    const Src src{{static_cast<const X*>(c.x)}, {c.resid}, c.base};
+    using Src = std::conditional_t<WIRE, SrcEfWire, SrcEf<X, 1>>;
+    static_assert(!WIRE || (std::is_same_v<X, float> && sizeof(Q) == 4 && KM != K_AUTO), "fp32 -> int32 words, k given");
+    Src src;
+    src.x[0] = static_cast<const X*>(c.x);
+    src.resid[0] = c.resid;
+    src.base = c.base;
     Q* q = static_cast<Q*>(c.q);
     // the vector path where the lane layout fits V (global k: the slots of the int16 flags, if any
     // are asked for), and a lane's 4 values of x, r, base and q are one load or store each
@@ -702,6 +729,9 @@ int ef_launch_q(const EfQuant& c, hipStream_t s) {
 
 int ef_quantize(const EfQuant& c, ina_stream_t stream) {
     hipStream_t s = hs(stream);
+    if (c.wire)
+        return c.km == K_GIVEN ? ef_launch<float, int32_t, K_GIVEN, true>(c, s)
+                               : ef_launch<float, int32_t, K_GLOBAL, true>(c, s);
     if (c.xtype == INA_X16_BF16) return ef_launch_q<bf16_t>(c, s);
     if (c.xtype == INA_X16_F16) return ef_launch_q<fp16_t>(c, s);
     return ef_launch_q<float>(c, s);

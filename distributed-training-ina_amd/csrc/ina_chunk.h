@@ -116,6 +116,14 @@ __device__ __forceinline__ void st4h(const int32_t* a, int16_t* p, size_t e, siz
 __device__ __forceinline__ u32x4 q32x4(f32x4 v, float s) {
     return u32x4{(uint32_t)q32(v.x, s), (uint32_t)q32(v.y, s), (uint32_t)q32(v.z, s), (uint32_t)q32(v.w, s)};
 }
+// the sharded int16 wire's words (q16w), and the q16 of each back out of them
+__device__ __forceinline__ u32x4 q16wx4(f32x4 v, float s) {
+    return u32x4{(uint32_t)q16w(v.x, s), (uint32_t)q16w(v.y, s), (uint32_t)q16w(v.z, s), (uint32_t)q16w(v.w, s)};
+}
+__device__ __forceinline__ u32x4 wire_q16x4(u32x4 w) {
+    return u32x4{(uint32_t)wire_q16((int32_t)w.x), (uint32_t)wire_q16((int32_t)w.y),
+                 (uint32_t)wire_q16((int32_t)w.z), (uint32_t)wire_q16((int32_t)w.w)};
+}
 // (int16 sums are held widened, as int32_t[4])
 __device__ __forceinline__ void q16x4_add(f32x4 v, float s, int32_t* a, bool& sat) {
     a[0] += q16(v.x, s, sat); a[1] += q16(v.y, s, sat); a[2] += q16(v.z, s, sat); a[3] += q16(v.w, s, sat);

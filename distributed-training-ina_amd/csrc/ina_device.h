@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ina.h"
+
 namespace ina {
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -141,6 +143,23 @@ __device__ __forceinline__ int32_t sat16(int32_t a, bool& sat) {
     bool hi = a > 32767, lo = a < -32768;
     sat |= hi | lo;
     return hi ? 32767 : (lo ? -32768 : a);
+}
+
+// the word of the sharded int16 wire (include/ina.h; ina_shard.hip): the quantiser of
+// ina_quantize_f32_i16_sat, sat16(rne(x * 2^k)), NaN -> 0 (flagged), with the saturation bit above
+// it -- q16 + (sat << 22).  The one copy: the wire quantisers of ina_shard.hip and their
+// error-feedback siblings (the kernels of ina_blk.hip) run it.
+constexpr int kWireShift = INA_I16_WIRE_SHIFT;   // 22
+__device__ __forceinline__ int32_t q16w(float x, float s) {
+    const float y = __builtin_rintf(x * s);
+    const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);   // one v_med3_f32
+    const int32_t v = (y != y) ? 0 : (int32_t)c;
+    const int32_t sat = !(c == y);               // clamped, +-inf or NaN
+    return v + (sat << kWireShift);
+}
+// q16 back out of one rank's word: its low 22 bits, sign-extended (|q16| <= 2^15, sat is 0 or 1)
+__device__ __forceinline__ int32_t wire_q16(int32_t w) {
+    return (int32_t)((uint32_t)w << (32 - kWireShift)) >> (32 - kWireShift);
 }
 
 // ---------------------------------------------------------------------------

@@ -17,6 +17,11 @@
 //
 // The EF worker packs are instances of the split multi pack kernels of ina_kernels.hip (their EF
 // template parameter); their entry points are there.
+//
+// The sharded int16 wire (include/ina_shard_ef.h): the two quantisers whose q is the int32 wire
+// word q16 + (sat << 22) of ina_shard.hip.  They run the int32 instances above with the SrcEfWire
+// source, which quantises with q16w and carries the word's q16: 16 bytes a value (x 4, r 4, word 4,
+// r' 4) where the composition from existing ops moves about 40.
 #include "ina.h"
 #include "ina_internal.h"
 
@@ -45,12 +50,43 @@ int quantize_ef_blk(const float* x, const float* base, float* resid, int8_t* kbl
                        stream);
 }
 
+// n fp32 / int32 values at a and at b share a byte
+bool overlap4(const void* a, const void* b, size_t n) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, len = (uintptr_t)n * 4u;
+    return pa < pb ? pb - pa < len : pa - pb < len;
+}
+
+// the checks the wire siblings (ina_shard.hip) leave to the EF calls, then the launch
+int quantize_ef_wire(const float* x, float* resid, int32_t* wire, size_t n, int km, int k, const int8_t* kblk, int V,
+                     ina_stream_t stream) {
+    if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (!resid) return set_error(INA_EINVAL, "null resid%s", "");
+    if (overlap4(resid, x, n) || overlap4(resid, wire, n)) return set_error(INA_EINVAL, "resid overlaps x or wire%s", "");
+    return ef_quantize(EfQuant{x, 0, nullptr, resid, wire, 32, n, km, k, const_cast<int8_t*>(kblk), 1.0, V, nullptr, true},
+                       stream);
+}
+
 }  // namespace
 }  // namespace ina
 
 using namespace ina;
 
 extern "C" {
+
+// ---- include/ina_shard_ef.h: checks in the order of ina_quantize_f32_i16_wire / ina_quantize_blk_f32_i16_wire ----
+int ina_quantize_ef_f32_i16_wire(const float* x, float* resid, int32_t* wire, size_t n, int k, ina_stream_t stream) {
+    if (int rc = check_k(k)) return rc;
+    if (n == 0) return INA_OK;
+    return quantize_ef_wire(x, resid, wire, n, K_GLOBAL, k, nullptr, 256, stream);   // (256: the scalar path's blocks)
+}
+
+int ina_quantize_ef_blk_f32_i16_wire(const float* x, float* resid, const int8_t* kblk, int V, int32_t* wire, size_t n,
+                                     ina_stream_t stream) {
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    return quantize_ef_wire(x, resid, wire, n, K_GIVEN, 0, kblk, V, stream);
+}
 
 int ina_quantize_ef_f32_i32(const float* x, const float* base, float* resid, int32_t* q, size_t n, int k,
                             ina_stream_t stream) {

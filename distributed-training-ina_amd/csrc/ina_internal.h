@@ -43,7 +43,8 @@ int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim);
 enum { K_GLOBAL, K_GIVEN, K_AUTO };
 // ina_blk.hip: the error-feedback launches (include/ina_ef.h; ina_ef.hip checks the arguments).  One
 // bucket quantised: x is fp32 (xtype 0) or INA_X16_*, q int32 or int16 (bits); V is the block of
-// K_GIVEN / K_AUTO, the slot of the int16 flags under K_GLOBAL (256 for int32 out).
+// K_GIVEN / K_AUTO, the slot of the int16 flags under K_GLOBAL (256 for int32 out).  The fields
+// ina_ef.hip's initialisers leave out are zero.
 struct EfQuant {
     const void* x;
     int xtype;
@@ -58,6 +59,8 @@ struct EfQuant {
     double lim;            // K_AUTO
     int V;
     uint8_t* ovf;          // int16 out: may be null
+    bool wire;             // include/ina_shard_ef.h: q holds int32 wire words q16 + (sat << 22); fp32 x,
+                           // no base, bits 32, K_GLOBAL or K_GIVEN
 };
 int ef_quantize(const EfQuant& c, ina_stream_t stream);
 // the scales alone over |(xs[w] - base) + rs[w]|; aligned: every xs[w] and rs[w] is 16-byte aligned

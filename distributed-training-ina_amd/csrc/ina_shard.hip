@@ -37,17 +37,10 @@ using u32x2 = u32x2_t;
 using f32x4 = f32x4_t;
 
 constexpr int kBlk = kHostBlock;
-constexpr int kWireShift = INA_I16_WIRE_SHIFT;   // 22
 constexpr int32_t kWireHalf = 1 << (kWireShift - 1);
 
-// the quantiser of ina_quantize_f32_i16_sat: sat16(rne(x * 2^k)), NaN -> 0 (flagged)
-__device__ __forceinline__ int32_t q16w(float x, float s) {
-    const float y = __builtin_rintf(x * s);
-    const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);   // one v_med3_f32
-    const int32_t v = (y != y) ? 0 : (int32_t)c;
-    const int32_t sat = !(c == y);               // clamped, +-inf or NaN
-    return v + (sat << kWireShift);
-}
+// (q16w, the wire word of one value, and kWireShift are in ina_device.h: the error-feedback wire
+// quantisers of include/ina_shard_ef.h, instances of the kernels of ina_blk.hip, run the same one)
 
 // decoded shard value: sum q16 and whether anything saturated (a rank, or the sum)
 __device__ __forceinline__ int32_t finish1(uint32_t w, bool& sat) {

@@ -178,6 +178,12 @@ SIGNATURES_EF = {
     "ina_quantize_pack_nga_multi_split_ef": [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp],
     "ina_quantize_pack_nga_multi_split_ef_blk": [_vp, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
 }
+# error feedback on the sharded int16 wire (include/ina_shard_ef.h): the wire siblings' arguments
+# with the residual after x
+SIGNATURES_SHARD_EF = {
+    "ina_quantize_ef_f32_i16_wire": [_vp, _vp, _vp, _sz, _i, _vp],
+    "ina_quantize_ef_blk_f32_i16_wire": [_vp, _vp, _vp, _i, _vp, _sz, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -194,7 +200,7 @@ def open_library(path: str) -> C.CDLL:
     lib = C.CDLL(path)
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
-                       **SIGNATURES_EF}.items():
+                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

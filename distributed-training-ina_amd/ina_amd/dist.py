@@ -45,6 +45,11 @@ ops.dequantize_blk).  Layout B: a rank holds all the summands of its range, so i
 reduce computes the scales and the all-gather carries them, one byte per block.  Either way the
 result equals one GPU's AUTO ops.quantize_reduce_blk / quantize_reduce_i16_blk over the same
 buckets, scales included; `kblk` holds the scales of the last call.
+
+error_feedback=True (ShardedAggregator only; include/ina_shard_ef.h, ina_amd.ef): the rank keeps what
+its rounding to the wire dropped in an fp32 residual on its GPU and adds it to the next step's
+bucket, in the quantiser's own launch.  The collectives, the decode and every byte on xGMI are those
+of the plain step: the residual never leaves the rank.
 """
 from __future__ import annotations
 
@@ -53,7 +58,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops
+from . import _lib, ef, ops
 
 
 class ShardPlan:
@@ -221,10 +226,18 @@ class ShardedAggregator:
     k="block": per-block scales (V values a block; the module docstring gives the sequence);
     `kblk` then holds the agreed scales of the last call and `scale_bytes` the bytes of their
     exchange.  Not with chunks > 1.
+    error_feedback=True: the rank owns `residual` (fp32 [n], zeros at first, reset_residual() zeroes
+    it again) and every quantise is the error-feedback one of ina_amd.ef -- v = grad + residual goes
+    to the wire and residual becomes v - dequantised(own wire value) (+0 where v is NaN or inf).
+    With k="block" the rank's scales are those of v (ef.block_scales) before the ranks take their
+    MIN; with chunks > 1 each chunk's quantise takes the matching slice of the residual.  Everything
+    after the quantise -- collectives, decode, gather, gather_bytes, scale_bytes -- is unchanged,
+    and with the default False so is every byte of the step.  Device buckets only.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
-                 wire: str = "i32", V: int = 256, collective: str = "rs_ag", chunks: int = 1):
+                 wire: str = "i32", V: int = 256, collective: str = "rs_ag", chunks: int = 1,
+                 error_feedback: bool = False):
         if wire not in ("i32", "i16"):
             raise ValueError("wire must be 'i32' or 'i16'")
         if collective not in ("rs_ag", "a2a", "allreduce"):
@@ -247,6 +260,10 @@ class ShardedAggregator:
         self.plan = ShardPlan(n, self.world, align)
         self.k, self.group, self.wire, self.V = k, group, wire, V
         dev = device or torch.device("cuda", torch.cuda.current_device())
+        self.error_feedback = bool(error_feedback)
+        if self.error_feedback and torch.device(dev).type != "cuda":
+            raise ValueError(f"error_feedback=True keeps its residual on the GPU and quantises there; the INA path "
+                             f"has no CPU fallback (device {torch.device(dev)})")
         self.chunks = chunks if self.world > 1 else 1
         tot = self.plan.padded
         if self.chunks > 1:
@@ -285,6 +302,8 @@ class ShardedAggregator:
         # the all-to-all's receive buffer (world slices of one shard each)
         self._recv = (torch.empty(self.plan.padded, dtype=torch.int32, device=dev)
                       if collective == "a2a" and self.world > 1 else None)
+        # error feedback: what this rank's rounding dropped, added to its next bucket
+        self.residual = torch.zeros(n, dtype=torch.float32, device=dev) if self.error_feedback else None
         if self.chunks > 1:
             m = self.chunks * self.sc
             self.sum_c = torch.empty(m, dtype=torch.int32, device=dev)
@@ -299,6 +318,12 @@ class ShardedAggregator:
         if b is None:
             b = self._shard_bufs[name] = torch.empty(self.plan.shard, dtype=dtype, device=self._dev)
         return b
+
+    def reset_residual(self):
+        """error_feedback=True: forget what earlier steps dropped (the residual back to zeros)."""
+        if self.residual is None:
+            raise AttributeError("a residual exists only with error_feedback=True")
+        self.residual.zero_()
 
     @property
     def sum_shard(self) -> torch.Tensor:
@@ -404,19 +429,41 @@ class ShardedAggregator:
         if grad.numel() != n:
             raise ValueError("bucket size changed")
         x = grad.reshape(-1)
+        r = self.residual
         if self.blk:
-            # this rank's scales for `world` summands, the MIN over ranks, then the wire
+            # this rank's scales for `world` summands (error feedback: of x + residual), the MIN over
+            # ranks, then the wire
             kb = self.kblk
-            ops.block_scales([x], self.V, bits=32 if self.wire == "i32" else 16, degree=self.world, out=kb)
+            bits = 32 if self.wire == "i32" else 16
+            if r is None:
+                ops.block_scales([x], self.V, bits=bits, degree=self.world, out=kb)
+            else:
+                ef.block_scales([x], [r], self.V, bits=bits, degree=self.world, out=kb)
             agree_block_scales(kb, self.group)
             if self.wire == "i32":
-                ops.quantize_blk(x, kb, self.V, out=self.q[:n])
-            else:
+                if r is None:
+                    ops.quantize_blk(x, kb, self.V, out=self.q[:n])
+                else:
+                    ef.quantize_blk(x, r, self.V, kblk=kb, out=self.q[:n])
+            elif r is None:
                 ops.quantize_i16_wire_blk(x, kb, self.V, out=self.q[:n])
-        elif self.wire == "i32":
-            ops.quantize(x, self.k, out=self.q[:n])
+            else:
+                ef.quantize_i16_wire_blk(x, r, kb, self.V, out=self.q[:n])
         else:
-            ops.quantize_i16_wire(x, self.k, out=self.q[:n])
+            self._quantize_global(x, r, self.q[:n])
+
+    def _quantize_global(self, x: torch.Tensor, r, out: torch.Tensor):
+        """x (the bucket or a chunk of it) to the wire at the global k; r: the same values of the
+        residual, or None without error feedback."""
+        if self.wire == "i32":
+            if r is None:
+                ops.quantize(x, self.k, out=out)
+            else:
+                ef.quantize(x, r, self.k, out=out)
+        elif r is None:
+            ops.quantize_i16_wire(x, self.k, out=out)
+        else:
+            ef.quantize_i16_wire(x, r, self.k, out=out)
 
     def _decode(self, src: torch.Tensor, y: torch.Tensor, ovf=None):
         """The whole (padded) bucket: one rank, or after an all-reduce."""
@@ -437,11 +484,9 @@ class ShardedAggregator:
         rs = []
         for c in range(self.chunks):           # quantise chunk c, then its RS on RCCL's stream
             lo, hi = c * L, min((c + 1) * L, n)
-            if hi > lo:
-                if self.wire == "i32":
-                    ops.quantize(x[lo:hi], self.k, out=self._qbuf[lo:hi])
-                else:
-                    ops.quantize_i16_wire(x[lo:hi], self.k, out=self._qbuf[lo:hi])
+            if hi > lo:         # (lo is a multiple of align: the slices stay on the vector path)
+                self._quantize_global(x[lo:hi], None if self.residual is None else self.residual[lo:hi],
+                                      self._qbuf[lo:hi])
             rs.append(reduce_scatter_sum(self._qbuf[c * L:(c + 1) * L], self.cplan, self.group,
                                          out=self.sum_c[c * sc:(c + 1) * sc], async_op=True)[1])
         ag = []
@@ -481,7 +526,9 @@ class ShardedAggregator:
     def aggregate_int(self, grad: torch.Tensor) -> torch.Tensor:
         """fp32 [n] -> this rank's integer shard of the aggregate (no gather): the
         int32 wrapped sum, or on the i16 wire the int16 saturated sum (its slot flags
-        in `ovf_shard`).  k="block": the integers are scaled per block; read `kblk` next to them."""
+        in `ovf_shard`).  k="block": the integers are scaled per block; read `kblk` next to them.
+        error_feedback=True: this is a step like any other -- it quantises grad + residual and
+        advances the residual."""
         self._quantize(grad)
         if self.collective == "a2a":
             s = reduce_scatter_a2a(self.q, self.plan, self.group, out=self.sum_shard, recv=self._recv)
@@ -507,6 +554,10 @@ class RangeAggregator:
     ranges hold whole slots.  k="block": the fused reduces in AUTO mode (ops.quantize_reduce_blk /
     quantize_reduce_i16_blk, degree = W) with one scale per block of V values; the all-gather also
     carries the shard's scales and `kblk` holds the bucket's after a call.
+    No error feedback here, and no such argument: a rank holds OTHER workers' slices, and the
+    residual of a slice lives with the worker that rounded it, not with the GPU that sums it (the
+    reason include/ina_ef.h gives for leaving out the fused quantise + reduce calls).  A worker that
+    wants it applies ina_amd.ef before it sends its slices.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,

@@ -15,6 +15,7 @@ that function's bit for bit.  The switch and the PS see plain integers, as befor
         q = ef.quantize(grad, r, k)                       # r updated in place
         kblk = ef.block_scales([grad], [r], V)            # then MIN across ranks
         q, kblk = ef.quantize_blk(grad, r, V, kblk=kblk)
+        wire = ef.quantize_i16_wire(grad, r, k)           # the sharded int16 wire's words
 
 x is float32, bfloat16 or float16 on the global-k quantisers and float32 everywhere else; resid and
 base are float32.  No CPU fallback.
@@ -168,6 +169,47 @@ def quantize_i16_blk(x: torch.Tensor, resid: torch.Tensor, V: int, kblk: torch.T
                                                  degree, V, out.data_ptr(), x.numel(), overflow.data_ptr(),
                                                  _stream(x)), "ef.quantize_i16_blk")
     return out, overflow, kblk
+
+
+def _wire_x(x):
+    """The sharded int16 wire has no 16-bit source path: a bf16 / fp16 tensor is refused as such."""
+    if isinstance(x, torch.Tensor) and x.dtype in _X16:
+        raise ValueError(f"the sharded int16 wire takes fp32 buckets: x is {x.dtype}")
+    _req(x, torch.float32, "x")
+
+
+def _wire_out(x: torch.Tensor, out):
+    out = torch.empty(x.shape, dtype=torch.int32, device=x.device) if out is None else out
+    _fits(out, x.numel())
+    _req(out, torch.int32, "out")
+    _same_device(x, out)
+    return out
+
+
+def quantize_i16_wire(x: torch.Tensor, resid: torch.Tensor, k: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """ops.quantize_i16_wire of x + resid (include/ina_shard_ef.h): the int32 wire words q16 +
+    (saturated << 22) of dist.ShardedAggregator(wire="i16", error_feedback=True).  resid becomes
+    v - float(q16) * 2^-k: the word's q16, never its count bits.  fp32 only."""
+    _wire_x(x)
+    _resid(resid, x)
+    out = _wire_out(x, out)
+    check(load().ina_quantize_ef_f32_i16_wire(x.data_ptr(), resid.data_ptr(), out.data_ptr(), x.numel(), k,
+                                              _stream(x)), "ef.quantize_i16_wire")
+    return out
+
+
+def quantize_i16_wire_blk(x: torch.Tensor, resid: torch.Tensor, kblk: torch.Tensor, V: int,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+    """ops.quantize_i16_wire_blk of x + resid with the given scales (the ranks agree on them first:
+    the MIN of their ef.block_scales([x], [resid], V, bits=16, degree=world))."""
+    V = _blk_v(V)
+    _wire_x(x)
+    _resid(resid, x)
+    kblk = _blk_scales_arg(kblk, (x.numel() + V - 1) // V, x, given=True)
+    out = _wire_out(x, out)
+    check(load().ina_quantize_ef_blk_f32_i16_wire(x.data_ptr(), resid.data_ptr(), kblk.data_ptr(), V, out.data_ptr(),
+                                                  x.numel(), _stream(x)), "ef.quantize_i16_wire_blk")
+    return out
 
 
 def quantize_pack_nga_multi_split(xs, resids, k, V: int, bitmaps, count: int, switch_id: int, seq0,

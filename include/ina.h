@@ -492,6 +492,10 @@ int ina_recv_packets_split_fd(int fd, uint8_t* host_hdr, uint8_t* host_pay, size
 int ina_recv_packets_fd(int fd, uint8_t* host_pkts, size_t max_pkts, size_t stride, size_t skip,
                         int timeout_ms, uint32_t* lens);
 
+/* Error feedback on the int16 wire of a sharded bucket (the wire quantisers with a residual); the
+ * contract is stated in ina_shard_ef.h. */
+#include "ina_shard_ef.h"   /* ina_quantize_ef_f32_i16_wire / ina_quantize_ef_blk_f32_i16_wire */
+
 /* Error feedback: the quantisers and the split worker packs with a residual carried on the device
  * from step to step; the contract is stated in ina_ef.h. */
 #include "ina_ef.h"   /* the ina_quantize_ef_* / ina_*_ef entry points */

@@ -38,8 +38,9 @@
  * aligned, as their siblings do.
  *
  * Not here: the fused quantise + reduce calls (their W residuals belong to workers that share the
- * GPU), the sharded int16 wire, the packed-row multi-worker pack, 16-bit sources on the
- * block-scaled and pack calls, the switch and the PS, which only see integers.
+ * GPU), the packed-row multi-worker pack, 16-bit sources on the block-scaled and pack calls, the
+ * switch and the PS, which only see integers.  The sharded int16 wire's quantisers are in
+ * ina_shard_ef.h.
  */
 #ifndef INA_EF_H
 #define INA_EF_H

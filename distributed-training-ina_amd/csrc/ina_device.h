@@ -9,14 +9,14 @@ namespace ina {
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
-// Streaming stores of the one-pass reduce and elementwise kernels.  INA_STORE_SC1 = 1: stores with
-// the sc1 cache-policy bit (write-through at system scope), so a launch leaves no dirty lines for the next
+// Streaming stores of the one-pass reduce and elementwise kernels: stores with the sc1
+// cache-policy bit (write-through at system scope), so a launch leaves no dirty lines for the next
 // dependent launch's boundary to drain (MI355X_MICROARCH.md: a boundary costs + B / 6 TB/s
 // when the predecessor leaves B bytes dirty).  The headline reduce, interleaved on two
 // boxes (tools/lab/store_policy_lab.py, profiles/r03/lab/store_policy_lab*.log): back to
 // back 151.7 -> 150.9 and 149.2 -> 147.1 us, single launches 157.2 -> 153.1 and
-// 152.7 -> 148.5 us against nt stores; default-policy stores 155.8-156.4.
-// INA_STORE_SC1 = 0: the non-temporal (nt) stores of rounds 1-2.
+// 152.7 -> 148.5 us against the non-temporal (nt) stores of rounds 1-2; default-policy stores
+// 155.8-156.4.
 //
 // The sc1 store is a compiler builtin (`__builtin_amdgcn_raw_buffer_store_b*`, aux bit 4 =
 // SC1 on gfx950), never inline asm: the compiler then owns the store's wait states and
@@ -33,9 +33,6 @@ typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 // split the unrolled loop and doubled its registers; profiles/r04/lab/store_builtin_lab.log).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
 #error "stream_store's SC1 cache-policy bit (aux bit 4) is the gfx942 / gfx950 encoding"
-#endif
-#ifndef INA_STORE_SC1
-#define INA_STORE_SC1 1
 #endif
 // buffer resource word 3 for a raw (stride 0, untyped) gfx9 buffer: 32-bit data format
 constexpr int kRawBufferWord3 = 0x00020000;
@@ -62,7 +59,6 @@ static inline unsigned long long take_store_violations() {
 #endif
 template <typename T>
 __device__ __forceinline__ void stream_store(T v, T* p) {
-#if INA_STORE_SC1
     static_assert(sizeof(T) == 16 || sizeof(T) == 8 || sizeof(T) == 4, "16, 8 or 4-byte stores");
     const uint64_t a = (uint64_t)(uintptr_t)p;
     // (readfirstlane returns int: each half goes through uint32_t, or the low half's bit 31
@@ -83,27 +79,15 @@ __device__ __forceinline__ void stream_store(T v, T* p) {
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), r, (int)d, 0, kAuxSC1);
     else
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, (int)d, 0, kAuxSC1);
-#else
-    __builtin_nontemporal_store(v, p);
-#endif
 }
 
 // Packet kernels (pack / unpack of NGA rows) keep non-temporal stores: their rows are the
 // next launch's input (the switch, the sender), and write-through made the fused worker
 // pack 9 % slower in the packet path (54.7 -> 59.6 us per launch beside the switch,
 // profiles/r03/lab/path_store_lab.log).
-#ifndef INA_PACKET_STORE
-#define INA_PACKET_STORE 0            // 0 non-temporal, 1 write-through (stream_store), 2 default
-#endif
 template <typename T>
 __device__ __forceinline__ void packet_store(T v, T* p) {
-#if INA_PACKET_STORE == 1
-    stream_store(v, p);
-#elif INA_PACKET_STORE == 2
-    *p = v;
-#else
     __builtin_nontemporal_store(v, p);
-#endif
 }
 
 
@@ -119,24 +103,12 @@ __device__ __forceinline__ int32_t q32(float x, float s) {
 }
 
 // returns the int16 value widened to int32; *sat |= clamped-or-NaN
-#ifndef INA_Q16_MED3
-#define INA_Q16_MED3 1
-#endif
 __device__ __forceinline__ int32_t q16(float x, float s, bool& sat) {
     float y = __builtin_rintf(x * s);
-#if INA_Q16_MED3
     // one v_med3_f32 clamps; a clamped value, +-inf or NaN differs from y
     const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);
     sat |= !(c == y);
     return (y != y) ? 0 : (int32_t)c;
-#else
-    bool in = (y <= 32767.0f) && (y >= -32768.0f);  // false for NaN
-    sat |= !in;
-    int32_t r = in ? (int32_t)y : 0;
-    r = (y > 32767.0f) ? 32767 : r;
-    r = (y < -32768.0f) ? -32768 : r;
-    return r;
-#endif
 }
 
 __device__ __forceinline__ int32_t sat16(int32_t a, bool& sat) {
@@ -177,7 +149,7 @@ __device__ __forceinline__ void write_slot_flags8(unsigned long long m, bool act
     if (active && (lane & (lanes_per_slot - 1)) == 0) ovf[elem0 / (size_t)V] = (m & gm) ? 1 : 0;
 }
 
-// the same for the split layout of the int16 kernels (INA_Q16_SPLIT, ina_kernels.hip: a wave owns
+// the same for the split layout of the int16 kernels (ina_kernels.hip: a wave owns
 // 512 values, lane l holds 4 at 4l of each 256-value half): a slot is V/4 adjacent lanes of one
 // half, or both halves at V = 512
 __device__ __forceinline__ void write_slot_flags_split(unsigned long long ma, unsigned long long mb,

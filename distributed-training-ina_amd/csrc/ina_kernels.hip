@@ -54,21 +54,12 @@ static std::atomic<int> g_unroll{0};   // 0 = per-W choice (launch_reduce_u)
 // 16-byte chunks in flight per thread in the one-in one-out elementwise kernels
 // (quantise, dequantise, PS apply): one, with the 8192-workgroup grid striding, beat 2
 // and 4 -- quantise 40.9 -> 37.6 us, dequantise 41.2 -> 36.8 (tools/lab/ew_lab.py)
-#ifndef INA_EW_U
-#define INA_EW_U 1
-#endif
-constexpr int kEwU = INA_EW_U;
+constexpr int kEwU = 1;
 // PS combine kernels, W <= 4 (tools/lab/ew_lab.py, C2 size): one chunk in flight --
 // fp32 combine 94.3 -> 91.9 us at 256 workgroups, INA combine 106.4 -> 93.2 us at 8192
-#ifndef INA_COMB_U
-#define INA_COMB_U 1
-#endif
-#ifndef INA_COMBI_U
-#define INA_COMBI_U 1
-#endif
-#ifndef INA_QR_U
-#define INA_QR_U 1     // fused quantise + reduce, W <= 8: C2 91.8 -> 86.7 us (ew_lab)
-#endif
+constexpr int kCombU = 1;
+constexpr int kCombiU = 1;
+constexpr int kQrU = 1;     // fused quantise + reduce, W <= 8: C2 91.8 -> 86.7 us (ew_lab)
 // the flat packet kernels (pack, fused quantise + pack, unpack; one 16-byte chunk per thread,
 // grid-striding) and the fused quantise + reduce for W > 8: 16,384 workgroups beat 8,192 by
 // 1-3 % on two boxes (pack 34.9 -> 33.9 us, worker pack 51.5 -> 50.8, unpack 36.6 -> 35.6;
@@ -118,9 +109,6 @@ __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32
 // int16 kernels: a wave covers 512 values as two 256-value halves (16 B per lane per
 // load, contiguous per instruction) -- C4 fused quantise+reduce 289 -> 251 us against
 // 8 consecutive values per lane (32-B lane stride; tools/lab/ew_lab.py, lab/q16_lab.log)
-#ifndef INA_Q16_SPLIT
-#define INA_Q16_SPLIT 1
-#endif
 // (write_slot_flags_split, the flags of that layout, is in ina_device.h: ina_ef.hip writes them too)
 
 // Cross-lane moves by one lane are DPP row moves (measured on gfx950, tools/lab/dpp_lab.hip):
@@ -298,14 +286,13 @@ __global__ __launch_bounds__(kBlock) void k_quantize_i32(const float* __restrict
         q[i] = q32(x[i], s);
 }
 
-// int16: thread owns 8 values (two float4 loads, one 16-byte store)
+// int16: lane owns 4 values of each half of its wave's 512 (two float4 loads, two 8-byte stores)
 __global__ __launch_bounds__(kBlock) void k_quantize_i16_vec(const float* __restrict__ x,
                                                              int16_t* __restrict__ q, size_t n,
                                                              float s, int V, int lanes_per_slot,
                                                              uint8_t* __restrict__ ovf) {
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * kBlock;
-#if INA_Q16_SPLIT
     // a wave owns 512 consecutive values, lane l the 4 at 4l of each 256-value half (one
     // contiguous KiB per load instruction); see k_quant_reduce_i16
     const int lane = (int)(tid & 63);
@@ -330,35 +317,6 @@ __global__ __launch_bounds__(kBlock) void k_quantize_i16_vec(const float* __rest
         const unsigned long long ma = __ballot(sa), mb = __ballot(sb);   // wave-convergent
         if (ovf) write_slot_flags_split(ma, mb, eA, eB, n, V, ovf);
     }
-#else
-    const size_t n8 = (n + 7) / 8;
-    // uniform trip count per wave so every lane reaches the ballot together
-    const size_t wave0 = tid & ~(size_t)63;
-    for (size_t base = wave0; base < n8; base += stride) {
-        size_t i = base + (tid & 63);
-        bool sat = false;
-        if (i < n8) {
-            size_t e = 8 * i;
-            int32_t r[8];
-            if (e + 8 <= n) {
-                f32x4 a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + e));
-                f32x4 b = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + e) + 1);
-                r[0] = q16(a.x, s, sat); r[1] = q16(a.y, s, sat); r[2] = q16(a.z, s, sat); r[3] = q16(a.w, s, sat);
-                r[4] = q16(b.x, s, sat); r[5] = q16(b.y, s, sat); r[6] = q16(b.z, s, sat); r[7] = q16(b.w, s, sat);
-                u32x4 o;
-                o.x = (uint32_t)(uint16_t)r[0] | ((uint32_t)r[1] << 16);
-                o.y = (uint32_t)(uint16_t)r[2] | ((uint32_t)r[3] << 16);
-                o.z = (uint32_t)(uint16_t)r[4] | ((uint32_t)r[5] << 16);
-                o.w = (uint32_t)(uint16_t)r[6] | ((uint32_t)r[7] << 16);
-                stream_store(o, reinterpret_cast<u32x4*>(q + e));
-            } else {
-                for (size_t j = e; j < n; ++j) q[j] = (int16_t)q16(x[j], s, sat);
-            }
-        }
-        unsigned long long m = __ballot(sat);   // wave-convergent: uniform trip count
-        if (ovf) write_slot_flags8(m, i < n8, 8 * i, V, lanes_per_slot, ovf);
-    }
-#endif
 }
 
 // generic int16 path (unaligned or V without a ballot layout): byte flags via a
@@ -434,7 +392,7 @@ __global__ __launch_bounds__(kBlock) void k_quant_reduce_i32(PtrPack<float> in, 
     size_t n4 = vec ? n / 4 : 0;
     u32x4* o4 = reinterpret_cast<u32x4*>(out);
     if constexpr (W > 0) {
-        chunk_loop<(W <= 8 ? INA_QR_U : 2)>(n4, [&]<int UU>(size_t i, size_t st) {
+        chunk_loop<(W <= 8 ? kQrU : 2)>(n4, [&]<int UU>(size_t i, size_t st) {
             f32x4 v[W][UU];
 #pragma unroll
             for (int w = 0; w < W; ++w)
@@ -472,7 +430,7 @@ __global__ __launch_bounds__(kBlock) void k_quant_reduce_i32(PtrPack<float> in, 
     }
 }
 
-// int16: thread owns 8 values; each worker value saturates at quantisation (wire
+// int16: each worker value saturates at quantisation (wire
 // width), exact int32 sum, one final saturation; per-slot flag = any saturation.
 template <int W>
 __global__ __launch_bounds__(kBlock) void k_quant_reduce_i16(PtrPack<float> in, int Wd,
@@ -483,7 +441,6 @@ __global__ __launch_bounds__(kBlock) void k_quant_reduce_i16(PtrPack<float> in, 
     const size_t stride = (size_t)gridDim.x * kBlock;
     const int nw = W > 0 ? W : Wd;
     constexpr int UNR = W > 0 ? W : 1;
-#if INA_Q16_SPLIT
     // a wave owns 512 consecutive values: lane l holds 4l..4l+3 of each 256-value half, so
     // every load instruction of the wave reads 1 KiB contiguous (16 B per lane, no 32-B
     // lane stride); the two halves' saturation ballots give the slot flags
@@ -525,43 +482,6 @@ __global__ __launch_bounds__(kBlock) void k_quant_reduce_i16(PtrPack<float> in, 
         const unsigned long long ma = __ballot(sa), mb = __ballot(sb);   // wave-convergent
         if (ovf) write_slot_flags_split(ma, mb, eA, eB, n, V, ovf);
     }
-#else
-    const size_t n8 = (n + 7) / 8;
-    const size_t wave0 = tid & ~(size_t)63;
-    for (size_t base = wave0; base < n8; base += stride) {
-        size_t i = base + (tid & 63);
-        bool sat = false;
-        if (i < n8) {
-            size_t e = 8 * i;
-            if (e + 8 <= n) {
-                int32_t a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll UNR
-                for (int w = 0; w < nw; ++w) {
-                    f32x4 u = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(in.p[w] + e));
-                    f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(in.p[w] + e) + 1);
-                    a[0] += q16(u.x, s, sat); a[1] += q16(u.y, s, sat);
-                    a[2] += q16(u.z, s, sat); a[3] += q16(u.w, s, sat);
-                    a[4] += q16(v.x, s, sat); a[5] += q16(v.y, s, sat);
-                    a[6] += q16(v.z, s, sat); a[7] += q16(v.w, s, sat);
-                }
-                u32x4 o;
-                o.x = (uint32_t)(uint16_t)sat16(a[0], sat) | ((uint32_t)sat16(a[1], sat) << 16);
-                o.y = (uint32_t)(uint16_t)sat16(a[2], sat) | ((uint32_t)sat16(a[3], sat) << 16);
-                o.z = (uint32_t)(uint16_t)sat16(a[4], sat) | ((uint32_t)sat16(a[5], sat) << 16);
-                o.w = (uint32_t)(uint16_t)sat16(a[6], sat) | ((uint32_t)sat16(a[7], sat) << 16);
-                stream_store(o, reinterpret_cast<u32x4*>(out + e));
-            } else {
-                for (size_t j = e; j < n; ++j) {
-                    int32_t a = 0;
-                    for (int w = 0; w < nw; ++w) a += q16(in.p[w][j], s, sat);
-                    out[j] = (int16_t)sat16(a, sat);
-                }
-            }
-        }
-        unsigned long long m = __ballot(sat);   // wave-convergent: uniform trip count
-        if (ovf) write_slot_flags8(m, i < n8, 8 * i, V, lanes_per_slot, ovf);
-    }
-#endif
 }
 
 __global__ __launch_bounds__(kBlock) void k_quant_reduce_i16_scalar(PtrPack<float> in, int W,
@@ -648,7 +568,7 @@ __global__ __launch_bounds__(kBlock) void k_ps_combine_f32(const float* __restri
     size_t n4 = vec ? n / 4 : 0;
     const f32x4* l4 = reinterpret_cast<const f32x4*>(local);
     f32x4* o4 = reinterpret_cast<f32x4*>(out);
-    chunk_loop<(W > 0 && W <= 4) ? INA_COMB_U : 2>(n4, [&]<int UU>(size_t i, size_t st) {
+    chunk_loop<(W > 0 && W <= 4) ? kCombU : 2>(n4, [&]<int UU>(size_t i, size_t st) {
         f32x4 l[UU], acc[UU];
 #pragma unroll
         for (int u = 0; u < UU; ++u) { l[u] = l4[i + u * st]; acc[u] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -722,7 +642,7 @@ __global__ __launch_bounds__(kBlock) void k_ps_combine_ina(const float* __restri
                                                            int vec) {
     const int nw = W > 0 ? W : Wd;
     size_t n4 = vec ? n / 4 : 0;
-    chunk_loop<(W > 0 && W <= 4) ? INA_COMBI_U : 2>(n4, [&]<int UU>(size_t i, size_t st) {
+    chunk_loop<(W > 0 && W <= 4) ? kCombiU : 2>(n4, [&]<int UU>(size_t i, size_t st) {
         f32x4 l[UU];
         u32x4 acc[UU];
 #pragma unroll
@@ -890,18 +810,8 @@ constexpr uint32_t kSelWire = 0x07000102u;   // perm(next, v): {v.b2, v.b1, v.b0
 // 16-byte chunks in flight per thread in the flat packet kernels: one (with an 8192-
 // workgroup grid striding over the rest, now 16,384: g_stream_blocks) beat 2, 4 and 8 -- fused worker pack 57.7 -> 54.2
 // us, pack 37.5 -> 36.5, unpack 40.4 -> 39.1 (tools/lab/apply_lab.py, lab/pack_u_lab.log)
-#ifndef INA_PACK_U
-#define INA_PACK_U 1
-#endif
-#ifndef INA_UNPACK_U
-#define INA_UNPACK_U 1
-#endif
-#ifndef INA_PACK_DESC_SPLIT
-#define INA_PACK_DESC_SPLIT 1
-#endif
-#ifndef INA_UNPACK_HDR_SPLIT
-#define INA_UNPACK_HDR_SPLIT 1
-#endif
+constexpr int kPackU = 1;
+constexpr int kUnpackU = 1;
 
 // The header: the 15 wire bytes of packet `seq` as four little-endian words, byte 15 zero.
 // fcs = count | flags << 8 | switch_id << 16; a descriptor (header bytes 4..11, ina.h) is
@@ -945,7 +855,6 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_flat(Src src, size_t n, Nga
     const uint32_t wave0 = (blockIdx.x * kBlock + threadIdx.x) & ~63u;
     const size_t V = (size_t)h.V;
     u32x4* ch = reinterpret_cast<u32x4*>(pkts);
-#if INA_PACK_DESC_SPLIT
     // descriptors (header bytes 4..11) depend on the packet number alone: a thread per
     // packet writes them, consecutive lanes consecutive entries (coalesced), instead of one
     // 8-byte store from each packet's chunk-0 lane (the unpack header fields' pattern)
@@ -960,7 +869,6 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_flat(Src src, size_t n, Nga
             desc[p] = u32x2{count | (flags << 8) | (bi << 16), (bi >> 16) | (sw << 16) | (bf << 24)};
         }
     }
-#endif
     for (uint32_t base = wave0; base < nch; base += U * gs) {
         u32x4 v[U];
         uint32_t nx0[U];
@@ -1002,7 +910,6 @@ __global__ __launch_bounds__(kBlock) void k_pack_nga_flat(Src src, size_t n, Nga
                 o.y = count | (flags << 8) | (bi << 16);
                 o.z = (bi >> 16) | (sw << 16) | (bf << 24);
                 o.w = (bf >> 8) | (nx & 0xFF000000u);        // value 0's top byte at byte 15
-                if (desc && !INA_PACK_DESC_SPLIT) desc[p] = u32x2{o.y, o.z};   // header bytes 4..11 (ina.h)
             } else if (c <= L) {
                 o = wire4(v[u], nx);
             } else {
@@ -1128,12 +1035,8 @@ __global__ __launch_bounds__(kBlock) void k_nga_make_desc(DescGroup a, int G, ui
 // packet, so no lane loads anything twice or alone; lane 0 also writes the header chunk.
 // (one launch, 8 workers, config 3: 343 -> 329 us, the steady packet-path step 587 -> 563 us;
 // write-through or default-policy stores are slower in both layouts, qpack_multi_lab.log)
-#ifndef INA_QPM_PPW
-#define INA_QPM_PPW 1
-#endif
-#ifndef INA_QPM_PPW_BLOCKS
-#define INA_QPM_PPW_BLOCKS (1 << 20)      // a covering grid (a wave per packet)
-#endif
+constexpr int kQpmPpw = 1;
+constexpr int kQpmPpwBlocks = 1 << 20;      // a covering grid (a wave per packet)
 // (amdgpu_waves_per_eu 6 / 7 -- 74 / 71 VGPRs against 87 -- gained nothing,
 // profiles/r03/lab/qpack_occupancy_lab.log)
 template <int G>
@@ -1453,9 +1356,7 @@ __global__ __launch_bounds__(kBlock) void k_unpack_nga_split_vals(const u32x4* _
 // One worker's NGA-256 packets, a wave per packet (the layout of k_qpack_nga_multi_v256):
 // fp32 quantised on the fly (int32 words and the per-packet overflow flag are supported; the
 // int32 pack is faster on the flat stream, see pack_nga_launch).
-#ifndef INA_PACK_PPW
-#define INA_PACK_PPW 1
-#endif
+constexpr int kPackPpw = 1;
 template <typename Src>
 __global__ __launch_bounds__(kBlock) void k_pack_nga_v256(Src src, size_t n, NgaHdr h,
                                                           const uint8_t* __restrict__ ovf,
@@ -1584,7 +1485,6 @@ __global__ __launch_bounds__(kBlock) void k_unpack_nga_flat(const uint8_t* __res
     const int lane = threadIdx.x & 63;
     const uint32_t wave0 = (blockIdx.x * kBlock + threadIdx.x) & ~63u;
     const u32x4* ch = reinterpret_cast<const u32x4*>(pkts);
-#if INA_UNPACK_HDR_SPLIT
     // header fields by a thread per packet: consecutive lanes store consecutive SoA
     // entries.  The chunk-0 lane's six narrow stores (one packet per wave, every field
     // line written from many waves) cost 13 % (profiles/r01/lab/unpack_out_lab.log);
@@ -1596,7 +1496,6 @@ __global__ __launch_bounds__(kBlock) void k_unpack_nga_flat(const uint8_t* __res
             nga_store_header(f, p, hv.x, hv.y, hv.z, hv.w);
         }
     }
-#endif
     for (uint32_t base = wave0; base < nch; base += U * gs) {
         u32x4 a[U];
         uint32_t pw0[U];
@@ -1614,9 +1513,7 @@ __global__ __launch_bounds__(kBlock) void k_unpack_nga_flat(const uint8_t* __res
                                                                       0xF, 0xF, false);
             if (t >= nch) continue;
             const uint32_t p = t / C, c = t - p * C;
-            if (c == 0) {
-                if (hdr && !INA_UNPACK_HDR_SPLIT) nga_store_header(f, p, a[u].x, a[u].y, a[u].z, a[u].w);
-            } else if (c <= L && vals) {
+            if (c != 0 && c <= L && vals) {          // chunk 0 is the header (above)
                 u32x4 o;
                 o.x = __builtin_amdgcn_perm(a[u].x, pw, kSelBE);
                 o.y = __builtin_amdgcn_perm(a[u].y, a[u].x, kSelBE);
@@ -1646,18 +1543,9 @@ __global__ __launch_bounds__(kBlock) void k_unpack_nga_flat(const uint8_t* __res
 // 1 in 8 packets completed): batch 4 with the local rows prefetched 56.7 us; batch 8
 // without prefetch 66.8, with prefetch 81.9 (VGPRs); 16-packet windows spread the
 // completed packets of a dense stream over more waves than 64-packet ones
-#ifndef INA_APPLY_BATCH
-#define INA_APPLY_BATCH 4
-#endif
-#ifndef INA_APPLY_WIN
-#define INA_APPLY_WIN 16
-#endif
-#ifndef INA_APPLY_MW
-#define INA_APPLY_MW 1
-#endif
-static_assert(64 % INA_APPLY_WIN == 0, "windows tile the wave's 64 lanes");
-constexpr int kApB = INA_APPLY_BATCH;
-constexpr int kApWin = INA_APPLY_WIN;   // packets per window (<= 64)
+constexpr int kApB = 4;
+constexpr int kApWin = 16;   // packets per window (<= 64)
+static_assert(64 % kApWin == 0, "windows tile the wave's 64 lanes");
 
 // BLK (include/ina_pkt_blk.h): the dequantise scale is 2^-kblk[slot], one wave-uniform byte load
 // per completed packet (the slot comes out of readfirstlane), in place of `inv`.
@@ -1677,7 +1565,6 @@ __global__ __launch_bounds__(kBlock) void k_apply_completed_nga(
     [[maybe_unused]] const int chn = 1 + (vl ? lane : 0);
     const uint32_t wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t nwaves = (gridDim.x * kBlock) >> 6;
-#if INA_APPLY_MW
     // one action load covers this wave's next 64 / kApWin windows (lane l: window l /
     // kApWin of the group, packet l % kApWin), so a stream whose completed packets sit in
     // one region does not pay a round trip per empty window
@@ -1686,11 +1573,6 @@ __global__ __launch_bounds__(kBlock) void k_apply_completed_nga(
     for (size_t w0 = (size_t)wave * kApWin; w0 < npk; w0 += kG * S) {
         const size_t p = w0 + (size_t)(lane / kApWin) * S + (size_t)(lane % kApWin);
         unsigned long long m = __ballot(p < npk && actions[p] == INA_ACT_FWD_AGG);
-#else
-    for (uint32_t w0 = wave * kApWin; w0 < npk; w0 += nwaves * kApWin) {
-        const uint32_t p = w0 + (uint32_t)lane;
-        unsigned long long m = __ballot(lane < kApWin && p < npk && actions[p] == INA_ACT_FWD_AGG);
-#endif
         while (m) {
             uint32_t pid[kApB];
             int nb = 0;
@@ -1698,11 +1580,7 @@ __global__ __launch_bounds__(kBlock) void k_apply_completed_nga(
             for (int b = 0; b < kApB; ++b) {
                 if (m) {
                     const uint32_t bit = (uint32_t)__builtin_ctzll(m);
-#if INA_APPLY_MW
                     pid[b] = (uint32_t)(w0 + (size_t)(bit / kApWin) * S + (bit % kApWin));
-#else
-                    pid[b] = w0 + bit;
-#endif
                     m &= m - 1;
                     nb = b + 1;
                 } else {
@@ -1904,19 +1782,15 @@ __device__ __forceinline__ float absdiff(float x, const float* base, size_t i) {
     return fabsf(base ? __fsub_rn(x, base[i]) : x);
 }
 
-#ifndef INA_ABSMAX_U
-#define INA_ABSMAX_U 4
-#endif
-#ifndef INA_ABSMAX_BLOCKS
-#define INA_ABSMAX_BLOCKS kFaninBlocks
-#endif
+constexpr int kAbsmaxU = 4;
+constexpr int kAbsmaxBlocks = kFaninBlocks;
 __global__ __launch_bounds__(kBlock) void k_absmax_f32(const float* __restrict__ x,
                                                        const float* __restrict__ base, size_t n,
                                                        int vec, uint32_t* __restrict__ out) {
     __shared__ float part[kBlock / 64];
     const size_t n4 = vec ? n / 4 : 0;
     float m = 0.0f;
-    chunk_loop<INA_ABSMAX_U>(n4, [&]<int UU>(size_t i, size_t st) {
+    chunk_loop<kAbsmaxU>(n4, [&]<int UU>(size_t i, size_t st) {
         f32x4 a[UU], b[UU];
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
@@ -1993,9 +1867,7 @@ __global__ __launch_bounds__(kBlock) void k_absmax_multi_f32(PtrPack<float> xs, 
         atomicMax(out, __float_as_uint(r));
     }
 }
-#ifndef INA_ABSMAX_MULTI_BLOCKS
-#define INA_ABSMAX_MULTI_BLOCKS 512
-#endif
+constexpr int kAbsmaxMultiBlocks = 512;
 
 }  // namespace ina
 
@@ -2049,14 +1921,14 @@ static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina
             // the int32 pack stays on the flat stream (36.5 -> 39.1 us with a wave per
             // packet: one 16-byte load per lane leaves too little in flight),
             // profiles/r03/lab/pack_ppw_lab.log
-            if (INA_PACK_PPW && kQuantSrc<Src> && V == 256 && C <= 65 + 64) {
+            if (kPackPpw && kQuantSrc<Src> && V == 256 && C <= 65 + 64) {
                 hipLaunchKernelGGL((k_pack_nga_v256<Src>), dim3(grid_for(np * 64, 1, cap > 0 ? cap : 1 << 20)), dim3(kBlock), 0, s,
                                    src.shifted(v0), n - v0, hp, ovf ? ovf + p0 : nullptr, pkts + p0 * pstride,
                                    (uint32_t)pstride, (uint32_t)np,
                                    desc ? reinterpret_cast<u32x2*>(desc + p0) : nullptr);
                 continue;
             }
-            hipLaunchKernelGGL((k_pack_nga_flat<Src, INA_PACK_U>), dim3(grid_for(np * C, INA_PACK_U, cap > 0 ? std::min(cap, g_stream_blocks.load()) : g_stream_blocks.load())),
+            hipLaunchKernelGGL((k_pack_nga_flat<Src, kPackU>), dim3(grid_for(np * C, kPackU, cap > 0 ? std::min(cap, g_stream_blocks.load()) : g_stream_blocks.load())),
                                dim3(kBlock), 0, s, src.shifted(v0), n - v0, hp, ovf ? ovf + p0 : nullptr,
                                pkts + p0 * pstride, (uint32_t)C, (uint32_t)(V / 4), (uint32_t)(np * C),
                                desc ? reinterpret_cast<u32x2*>(desc + p0) : nullptr);
@@ -2361,7 +2233,7 @@ int ina_quantize_reduce_f32_i32(const float* const* bufs, int W, int32_t* out, s
     // W <= 8: one 16-byte chunk per stream per thread and a grid covering the bucket (C2,
     // back to back: 86.2 us against 88.7 at 8192 workgroups and 87.9-96.7 at 256-2048,
     // tools/lab/ew16_lab.py, profiles/r03/lab/ew16_lab.log); more streams stride
-    unsigned g = grid_for(vec ? n / 4 + 1 : n, W <= 8 ? INA_QR_U : 2, W <= 8 ? g_ew_blocks.load() : g_stream_blocks.load());
+    unsigned g = grid_for(vec ? n / 4 + 1 : n, W <= 8 ? kQrU : 2, W <= 8 ? g_ew_blocks.load() : g_stream_blocks.load());
     hipStream_t s = hs(stream);
     switch (W) {
         case 2: hipLaunchKernelGGL(k_quant_reduce_i32<2>, dim3(g), dim3(kBlock), 0, s, pk, W, out, n, sc, vec); break;
@@ -2410,7 +2282,7 @@ int ina_ps_combine_f32(const float* local, const float* const* paras, int W, dou
     if (int rc = fill_pack(pk, paras, W, al)) return rc;
     if (!local || !out) return set_error(INA_EINVAL, "null pointer%s", "");
     int vec = al && aligned16(local) && aligned16(out);
-    unsigned g = grid_for(vec ? n / 4 + 1 : n, W <= 4 ? INA_COMB_U : 2, g_combine_blocks);
+    unsigned g = grid_for(vec ? n / 4 + 1 : n, W <= 4 ? kCombU : 2, g_combine_blocks);
     hipStream_t s = hs(stream);
     float ws = (float)weight_step;
     switch (W) {
@@ -2442,7 +2314,7 @@ int ina_ps_combine_ina_f32(const float* local, const float* const* paras, int W,
     if (int rc = fill_pack(pk, paras, W, al)) return rc;
     if (!local || !out) return set_error(INA_EINVAL, "null pointer%s", "");
     int vec = al && aligned16(local) && aligned16(out);
-    unsigned g = grid_for(vec ? n / 4 + 1 : n, W <= 4 ? INA_COMBI_U : 2, g_combine_ina_blocks);
+    unsigned g = grid_for(vec ? n / 4 + 1 : n, W <= 4 ? kCombiU : 2, g_combine_ina_blocks);
     hipStream_t s = hs(stream);
     float sc = ldexpf(1.0f, k), inv = ldexpf(1.0f, -k), ws = (float)weight_step;
     switch (W) {
@@ -2556,8 +2428,8 @@ int ina_quantize_pack_nga_multi(const float* const* x, int W, const float* base,
             const dim3 blk(kBlock);
             const float* bp = base ? base + v0 : nullptr;
             const size_t nn = n - v0;
-            if (INA_QPM_PPW && V == 256 && C <= 65 + 64) {          // a wave per packet
-                const dim3 grid(grid_for(np * 64, 1, INA_QPM_PPW_BLOCKS));
+            if (kQpmPpw && V == 256 && C <= 65 + 64) {          // a wave per packet
+                const dim3 grid(grid_for(np * 64, 1, kQpmPpwBlocks));
                 with_group(G, [&](auto g) {
                     hipLaunchKernelGGL(k_qpack_nga_multi_v256<g.value>, grid, blk, 0, s, a, bp, nn, sc,
                                        prm[0].num_slots, (uint32_t)pstride, (uint32_t)np);
@@ -2691,7 +2563,7 @@ int ina_unpack_nga(const uint8_t* pkts, size_t npk, int V, size_t pstride,
             if (fo.index) fo.index += p0;
             if (fo.switch_id) fo.switch_id += p0;
             if (fo.frag_id) fo.frag_id += p0;
-            hipLaunchKernelGGL(k_unpack_nga_flat<INA_UNPACK_U>, dim3(grid_for(np * C, INA_UNPACK_U, g_stream_blocks)),
+            hipLaunchKernelGGL(k_unpack_nga_flat<kUnpackU>, dim3(grid_for(np * C, kUnpackU, g_stream_blocks)),
                                dim3(kBlock), 0, s, pkts + p0 * pstride, (uint32_t)C, (uint32_t)(V / 4),
                                (uint32_t)(np * C), fo, fields ? 1 : 0, vals + p0 * (size_t)V,
                                (uint32_t)V);
@@ -2853,7 +2725,7 @@ int ina_absmax_f32(const float* x, const float* base, size_t n, float* out_dev, 
     // blocks end together), so the grid stays small: 256 workgroups 38 us, 2048 47 us, 8192
     // 86 us (ResNet-50 delta); 8 or 16 chunks in flight per lane instead of 4 were slower
     // (profiles/r02/lab/absmax_geometry_lab.log)
-    hipLaunchKernelGGL(k_absmax_f32, dim3(grid_for(vec ? n / 4 + 1 : n, INA_ABSMAX_U, INA_ABSMAX_BLOCKS)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_absmax_f32, dim3(grid_for(vec ? n / 4 + 1 : n, kAbsmaxU, kAbsmaxBlocks)), dim3(kBlock), 0,
                        s, x, base, n, vec, reinterpret_cast<uint32_t*>(out_dev));
     return check_launch("absmax_f32");
 }
@@ -2869,7 +2741,7 @@ int ina_absmax_multi_f32(const float* const* xs, int W, const float* base, size_
         return set_error(INA_EHIP, "memset absmax%s", "");
     if (n == 0) return INA_OK;
     const int vec = al && (!base || aligned16(base));
-    hipLaunchKernelGGL(k_absmax_multi_f32, dim3(grid_for(vec ? n / 4 + 1 : n, 1, INA_ABSMAX_MULTI_BLOCKS)),
+    hipLaunchKernelGGL(k_absmax_multi_f32, dim3(grid_for(vec ? n / 4 + 1 : n, 1, kAbsmaxMultiBlocks)),
                        dim3(kBlock), 0, s, pk, W, base, n, vec, reinterpret_cast<uint32_t*>(out_dev));
     return check_launch("absmax_multi_f32");
 }

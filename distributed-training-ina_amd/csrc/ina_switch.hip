@@ -73,35 +73,17 @@ __device__ __forceinline__ uint32_t rd_be32(const uint8_t* p) {
 // ~130 us at 819,200 pairs: 10 dependent merge passes, or onesweep + lookback resets.)
 constexpr int kRsMaxBits = 9;
 constexpr int kRsBins = 1 << kRsMaxBits;     // 512
-#ifndef INA_RS_WAVES
-#define INA_RS_WAVES 4
-#endif
-#ifndef INA_RS_ROUNDS
-#define INA_RS_ROUNDS 16
-#endif
-constexpr int kRsRounds = INA_RS_ROUNDS;
-#ifndef INA_RS_ROUNDS_SMALL
-#define INA_RS_ROUNDS_SMALL 4
-#endif
-#ifndef INA_RS_SMALL_ITEMS
-#define INA_RS_SMALL_ITEMS 262144
-#endif
-#ifndef INA_RS_ROUNDS_MID
-#define INA_RS_ROUNDS_MID 8
-#endif
-#ifndef INA_RS_MID_ITEMS
-#define INA_RS_MID_ITEMS 524288
-#endif
+constexpr int kRsWaves = 4;
+constexpr int kRsRounds = 16;
+constexpr int kRsRoundsSmall = 4;
+constexpr int kRsSmallItems = 262144;
+constexpr int kRsRoundsMid = 8;
+constexpr int kRsMidItems = 524288;
 // chunk + bucket sort of more than 2 Mi packets: 8,192-packet chunks (32 rounds), so a
 // bucket's run in each chunk is twice as long and B gathers half as many of them
-#ifndef INA_RS_ROUNDS_BIG
-#define INA_RS_ROUNDS_BIG 32
-#endif
-#ifndef INA_RS_BIG_ITEMS
-#define INA_RS_BIG_ITEMS 2097152
-#endif
-constexpr int kRsBlock = 64 * INA_RS_WAVES;
-constexpr int kRsWaves = kRsBlock / 64;
+constexpr int kRsRoundsBig = 32;
+constexpr int kRsBigItems = 2097152;
+constexpr int kRsBlock = 64 * kRsWaves;
 static_assert(kRsBins % kRsBlock == 0, "digits split evenly over the block's threads");
 
 __device__ __forceinline__ unsigned long long lanes_with_digit(uint32_t d, int bits, bool valid) {
@@ -215,21 +197,12 @@ constexpr uint32_t kPlainBit = 0x40000000u;
 // or of a dense run stores none: 26 MB of stores left the pass in front of every NGA-32 C3 call)
 // and tags the wave's entry of `flags` with the call's epoch; a reader takes the array where the
 // tag matches and the descriptor elsewhere (the in-order run: always the descriptor).
-#ifndef INA_SWITCH_PLAIN
-#define INA_SWITCH_PLAIN 1
-#endif
-#ifndef INA_KEYS_FROM_DESC
-#define INA_KEYS_FROM_DESC 1
-#endif
 constexpr uint32_t kKeysSpanMax = 65535;      // slots a storing detection wave may span
 // ... and must span more than this: a wave of small local disorder leaves its keys to the
 // descriptors, which the lists then read instead.  NGA-32 C3 split (profiles/r06/lab/
 // keys_span_min_ab_v32.log): jitter 64 289-290 -> 285 us, jitter 512 296 -> 292, jitter 4096
 // unchanged at 128 (its waves span 193-256 slots; a minimum of 256 lost it 13 us)
-#ifndef INA_KEYS_SPAN_MIN
-#define INA_KEYS_SPAN_MIN 128
-#endif
-constexpr uint32_t kKeysSpanMin = INA_KEYS_SPAN_MIN;
+constexpr uint32_t kKeysSpanMin = 128;
 struct KeySrc {
     const uint32_t* keys;
     const uint2* desc;
@@ -329,21 +302,13 @@ __global__ __launch_bounds__(NW * 64) void k_switch_keys(const uint8_t* __restri
 //     gives the stable slot order with no rank bookkeeping; then the run kernel: two
 //     launches instead of seven.
 constexpr int kSmallBatch = 4096;                 // LDS capacity of the one-workgroup sort
-#ifndef INA_SWITCH_SMALL_MAX
-#define INA_SWITCH_SMALL_MAX 2048
-#endif
-static_assert(INA_SWITCH_SMALL_MAX <= kSmallBatch, "small path limited by its LDS");
+constexpr int kSmallMax = 2048;
+static_assert(kSmallMax <= kSmallBatch, "small path limited by its LDS");
 constexpr int kSmallBlock = 1024;
 // the largest batch the one-workgroup sort takes by default (ina_set_tuning key 9, g_switch_keys)
-#ifndef INA_SWITCH_SMALL_DEFAULT
-#define INA_SWITCH_SMALL_DEFAULT 768
-#endif
-#ifndef INA_SWITCH_TINY_MAX
-#define INA_SWITCH_TINY_MAX 128                // one-launch path (k_switch_tiny) up to this many packets (tiny_lab: break-even ~150)
-#endif
-#ifndef INA_SWITCH_PRE_ALL
-#define INA_SWITCH_PRE_ALL 1                   // ina_set_tuning key 19's default (g_switch_keys)
-#endif
+constexpr int kSmallDefault = 768;
+constexpr int kTinyMax = 128;                  // one-launch path (k_switch_tiny) up to this many packets (tiny_lab: break-even ~150)
+constexpr int kPreAll = 1;                     // ina_set_tuning key 19's default (g_switch_keys)
 static std::atomic<uint32_t> g_sort_epoch{0};   // per-call tag of the chunk sort's "unsorted" flag
 
 // T = uint32_t packs (slot << 12 | id) when num_slots + 1 <= 2^20, else uint64_t (slot << 32
@@ -550,10 +515,7 @@ __global__ __launch_bounds__(NW * 64) void k_rs_scatter(const uint32_t* __restri
 // pool that is a multiple of 2^lb slots) is not gathered: B stores its size and the
 // register-resident run kernel stops before it.  Keys of one digit (pools < 512 slots) are
 // the same with lb = 0: B only gathers.
-#ifndef INA_BK_WAVES
-#define INA_BK_WAVES 16
-#endif
-constexpr int kBkWaves = INA_BK_WAVES;
+constexpr int kBkWaves = 16;
 constexpr int kBkThr = kBkWaves * 64;
 constexpr int kBkMaxChunks = 2048;                  // B's LDS rows: up to 2048 x CH packets
 // B's tile: 16 waves x 64 x R items.  R = 4 (4,096) by default; 8,192 (R = 8) takes the
@@ -591,12 +553,12 @@ struct SwitchKey {
 };
 static SwitchKey g_switch_keys[] = {
     // key 9: the largest batch the one-workgroup sort takes (0: never; 1: the
-    // default, INA_SWITCH_SMALL_DEFAULT; 2..INA_SWITCH_SMALL_MAX: that many packets).  Above
+    // default, kSmallDefault; 2..kSmallMax: that many packets).  Above
     // ~700 packets the bucket sort is faster (tiny_lab: 1,024 packets 26.6 vs 25.2 us, 2,048
     // 37.5 vs 25.3; 512: 23.1 vs 24.0 -- profiles/r02/lab/tiny_lab.log)
     {9, &SwitchTuning::small_sort,
-     [](int v) { return v == 1 ? INA_SWITCH_SMALL_DEFAULT : key_range<0, INA_SWITCH_SMALL_MAX>(v); },
-     INA_SWITCH_SMALL_DEFAULT},
+     [](int v) { return v == 1 ? kSmallDefault : key_range<0, kSmallMax>(v); },
+     kSmallDefault},
     // key 10 (lab builds only, gated in ina_set_tuning): run-kernel window (0: auto)
     {10, &SwitchTuning::win, key_range<0, 64>, 0},
     // key 11: lone-ack lane path (0: off)
@@ -609,7 +571,7 @@ static SwitchKey g_switch_keys[] = {
     // key 13: sort chunk rounds (0 auto, 4/8/16)
     {13, &SwitchTuning::os_rounds, key_one_of<0, 4, 8, 16>, 0},
     // key 15: the one-launch path (k_switch_tiny) up to this many packets (0: off)
-    {15, &SwitchTuning::tiny_max, key_range<0, INA_SWITCH_SMALL_MAX>, INA_SWITCH_TINY_MAX},
+    {15, &SwitchTuning::tiny_max, key_range<0, kSmallMax>, kTinyMax},
     // key 17: the bucket pass's tile, 0 auto, 4 or 8 rounds
     {17, &SwitchTuning::bucket_tile, key_one_of<0, kLcRounds, kLcRoundsBig>, 0},
     // key 18: dense-run batches skip the sort (0: off)
@@ -619,7 +581,7 @@ static SwitchKey g_switch_keys[] = {
     // rows at 819,200 NGA-256 packets (tools/lab/switch_pre_lab.py, profiles/r04/lab): worker-
     // major -3.8 / -3.2 us, round-robin -6.1 / -5.4 us, a shuffled batch +5.6 / +4.9 us (it pays
     // the detection pass and one launch more); NIC arrival is structured, so split by default
-    {19, &SwitchTuning::pre_all, key_flag, INA_SWITCH_PRE_ALL},
+    {19, &SwitchTuning::pre_all, key_flag, kPreAll},
     // key 20: near-sorted batches skip the sort (0: off)
     {20, &SwitchTuning::local, key_flag, 1},
     // key 21 (tests): block 0 of the decision pass waits this many microseconds
@@ -840,20 +802,12 @@ constexpr uint32_t kLocMaxWindow = 65535;                     // 16-bit cursors
 // how long a digit-pass block waits for block 0's near-sorted verdict before it sorts its chunk
 // anyway (constant 100 MHz clock: 50 us; block 0's decision takes ~8 us, r05)
 constexpr unsigned long long kLocPollTicks = 5000;
-#ifndef INA_LOC_U
-#define INA_LOC_U 4                                           // granules per unit (a half chunk)
-#endif
-constexpr uint32_t kLocU = INA_LOC_U;
-#ifndef INA_LL_WAVES
-#define INA_LL_WAVES 4
-#endif
-constexpr int kLlWaves = INA_LL_WAVES;                        // waves per unit in the list build
+constexpr uint32_t kLocU = 4;                                 // granules per unit (a half chunk)
+constexpr int kLlWaves = 4;                                   // waves per unit in the list build
 constexpr int kLlBins = 1024;                                 // slots one LDS pass counts
 constexpr int kLlBits = 10;
-#ifndef INA_LL_ROUNDS
-#define INA_LL_ROUNDS 20      // a J = 64 unit window (5 granules) held: 310.1 -> 304.3 us (r05v)
-#endif
-constexpr int kLlRounds = INA_LL_ROUNDS;                      // key rounds a lane holds
+// key rounds a lane holds; 20, a J = 64 unit window (5 granules) held: 310.1 -> 304.3 us (r05v)
+constexpr int kLlRounds = 20;
 
 // wave-wide inclusive max (lane i: max over lanes <= i) and suffix min (lane i: min over lanes >= i)
 __device__ __forceinline__ uint32_t wave_incl_max(uint32_t x) {
@@ -874,21 +828,6 @@ __device__ __forceinline__ uint32_t wave_suffix_min(uint32_t x) {
     }
     return x;
 }
-
-#ifndef INA_LOC_TIMING
-#define INA_LOC_TIMING 0
-#endif
-#if INA_LOC_TIMING
-// lab builds only: per-unit wall-clock stamps of k_local_lists' phases (tools/lab)
-__device__ unsigned long long g_loc_t[8192][4];
-#define LOC_STAMP(q) do { if (threadIdx.x == 0 && u < 8192) g_loc_t[u][q] = wall_clock64(); } while (0)
-// the decision pass: rows 8191 (block 0: entry, breaks summed, decided) and 8190 (the last
-// block: entry, verdict seen)
-#define DEC_STAMP(row, q) do { if (threadIdx.x == 0) g_loc_t[row][q] = wall_clock64(); } while (0)
-#else
-#define LOC_STAMP(q) do { } while (0)
-#define DEC_STAMP(row, q) do { } while (0)
-#endif
 
 // unit u: slots [lo, hi), window from granule g_lo to the unit's last granule
 struct LocUnit {
@@ -952,7 +891,6 @@ __device__ __forceinline__ bool local_decide(const uint32_t* __restrict__ gmin, 
     }
     __syncthreads();                                          // PM / SM final; s_a is reused
     if (kmin > kmax) return false;                            // no packet of this switch
-    DEC_STAMP(8189, 0);
     // the units: slot range, window, scan cost (window x LDS passes).  Thread t takes units
     // [t upt, (t+1) upt) and keeps them in registers: one binary search for g_lo of its first
     // unit (PM is non-decreasing), then a short forward walk for the next (g_lo grows with u)
@@ -985,7 +923,6 @@ __device__ __forceinline__ bool local_decide(const uint32_t* __restrict__ gmin, 
         cost += (unsigned long long)((hi - lo + kLlBins - 1) / kLlBins) * win;
         maxwin = max(maxwin, win);
     }
-    DEC_STAMP(8189, 1);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         cost += (unsigned long long)__shfl_xor((long long)cost, o);
@@ -1003,7 +940,6 @@ __device__ __forceinline__ bool local_decide(const uint32_t* __restrict__ gmin, 
         total += s_cost[w];
         mw = max(mw, s_a[w]);
     }
-    DEC_STAMP(8189, 2);
     if (mw > kLocMaxWindow || total > (unsigned long long)kLocBeta * npk) return false;   // the sort
     if (writer) {
 #pragma unroll
@@ -1033,10 +969,8 @@ __device__ __forceinline__ bool local_decide(const uint32_t* __restrict__ gmin, 
 // key).
 __device__ __forceinline__ size_t switch_block_index();
 __device__ __forceinline__ size_t xcd_block_index();
-#ifndef INA_LL_WAVES_PER_EU
-#define INA_LL_WAVES_PER_EU 8
-#endif
-__global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(INA_LL_WAVES_PER_EU, 8))) void k_local_lists(const KeySrc keys_in, size_t npk,
+constexpr int kLlWavesPerEu = 8;
+__global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(kLlWavesPerEu, 8))) void k_local_lists(const KeySrc keys_in, size_t npk,
                                                                uint32_t num_slots, uint32_t kmask,
                                                                const uint32_t* __restrict__ unsorted,
                                                                const LocUnit* __restrict__ units, uint32_t gsize,
@@ -1057,7 +991,6 @@ __global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(I
     for (uint32_t u = (uint32_t)xcd_block_index(); u < nunits; u += gridDim.x) {
         const LocUnit w = units[u];
         if (w.hi <= w.lo) continue;                               // no slot (block-uniform)
-        LOC_STAMP(0);
         // positions fit 32 bits (npk <= 2^31 - 1)
         const uint32_t P0 = w.g_lo * gsize, Pu = u * kLocU * gsize;
         const uint32_t P1 = (uint32_t)min((size_t)Pu + (size_t)kLocU * gsize, npk);
@@ -1116,7 +1049,6 @@ __global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(I
 #pragma unroll
                 for (int v = 0; v < kLlWaves; ++v) area += s_ws[v];
             }
-            LOC_STAMP(1);
             // thread t: slots d = t*DPT + j -- totals, the block scan, then the per-wave cursors
             uint32_t tc[DPT], tt = 0;
 #pragma unroll
@@ -1157,7 +1089,6 @@ __global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(I
                 e += tc[j];
             }
             __syncthreads();
-            LOC_STAMP(2);
             for (uint32_t r0 = b0; r0 < b1; r0 += 64 * kLlRounds) { // the lists, in arrival order
                 if (!held) {
 #pragma unroll
@@ -1184,7 +1115,6 @@ __global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(I
             area += passn;
             __syncthreads();                                      // cw of the next pass or unit
         }
-        LOC_STAMP(3);
     }
 }
 
@@ -1192,19 +1122,11 @@ __global__ __launch_bounds__(kLlWaves * 64) __attribute__((amdgpu_waves_per_eu(I
 // (interleaved A/B at NGA-32 C3 size, shuffled: 732.8 -> 709.2 us packed, 639.7 -> 615.9 us
 // split, bytes equal; profiles/r04/lab/sort_stage_ab_v32.log).  The LDS (104 KiB) costs
 // the second block per CU the packed counts bought; the contiguous stores win.
-// (lab) the largest chunk rounds the staging takes: at 8,192-packet chunks it costs one block
-// per CU (139 KiB) and still wins, NGA-32 shuffled 654 vs 691 us unstaged at two blocks per
+// The staging reuses the digit-count LDS once the offsets are read.
+// kSortStageMaxR: the largest chunk rounds the staging takes: at 8,192-packet chunks it costs one
+// block per CU (139 KiB) and still wins, NGA-32 shuffled 654 vs 691 us unstaged at two blocks per
 // CU (profiles/r04/lab/stage_big_chunk_ab_v32.log)
-// the staging reuses the digit-count LDS once the offsets are read (0: its own arrays)
-#ifndef INA_SORT_STAGE_ALIAS
-#define INA_SORT_STAGE_ALIAS 1
-#endif
-#ifndef INA_SORT_STAGE_MAX_R
-#define INA_SORT_STAGE_MAX_R 8
-#endif
-#ifndef INA_SORT_STAGE
-#define INA_SORT_STAGE 1
-#endif
+constexpr int kSortStageMaxR = 8;
 // The 2,048-bin chunk pass and the 1,024- / 2,048-bin bucket pass keep two waves' per-digit
 // counts in one LDS word (16 bits each: a wave counts at most 64 x 8 items of a digit, and
 // the offsets below stay inside one chunk or tile, <= 8,192): half the count array, so two
@@ -1257,12 +1179,7 @@ __device__ __forceinline__ void rs_tile_scatter_half(const uint32_t (&k)[R], con
             if constexpr (kPosOnly) {
                 spos[r] = pos - sbase;
             } else if constexpr (kStage) {            // the chunk's output staged in LDS
-#if INA_SORT_STAGE_ALIAS
                 spos[r] = pos - sbase;
-#else
-                sk[pos - sbase] = k[r];
-                sv[pos - sbase] = v[r];
-#endif
             } else {
                 kout[pos] = k[r];
                 vout[pos] = v[r];
@@ -1275,7 +1192,6 @@ __device__ __forceinline__ void rs_tile_scatter_half(const uint32_t (&k)[R], con
         for (int r = 0; r < R; ++r) spos_out[r] = spos[r];
         return;
     }
-#if INA_SORT_STAGE_ALIAS
     if constexpr (kStage) {
         // the staging area is the count array itself (sk, sv alias base): every wave's
         // offsets are read before any item lands there
@@ -1287,7 +1203,6 @@ __device__ __forceinline__ void rs_tile_scatter_half(const uint32_t (&k)[R], con
                 sv[spos[r]] = v[r];
             }
     }
-#endif
 }
 
 // kMode: 0 the chunk pass (keys, detection, digits, scatter); split in two (tuning key 19, the
@@ -1296,37 +1211,22 @@ __device__ __forceinline__ void rs_tile_scatter_half(const uint32_t (&k)[R], con
 // kout, the descent flag, the breaks; no digits, a small LDS footprint), then 2 = the decision
 // (every block sums the break counts; dense runs: block 0 writes the run table) and, for a
 // batch neither in slot order nor dense runs, the digits + scatter.
-// lab builds only (timing what the detection pass's action stores cost; results then differ)
 // The digit pass writes each chunk's (digit, chunk) run lengths and starts as COLUMNS (word c of
 // row d): neighbouring chunks write neighbouring words, so a line of them is written by 32 chunk
 // blocks.  Dispatched round-robin over the XCDs, those blocks sat on 8 L2s and each wrote the line
 // back partly: 182 MB written against 59 MB of data at NGA-32 C3 size.  With neighbouring chunks
-// on one XCD (switch_block_index) the line fills in one L2: 69 MB, shuffled split 436 -> 426 us
+// on one XCD (xcd_block_index) the line fills in one L2: 69 MB, shuffled split 436 -> 426 us
 // (profiles/r06/lab/sort_stage_xcd_ab_v32.log)
-#ifndef INA_CHUNK_XCD
-#define INA_CHUNK_XCD 1
-#endif
 // A one-tile bucket's sorted keys and values leave through LDS as two contiguous runs instead of
 // scattered 4-byte stores: the bucket pass wrote 214 MB for 52 MB of keys and values, now 52 MB;
 // shuffled split 436 -> 404 us, with the chunk mapping 393 us (same log; NGA-256 neutral)
-#ifndef INA_BUCKET_STAGE
-#define INA_BUCKET_STAGE 1
-#endif
-#ifndef INA_BUCKET_XCD
-#define INA_BUCKET_XCD 0
-#endif
 // Groups of 8 neighbouring buckets on one XCD: a bucket's run in a digit-pass chunk is ~6 items,
 // so the runs of neighbouring buckets share lines, and round-robin dispatch read each line into
 // up to eight L2s (218 MB read for ~60 MB at NGA-32 C3 size, shuffled).  Groups of 8: 79 MB, the
 // shuffled split call 386 -> 378 us, packed 554 / 515 -> 538 / 506 us, NGA-256 -2 us.  All 128 of
-// an XCD's buckets in one run (INA_BUCKET_XCD) reads 62 MB but costs 7 us: its in-flight blocks
+// an XCD's buckets in one run was measured too: it reads 62 MB but lost by 7 us, its in-flight blocks
 // then share too few lines (profiles/r06/lab/bucket_group_ab_v32.log, bucket_xcd_ab_v32.log)
-#ifndef INA_BUCKET_GROUP
-#define INA_BUCKET_GROUP 8
-#endif
-#ifndef INA_LAB_DETECT_NOACT
-#define INA_LAB_DETECT_NOACT 0
-#endif
+constexpr uint32_t kBucketGroup = 8;
 template <int R, bool kDesc, int BINS, int kMode = 0>
 __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sort_chunks(const uint8_t* __restrict__ pkts,
                                                         const uint2* __restrict__ desc, size_t npk,
@@ -1350,14 +1250,12 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     __shared__ uint32_t wbrk[kBkWaves];               // per-wave break counts
     __shared__ uint32_t wgmn[kBkWaves], wgmx[kBkWaves];   // per-wave slot-key bounds (near-sorted path)
     const int lane = threadIdx.x & 63, wv = wave_in_block();
-    // (INA_CHUNK_XCD: neighbouring chunks on one XCD, so the (digit, chunk) columns they write share its L2)
-    const size_t c = INA_CHUNK_XCD && kMode == 2 ? xcd_block_index() : blockIdx.x;
+    // (neighbouring chunks on one XCD, so the (digit, chunk) columns they write share its L2)
+    const size_t c = kMode == 2 ? xcd_block_index() : blockIdx.x;
     // gstat (near-sorted path on): granule bounds, gmin[G] then gmax[G], G = 8 granules a chunk
     const uint32_t G = (uint32_t)nch * (uint32_t)kGranPerChunk;
     if constexpr (kMode == 2) {
         if (unsorted[0] != epoch) return;             // in slot order: no sort
-        if (c == 0) DEC_STAMP(8191, 0);
-        if (c == nch - 1) DEC_STAMP(8190, 0);
         if (brk_cnt) {
             // the decision after the detection pass: every block sums the chunks' break counts
             // (the same answer everywhere); a batch of at most kRunsMax dense runs gets its run
@@ -1394,7 +1292,6 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             __shared__ uint32_t s_loc;
             unsigned long long* verdict = reinterpret_cast<unsigned long long*>(unsorted + kLocVerdict);
             if (c == 0) {
-                DEC_STAMP(8191, 1);
                 if (decide_delay_ticks) {                 // (tests: key 21) a late block 0
                     const unsigned long long t0 = wall_clock64();
                     while (wall_clock64() - t0 < decide_delay_ticks) __builtin_amdgcn_s_sleep(64);
@@ -1407,7 +1304,6 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     s_loc = loc ? 1u : 0u;
                 }
-                DEC_STAMP(8191, 2);
             } else if (threadIdx.x == 0) {
                 unsigned long long v;
                 uint32_t loc = 0u;
@@ -1422,7 +1318,6 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                     __builtin_amdgcn_s_sleep(8);
                 }
                 s_loc = loc;
-                if (c == nch - 1) DEC_STAMP(8190, 1);
             }
             __syncthreads();
             if (s_loc) return;
@@ -1493,7 +1388,7 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         // the other actions (1 in W): scattered byte stores in slot / list order wrote back a line
         // each (shuffled NGA-32 run kernel: 440 MB written, r05e); the in-order and run-table
         // paths store every action anyway
-        if (kMode == 1 && p < npk && !INA_LAB_DETECT_NOACT) actions[p] = mine ? INA_ACT_DROP : INA_ACT_FWD_OTHER;
+        if (kMode == 1 && p < npk) actions[p] = mine ? INA_ACT_DROP : INA_ACT_FWD_OTHER;
         if constexpr (kMode != 1) {
             if constexpr (kHalf) lds_count_half(base[wv >> 1], (key >> lb) & (nb - 1), p < npk, (wv & 1) * 16);
             else lds_count(base[wv], (key >> lb) & (nb - 1), p < npk);
@@ -1618,19 +1513,14 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         }
     }
     __syncthreads();
-#if INA_SORT_STAGE
-    if constexpr (kHalf && R <= INA_SORT_STAGE_MAX_R) {
+    if constexpr (kHalf && R <= kSortStageMaxR) {
         // the chunk's sorted output lands in LDS, then leaves as one contiguous stretch (the
         // 2,048-bin scatter writes runs of ~2 items: scattered 4-byte stores)
-#if INA_SORT_STAGE_ALIAS
         // the chunk's 2 x 4 x kBkThr x R bytes fit the packed count array (8 x 2,048 words
         // at R = 8): 139 -> 74 KiB at 8,192-packet chunks, two blocks per CU
         static_assert(2 * kBkThr * R <= (kBkWaves / 2) * BINS, "staging fits the count array");
         uint32_t* s_k = &base[0][0];
         uint32_t* s_v = s_k + kBkThr * R;
-#else
-        __shared__ uint32_t s_k[kBkThr * R], s_v[kBkThr * R];
-#endif
         const uint32_t cb = (uint32_t)(c * (size_t)(kBkThr * R));
         rs_tile_scatter_half<R, BINS, true>(k, v, i0, npk, lb, hbits, base, gst, kout, vout, R, s_k, s_v, cb);
         __syncthreads();
@@ -1641,21 +1531,9 @@ __global__ __launch_bounds__(kBkThr) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         }
         return;
     }
-#endif
     if constexpr (kHalf) rs_tile_scatter_half<R, BINS>(k, v, i0, npk, lb, hbits, base, gst, kout, vout);
     else rs_tile_scatter<R, kBkWaves, BINS>(k, v, i0, npk, lb, hbits, base, gst, kout, vout);
 }
-
-#ifndef INA_BK_TIMING
-#define INA_BK_TIMING 0
-#endif
-#if INA_BK_TIMING
-// lab builds only: per-block wall-clock stamps of k_sort_buckets' phases (tools/lab)
-__device__ unsigned long long g_bk_t[kBkMaxChunks][6];   // one row per bucket (<= 2,048)
-#define BK_STAMP(q) do { if (threadIdx.x == 0) g_bk_t[blockIdx.x][q] = wall_clock64(); } while (0)
-#else
-#define BK_STAMP(q) do { } while (0)
-#endif
 
 // positions of bucket items i[r] (0 <= i < the bucket's size) in A's output: the run of the
 // last chunk whose bucket offset is <= i (s_dst: exclusive prefix of the run lengths over the
@@ -1681,7 +1559,7 @@ __device__ __forceinline__ void bucket_src(const uint32_t* s_dst, const uint32_t
 
 // two blocks per CU (8 waves per SIMD) where the LDS allows it (<= 1,024 bins, 53 KiB): the
 // bound caps the scalar registers too -- at 106 SGPRs (R = 8) a SIMD held 7 waves, so one
-// 16-wave block per CU ran (most blocks in flight at once: 256, tools/lab/bucket_phase_lab.py)
+// 16-wave block per CU ran (most blocks in flight at once: 256, profiles/r03/lab/bucket_phase_lab.log)
 template <int R, int BINS>
 __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 256) void k_sort_buckets(const uint32_t* __restrict__ kin,
                                                          const uint32_t* __restrict__ vin,
@@ -1701,19 +1579,17 @@ __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 
     __shared__ uint32_t gst[BINS];                    // bucket digit counts, then output positions
     __shared__ uint32_t red[kBkWaves], red2[kBkWaves];
     const int lane = threadIdx.x & 63, wv = wave_in_block();
-    // (INA_BUCKET_XCD: neighbouring buckets on one XCD: their runs in a chunk share lines, read through one L2)
-    uint32_t b = INA_BUCKET_XCD ? (uint32_t)xcd_block_index() : blockIdx.x;
-#if INA_BUCKET_GROUP > 1
-    {   // groups of INA_BUCKET_GROUP neighbouring buckets on one XCD (blocks go to the XCDs
-        // round-robin); the grid's tail past whole groups of 8 x G keeps its own index
-        constexpr uint32_t G = INA_BUCKET_GROUP;
+    uint32_t b = blockIdx.x;
+    {   // groups of kBucketGroup neighbouring buckets on one XCD (blocks go to the XCDs
+        // round-robin): their runs in a chunk share lines, read through one L2; the grid's tail
+        // past whole groups of 8 x G keeps its own index
+        constexpr uint32_t G = kBucketGroup;
         const uint32_t p = blockIdx.x, full = (gridDim.x / (8u * G)) * (8u * G);
         if (p < full) {
             const uint32_t x = p & 7u, i = p >> 3;
             b = (i / G) * (8u * G) + x * G + (i % G);
         }
     }
-#endif
     // keys already in slot order: A's output is the sorted order and the register-resident
     // run kernel reads it there (sorted_copy = 0), so only the foreign bucket's size is needed
     const bool in_order = unsorted[0] != epoch;
@@ -1738,7 +1614,6 @@ __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 
         }
         __syncthreads();                              // red[] is reused below
     }
-    BK_STAMP(0);
     // this bucket's run in every chunk: thread t owns chunks [t*per, t*per + per).  A chunk's
     // run start rst[b][c] is the number of its packets in lower buckets, so the rst row also
     // sums to the bucket's place in the output: no look-back over the other buckets
@@ -1782,7 +1657,6 @@ __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 
     }
     if (threadIdx.x == 0) s_dst[nch] = total;
     __syncthreads();
-    BK_STAMP(1);
     const uint32_t cnt = total;
     if (b == skip) {                                  // foreign packets only: left out, counted
         if (threadIdx.x == 0) *nforeign = cnt;
@@ -1869,7 +1743,6 @@ __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 
                     lds_count(base[wv], k[r] & (nb - 1), i0 + (uint32_t)r * 64u < t_end);
             }
         __syncthreads();
-        BK_STAMP(2);
         uint32_t tc[DPT];                             // this tile's counts of the thread's digits
 #pragma unroll
         for (int j = 0; j < DPT; ++j) {
@@ -1898,11 +1771,9 @@ __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 
             }
         }
         __syncthreads();
-        BK_STAMP(3);
         // (staging a one-tile bucket's output in LDS: round 3 measured it neutral at NGA-256,
         // profiles/r03/lab/bucket_stage_lab.log; at NGA-32 it cuts the pass's writes 4x, see
-        // INA_BUCKET_STAGE)
-#if INA_BUCKET_STAGE
+        // the note above k_sort_chunks)
         if constexpr (kHalf) {
             if (ntile == 1) {
                 // a one-tile bucket leaves as two contiguous runs: keys, then values, each staged in
@@ -1927,11 +1798,9 @@ __global__ __launch_bounds__(kBkThr, BINS <= 1024 ? 2 * kBkThr / 256 : kBkThr / 
                 return;
             }
         }
-#endif
         if constexpr (kHalf) rs_tile_scatter_half<R, BINS>(k, v, i0, t_end, 0, lbits, base, gst, kout, vout, rw);
         else rs_tile_scatter<R, kBkWaves, BINS>(k, v, i0, t_end, 0, lbits, base, gst, kout, vout, rw);
         __syncthreads();
-        BK_STAMP(4);
 #pragma unroll
         for (int j = 0; j < DPT; ++j) {
             const uint32_t d = threadIdx.x * DPT + (uint32_t)j;
@@ -2062,35 +1931,20 @@ __global__ __launch_bounds__(kSwBlock) void k_switch_run(ina_switch_state_t st,
 // once, runs the P4 state machine over them in arrival order with the slot's
 // registers in VGPRs, re-encodes and stores each packet.  Each wave owns windows of
 // 64 sorted positions and runs the segments that start in them.
-#ifndef INA_SWITCH_BATCH
-#define INA_SWITCH_BATCH 8
-#endif
-constexpr int kB = INA_SWITCH_BATCH;         // packets of a segment loaded at once
-#ifndef INA_SWITCH_WIN_SMALL
-#define INA_SWITCH_WIN_SMALL 8
-#endif
-#ifndef INA_SWITCH_WIN_NARROW
-#define INA_SWITCH_WIN_NARROW 64
-#endif
-static_assert(INA_SWITCH_WIN_NARROW >= 1 && INA_SWITCH_WIN_NARROW <= 64, "a narrow window's heads are one wave's lanes");
-#ifndef INA_SWITCH_WIN_LARGE
-#define INA_SWITCH_WIN_LARGE 16
-#endif
-#ifndef INA_SWITCH_GRID
-#define INA_SWITCH_GRID (1 << 20)
-#endif
-static_assert(INA_SWITCH_WIN_SMALL >= 1 && INA_SWITCH_WIN_SMALL <= 64 && INA_SWITCH_WIN_LARGE >= 1 &&
-              INA_SWITCH_WIN_LARGE <= 64, "a window is at most one wave of keys");
+constexpr int kB = 8;                        // packets of a segment loaded at once
+constexpr int kWinSmall = 8;
+constexpr int kWinNarrow = 64;
+static_assert(kWinNarrow >= 1 && kWinNarrow <= 64, "a narrow window's heads are one wave's lanes");
+constexpr int kWinLarge = 16;
+constexpr int kSwitchGrid = 1 << 20;
+static_assert(kWinSmall >= 1 && kWinSmall <= 64 && kWinLarge >= 1 && kWinLarge <= 64,
+              "a window is at most one wave of keys");
 // occupancy target of k_switch_run2 without the PS step (72 VGPRs -> 7 waves per SIMD)
-#ifndef INA_SWITCH_WAVES_RUN
-#define INA_SWITCH_WAVES_RUN 7
-#endif
+constexpr int kWavesRun = 7;
 // occupancy floor of k_switch_run2<true> (waves per SIMD): the compiler then takes 75 VGPRs
 // = 6 waves, no scratch; forcing 7 (72 VGPRs, 12 B/lane scratch) ran 1 % slower
 // (profiles/r02/lab/fuse_lab_waves.log)
-#ifndef INA_SWITCH_WAVES
-#define INA_SWITCH_WAVES 4
-#endif
+constexpr int kWavesPs = 4;
 
 // packet chunk loads of the run kernel carry the streaming (nt) hint: 294 -> 276 us for
 // 819,200 NGA-256 packets (tools/lab/switch_lab.py, r01 session log switch_lab_nt.log);
@@ -2390,14 +2244,8 @@ constexpr int kNarrowMaxV = 32;
 // (round 5: packed rows read as one unaligned 16-byte access per lane, no LDS exchange -- 1 in
 // flight at 8 waves per SIMD: round-robin 337.2 -> 329.5 us, jitter 64 398.4 -> 365.5 us,
 // worker-major and shuffled equal; 2 at 8 waves spills, profiles/r05/lab/packed_inflight_waves_ab_v32.log)
-#ifndef INA_SWITCH_SLOT_INFLIGHT
-#define INA_SWITCH_SLOT_INFLIGHT 1
-#endif
-#ifndef INA_SWITCH_SLOT_INFLIGHT_SPLIT
-#define INA_SWITCH_SLOT_INFLIGHT_SPLIT 1
-#endif
 template <bool kSplit>
-constexpr int kSlotInFlight = kSplit ? INA_SWITCH_SLOT_INFLIGHT_SPLIT : INA_SWITCH_SLOT_INFLIGHT;
+constexpr int kSlotInFlight = 1;
 // Packed rows (the payload at byte 15 of the row): a lane's four values are one 16-byte access at
 // byte 15 + 16 l -- an unaligned global load / store (gfx950 runs HSA code in unaligned access
 // mode; the compiler emits one dwordx4 with offset 15) instead of the aligned chunk l + 1 and the
@@ -2510,10 +2358,7 @@ __device__ __forceinline__ void group_packet(const ina_switch_state_t& st, uint8
 // other segment in the wave -> false, and the caller walks the wave's segments packet by packet
 // (the rows it reads then come from L2).  Lane l of group g: pidl = the id of packet l of group
 // g's segment, ackl its PS-ack hint (sort key bit 31); has = the group holds a segment.
-#ifndef INA_SEG8_FLIGHT
-#define INA_SEG8_FLIGHT 4
-#endif
-constexpr int kSeg8Flight = INA_SEG8_FLIGHT;
+constexpr int kSeg8Flight = 4;
 static_assert(8 % kSeg8Flight == 0, "whole rounds of payload loads");
 // kPs: the completing packet's sum goes straight into the PS update and its ack row (as
 // group_packet does).  ack_pid != ~0u (group-uniform): a PS ack leads the segment (the steady
@@ -3205,22 +3050,14 @@ __device__ __forceinline__ size_t switch_block_index() { return blockIdx.x; }
 
 // occupancy target of the narrow split-row run without the PS step: 8 waves per SIMD takes its
 // SGPRs to the 80 that admit 8 blocks per CU (8 spilled to VGPR lanes; 86 admitted 7)
-#ifndef INA_SWITCH_WAVES_RUN_NS
-#define INA_SWITCH_WAVES_RUN_NS 8     // NGA-32 C3 split: worker-major 232.2 -> 223.0, round-robin 259.2 -> 252.6 us (r05x)
-#endif
-#ifndef INA_SWITCH_WAVES_PS_NS
-#define INA_SWITCH_WAVES_PS_NS 8      // NGA-32 packet path: switch + PS 329.3 -> 297.6 us, step 636.9 -> 608.9 (r05y)
-#endif
+constexpr int kWavesRunNs = 8;     // NGA-32 C3 split: worker-major 232.2 -> 223.0, round-robin 259.2 -> 252.6 us (r05x)
+constexpr int kWavesPsNs = 8;      // NGA-32 packet path: switch + PS 329.3 -> 297.6 us, step 636.9 -> 608.9 (r05y)
 // the same with per-block scales: the scale byte's address and factor do not fit the 64 VGPRs of
 // 8 waves (48 B/lane of scratch, 15 VGPRs spilled); 7 waves (72 VGPRs) hold them
-#ifndef INA_SWITCH_WAVES_PS_NS_BLK
-#define INA_SWITCH_WAVES_PS_NS_BLK 7
-#endif
+constexpr int kWavesPsNsBlk = 7;
+constexpr int kWavesRunNp = 8;     // narrow packed rows (with 1 packet in flight, see kSlotInFlight)
 template <bool kPs, bool kBlk, bool kNarrow, bool kSplit>
-#ifndef INA_SWITCH_WAVES_RUN_NP
-#define INA_SWITCH_WAVES_RUN_NP 8     // narrow packed rows (with 1 packet in flight, see kSlotInFlight)
-#endif
-__global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? ((kNarrow && kSplit) ? (kBlk ? INA_SWITCH_WAVES_PS_NS_BLK : INA_SWITCH_WAVES_PS_NS) : INA_SWITCH_WAVES) : (kNarrow && kSplit) ? INA_SWITCH_WAVES_RUN_NS : kNarrow ? INA_SWITCH_WAVES_RUN_NP : INA_SWITCH_WAVES_RUN, 8))) void k_switch_run2(ina_switch_state_t st,
+__global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? ((kNarrow && kSplit) ? (kBlk ? kWavesPsNsBlk : kWavesPsNs) : kWavesPs) : (kNarrow && kSplit) ? kWavesRunNs : kNarrow ? kWavesRunNp : kWavesRun, 8))) void k_switch_run2(ina_switch_state_t st,
                                                           uint8_t* __restrict__ pkts,
                                                           uint8_t* __restrict__ pay, size_t npk,
                                                           size_t stride,
@@ -3291,7 +3128,7 @@ __global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kPs ? 
                                                   wave, nwaves, drop_prefill != 0, kdesc, plB, plC);
 }
 
-// batches of at most INA_SWITCH_TINY_MAX packets (latency, not bandwidth): ONE launch of
+// batches of at most kTinyMax packets (latency, not bandwidth): ONE launch of
 // one 16-wave workgroup -- the bitonic (slot, packet id) sort in LDS, then the run
 // kernel's work on the same 16 waves with the sorted arrays read from LDS.
 template <bool kPs, bool kBlk, typename T, int kIdBits, bool kSplit>
@@ -3301,7 +3138,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_switch_tiny(ina_switch_state_t 
                                                              PsFuse ps) {
     // the sorted (slot, packet id) arrays stay in LDS: the run loop's window loads are LDS
     // reads, not a memory round trip
-    __shared__ uint32_t keys_s[INA_SWITCH_SMALL_MAX], ids_s[INA_SWITCH_SMALL_MAX];
+    __shared__ uint32_t keys_s[kSmallMax], ids_s[kSmallMax];
     switch_sort_small_body<T, kIdBits>(pkts, npk, stride, st.num_slots, st.switch_id, actions, keys_s, ids_s);
     __syncthreads();
     switch_run2_body<kPs, kBlk, true, false, kSplit>(st, pkts, pay, npk, stride, keys_s, ids_s, actions, win,
@@ -3343,8 +3180,8 @@ static SortPlan sort_plan(size_t npk, uint32_t num_slots, const SwitchTuning& t)
     // 409,600 155.5 -> 146.1, 819,200 unchanged).  With the chunk + bucket sort, 819,200
     // packets: 4,096-packet chunks (200 A blocks) 234.6 us worker-major, 2,048 235.8, 1,024
     // 241.3 (profiles/r03/lab/sort_rounds_lab.log)
-    p.rounds = npk <= (size_t)INA_RS_SMALL_ITEMS ? INA_RS_ROUNDS_SMALL
-             : npk <= (size_t)INA_RS_MID_ITEMS   ? INA_RS_ROUNDS_MID
+    p.rounds = npk <= (size_t)kRsSmallItems ? kRsRoundsSmall
+             : npk <= (size_t)kRsMidItems   ? kRsRoundsMid
                                                  : kRsRounds;
     // more than 2 Mi packets through the chunk + bucket sort: 8,192-packet chunks.  NGA-32
     // at C3 size (6,553,600 packets, 2^20 slots: 1,025 buckets of 6,400, i.e. runs of 4
@@ -3352,9 +3189,9 @@ static SortPlan sort_plan(size_t npk, uint32_t num_slots, const SwitchTuning& t)
     // structured arrival unchanged; at 819,200 NGA-256 packets (100 chunks) +2 %, so not
     // there (interleaved A/B, bytes equal, profiles/r04/lab/chunk_rounds32_ab_v*.log).  The
     // digit passes keep 4,096 (they never see this tier: bucket_ok, mode 0, <= 2,048 chunks)
-    if (npk > (size_t)INA_RS_BIG_ITEMS && p.bucket_ok && t.sort_mode == 0 &&
-        npk <= (size_t)kBkMaxChunks * kRsWaves * 64 * INA_RS_ROUNDS_BIG)
-        p.rounds = INA_RS_ROUNDS_BIG;
+    if (npk > (size_t)kRsBigItems && p.bucket_ok && t.sort_mode == 0 &&
+        npk <= (size_t)kBkMaxChunks * kRsWaves * 64 * kRsRoundsBig)
+        p.rounds = kRsRoundsBig;
     if (const int r = t.os_rounds) p.rounds = r;   // ina_set_tuning key 13 (the tests' tier cover)
     const size_t chunk = (size_t)kRsWaves * 64 * (size_t)p.rounds;
     p.nch = (npk + chunk - 1) / chunk;
@@ -3388,7 +3225,7 @@ struct SwitchScratch {
 };
 
 static size_t sort_nch_cap(size_t npk) {
-    const size_t chunk = (size_t)kRsWaves * 64 * (size_t)INA_RS_ROUNDS_SMALL;
+    const size_t chunk = (size_t)kRsWaves * 64 * (size_t)kRsRoundsSmall;
     return (npk + chunk - 1) / chunk;
 }
 
@@ -3480,7 +3317,7 @@ static bool sort_record_find(const void* scratch, const SortRecord& want, Switch
 // and the driver (switch_process_impl)
 // ---------------------------------------------------------------------------
 // sort chunk geometry (sort_plan): one instantiation per rounds-per-wave choice
-constexpr int kR0 = INA_RS_ROUNDS_SMALL, kR1 = INA_RS_ROUNDS_MID, kR2 = kRsRounds, kR3 = INA_RS_ROUNDS_BIG;
+constexpr int kR0 = kRsRoundsSmall, kR1 = kRsRoundsMid, kR2 = kRsRounds, kR3 = kRsRoundsBig;
 static_assert(kR0 % 4 == 0 && kR1 % 4 == 0 && kR2 % 4 == 0 && kR3 % 4 == 0, "chunk sort: 16 waves x rounds/4");
 
 // f(integral_constant<int, rounds / 4>) for the plan's rounds tier: the chunk pass's instantiations
@@ -3566,12 +3403,12 @@ static SwitchPlan switch_plan(const ina_switch_state_t& st, size_t npk, size_t s
         // read those and make the rest from the descriptors, the in-order run makes all (KeySrc).
         // A sort queued alone still writes every key (its run may come without the descriptors).
         // (narrow + descriptors, one call: no arrival-order key array)
-        p.keys_from_desc = INA_KEYS_FROM_DESC && p.pre && desc && phase == 0 && st.V <= kNarrowMaxV;
+        p.keys_from_desc = p.pre && desc && phase == 0 && st.V <= kNarrowMaxV;
         // plain packets (kPlainBit): the digit pass of a narrow split-row batch reads its header rows
         // and marks them, so the sorted run reads no header row for them.  One call only (a sort
         // queued alone reads nothing but the descriptors), no PS step, and the ack hint on (both
         // hint bits outside the digits, masked out of the slot by the run)
-        p.plain = INA_SWITCH_PLAIN && p.pre && split && phase == 0 && !ps_on && p.ack_hint && st.V <= kNarrowMaxV &&
+        p.plain = p.pre && split && phase == 0 && !ps_on && p.ack_hint && st.V <= kNarrowMaxV &&
                   sp.passes * sp.bits <= 30 && st.num_slots < kPlainBit;
         // the bucket of foreign packets only (a pool of a multiple of 2^lb slots) is left out
         // when the register-resident run kernel takes the batch (it stops before them); the
@@ -3585,7 +3422,7 @@ static SwitchPlan switch_plan(const ina_switch_state_t& st, size_t npk, size_t s
         p.big = tile == kLcRoundsBig || (tile == 0 && npk > (size_t)p.gb * kBigTileAvg);
     }
     if (p.path == kPathTiny) {
-        p.win = (uint32_t)INA_SWITCH_WIN_SMALL;
+        p.win = (uint32_t)kWinSmall;
         if (const int wv = t.win) p.win = (uint32_t)wv;
     } else if (p.fast) {
         // a wave runs the segments that start in its window of `win` sorted positions: a
@@ -3596,13 +3433,13 @@ static SwitchPlan switch_plan(const ina_switch_state_t& st, size_t npk, size_t s
         // V <= 32 (NGA-32, the P4 program's format): 8 slots side by side per wave, one per
         // lane group (the *_slots_narrow drivers); wider packets: a packet per wave instruction
         p.narrow = st.V <= kNarrowMaxV;
-        p.win = npk <= 65536 ? (uint32_t)INA_SWITCH_WIN_SMALL : (uint32_t)INA_SWITCH_WIN_LARGE;
+        p.win = npk <= 65536 ? (uint32_t)kWinSmall : (uint32_t)kWinLarge;
         // a narrow wave's 8 lane groups take 8 segments at a time: a window of 64 sorted
         // positions (about 8 segments) keeps the grid at npk / 256 workgroups
-        if (p.narrow) p.win = INA_SWITCH_WIN_NARROW;
+        if (p.narrow) p.win = kWinNarrow;
         if (const int wv = t.win) p.win = (uint32_t)wv;
         const size_t per_block = (size_t)p.win * (kSwBlock / 64);
-        p.gr = (unsigned)std::min<size_t>((npk + per_block - 1) / per_block, INA_SWITCH_GRID);
+        p.gr = (unsigned)std::min<size_t>((npk + per_block - 1) / per_block, kSwitchGrid);
     } else {
         p.gr = (unsigned)((npk + (kSwBlock / 64) - 1) / (kSwBlock / 64));
     }
@@ -3912,17 +3749,6 @@ __global__ __launch_bounds__(256) void k_route_ipv4(const uint8_t* __restrict__ 
 using namespace ina;
 
 extern "C" {
-
-#if INA_LOC_TIMING
-int ina_lab_loc_times(unsigned long long* host_out) {  // lab builds only
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_loc_t), sizeof(g_loc_t)) == hipSuccess ? 0 : -1;
-}
-#endif
-#if INA_BK_TIMING
-int ina_lab_bk_times(unsigned long long* host_out) {   // lab builds only
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_bk_t), sizeof(g_bk_t)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 size_t ina_switch_scratch_bytes(size_t npkts, uint32_t num_slots) {
     if (npkts == 0 || npkts > 0x7FFFFFFFu || num_slots == 0) return 256;

@@ -22,7 +22,7 @@ from oracle import oracle as orc
 pytestmark = pytest.mark.gpu
 
 COMBINE_CAP, FANIN_CAP, MULTI_CAP = 256, 256, 512      # g_combine_blocks, kFaninBlocks, the absmax_multi grids
-ABSMAX_U = 4                                           # INA_ABSMAX_U
+ABSMAX_U = 4                                           # kAbsmaxU
 
 
 @pytest.fixture(scope="module", autouse=True)

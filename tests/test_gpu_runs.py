@@ -536,7 +536,7 @@ def test_nga32_config3_full_size(order):
 @pytest.mark.parametrize("order", ["shuffled", "worker_major", "round_robin"])
 def test_big_batch_chunks_vs_digit_passes(order, num_slots):
     """More than 2 Mi packets through the chunk + bucket sort take 8,192-packet chunks
-    (INA_RS_BIG_ITEMS).  Two batches of 8 x 300,000 NGA-4 packets (1 % frag-id collisions;
+    (kRsBigItems).  Two batches of 8 x 300,000 NGA-4 packets (1 % frag-id collisions;
     at 2^16 slots every worker wraps the pool four times), state carried: actions, rewritten
     rows and registers byte for byte against the same batches through the LSD digit passes
     (tuning key 12 = 3, 4,096-packet chunks), in packed and in split rows."""

@@ -42,9 +42,6 @@ for st in $STAGES; do
     ew16lab)
       timeout -k 10 300 python tools/lab/ew16_lab.py > "$OUT/ew16_lab.log" 2>&1
       rc=$?; cat "$OUT/ew16_lab.log"; [ $rc -ne 0 ] && fatal ew16lab $rc ;;
-    bkphase)
-      timeout -k 10 200 python tools/lab/bucket_phase_lab.py > "$OUT/bucket_phase_lab.log" 2>&1
-      rc=$?; cat "$OUT/bucket_phase_lab.log"; [ $rc -ne 0 ] && fatal bkphase $rc ;;
     zerocopy)
       timeout -k 10 200 python tools/lab/zerocopy_lab.py > "$OUT/zerocopy_lab.log" 2>&1
       rc=$?; cat "$OUT/zerocopy_lab.log"; [ $rc -ne 0 ] && fatal zerocopy $rc ;;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Switch A/B/... lab (experiment only): the in-tree libina.so ("A") against other builds of it
-(env LIBS=name:path,name:path; e.g. make -C distributed-training-ina_amd/csrc
-OUT=../../tools/lab/libina_x.so BUILD=build_x EXTRA=-D...) on config 3 as NGA-V packets (V env,
+(env LIBS=name:path,name:path; e.g. another branch's make -C distributed-training-ina_amd/csrc
+OUT=../../tools/lab/libina_x.so BUILD=build_x) on config 3 as NGA-V packets (V env,
 default 32: 8 x 819,200 packets, 2^20 slots; descriptors) in the orders of ORDERS (worker_major,
 round_robin, jitterJ -- round-robin with every packet displaced by < J positions --, shuffled),
 split rows (ROWS=packed for packed rows).  Per order: the libraries' actions, payload rows and

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Switch A/B lab (experiment only): the in-tree libina.so against another build of it
-(LIB_B: e.g. make -C distributed-training-ina_amd/csrc OUT=../../tools/lab/libina_b.so
-BUILD=build_b EXTRA=-D...) on config 3
+(LIB_B: e.g. another branch's make -C distributed-training-ina_amd/csrc
+OUT=../../tools/lab/libina_b.so BUILD=build_b) on config 3
 as NGA-V packets (V env, 256 or 32; 8 workers; 2^17 / 2^20-slot pool; descriptors) in
 worker-major, round-robin and shuffled arrival, packed rows and split rows.  Per order: the
 two libraries' actions, rewritten rows and registers compared byte for byte on fresh

@@ -627,6 +627,72 @@ def run_blk_shard(dev):
     return rows
 
 
+def run_x16_shard(dev):
+    """bf16 / fp16 buckets on the sharded int16 wire (include/ina_shard_x16.h) at the ResNet-50 size, cold
+    caches, median of 20, the whole set twice in this process (run 1 / run 2), as run_blk_shard.  Each of
+    the four calls -- wire.quantize, wire.quantize_blk from a 16-bit bucket, wire.finish, wire.finish_blk
+    into a 16-bit y (y + out16 + flags) -- beside (a) its fp32 sibling timed twice, the two times'
+    difference being the spread, and (b) what a caller without the 16-bit entry points does around the
+    sibling with a preallocated fp32 buffer: widen first (quantisers), or narrow afterwards (finishes).
+    Bar: no slower than the sibling's slower timing plus the spread (the 16-bit call moves 6 bytes a
+    value against 8, 8 + flags against 10 + flags), and faster than (b); reported, not gated."""
+    from ina_amd import ops, wire
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(19)
+    n, k, V = 25_557_032, 9, 256
+    nblk = (n + V - 1) // V
+    x = torch.randn(n, device=dev, generator=gen) * 1e-2
+    wide = torch.empty(n, dtype=torch.float32, device=dev)
+    w = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+    f = torch.empty(nblk, dtype=torch.uint8, device=dev)
+    kb = ops.block_scales([x], V, bits=16, degree=64)              # the 64-rank wire's scales
+
+    def one(run, name, dt, nb16, nbsib, f16, fsib, fround):
+        ta, tb, tr, tc = _time(fsib), _time(f16), _time(fround), _time(fsib)
+        lo, hi = min(ta, tc), max(ta, tc)
+        bar = hi + (hi - lo)
+        rows.append(_row(f"{name} {dt} [x16 shard, run {run}]", tb, nb16,
+                         sibling_us=[round(ta * 1e6, 2), round(tc * 1e6, 2)], sibling_bytes=int(nbsib),
+                         sibling_spread_us=round((hi - lo) * 1e6, 2), bar_us=round(bar * 1e6, 2),
+                         bar_met=bool(tb <= bar), roundabout_us=round(tr * 1e6, 2), beats_roundabout=bool(tb < tr)))
+
+    for run in (1, 2):
+        for dt in (torch.bfloat16, torch.float16):
+            name = "bf16" if dt == torch.bfloat16 else "fp16"
+            x16 = x.to(dt)
+            y16 = torch.empty(n, dtype=dt, device=dev)
+
+            def widen_then(q):
+                wide.copy_(x16)
+                q(wide)
+
+            one(run, "quantize_i16_wire", name, 6 * n, 8 * n, lambda: wire.quantize(x16, k, out=w),
+                lambda: ops.quantize_i16_wire(x, k, out=w),
+                lambda: widen_then(lambda t: ops.quantize_i16_wire(t, k, out=w)))
+            one(run, f"quantize_i16_wire_blk V={V}", name, 6 * n + nblk, 8 * n + nblk,
+                lambda: wire.quantize_blk(x16, kb, V, out=w), lambda: ops.quantize_i16_wire_blk(x, kb, V, out=w),
+                lambda: widen_then(lambda t: ops.quantize_i16_wire_blk(t, kb, V, out=w)))
+            ops.quantize_i16_wire(x, k, out=w)                     # the same summed wire for every decode
+
+            def then_narrow(fin):
+                fin()
+                y16.copy_(y)
+
+            one(run, "i16_wire_finish (y + out16 + flags)", name, 8 * n + nblk, 10 * n + nblk,
+                lambda: wire.finish(w, k, V, out16=o16, y=y16, overflow=f),
+                lambda: ops.i16_wire_finish(w, k, V, out16=o16, y=y, overflow=f),
+                lambda: then_narrow(lambda: ops.i16_wire_finish(w, k, V, out16=o16, y=y, overflow=f)))
+            one(run, f"i16_wire_finish_blk V={V} (y + out16 + flags)", name, 8 * n + 2 * nblk, 10 * n + 2 * nblk,
+                lambda: wire.finish_blk(w, kb, V, out16=o16, y=y16, overflow=f),
+                lambda: ops.i16_wire_finish_blk(w, kb, V, out16=o16, y=y, overflow=f),
+                lambda: then_narrow(lambda: ops.i16_wire_finish_blk(w, kb, V, out16=o16, y=y, overflow=f)))
+            del x16, y16
+    return rows
+
+
 def _sweep(ops, rows, sweeps, name, knob, values, fn, nbytes):
     """Time fn at each grid cap of one knob; keep all points, restore the default.  The grid-cap
     knobs exist in lab builds only (make EXTRA=-DINA_LAB_KEYS=1): the product library refuses
@@ -1005,4 +1071,5 @@ def run_extra(dev):
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)
     rows += run_blk_shard(dev)
+    rows += run_x16_shard(dev)
     return {"rows": rows, "sweep": sweep, "grid_sweeps": gsweep}

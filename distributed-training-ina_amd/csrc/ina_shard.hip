@@ -21,6 +21,13 @@
 // touched once) over a grid-stride loop; HBM-bound at 8 B/value (quantise: 4 in, 4 out)
 // and 4 + 2 + 4 B/value (finish: wire in, int16 + fp32 out).  Each has a sibling that takes one
 // scale per block of V values (include/ina_shard_blk.h) and reads 1/V byte more per value.
+//
+// bf16 / fp16 buckets (include/ina_shard_x16.h): every kernel here takes its bucket's element type --
+// X of a quantiser's source, Y of a finish's y: float, or ina_chunk.h's h16<XT>.  A lane still owns 4
+// values: one 8-byte access on the 16-bit side (512 B contiguous per wave instruction), one 16-byte
+// access on the 32-bit side, so a 16-bit quantiser moves 6 B/value and a finish 4 + 2 + 2.  Widening
+// is exact and y is rounded once (rne16), so the words are the fp32 instances' on the widened bucket
+// and y is theirs rounded.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,13 +35,10 @@
 #include "ina.h"
 #include "ina_internal.h"
 #include "ina_device.h"
+#include "ina_chunk.h"
 
 namespace ina {
 namespace {
-
-using u32x4 = u32x4_t;
-using u32x2 = u32x2_t;
-using f32x4 = f32x4_t;
 
 constexpr int kBlk = kHostBlock;
 constexpr int32_t kWireHalf = 1 << (kWireShift - 1);
@@ -53,22 +57,33 @@ __device__ __forceinline__ int32_t finish1(uint32_t w, bool& sat) {
     return hi ? 32767 : (lo ? -32768 : v);
 }
 
-__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire(const float* __restrict__ x,
+// a whole chunk at element e, checked against n by the caller: ina_chunk.h's load and store (float:
+// 16 bytes; h16: 8 bytes, widened / rounded in registers) with their test against n folded away
+template <typename X>
+__device__ __forceinline__ f32x4 ldw(const X* p, size_t e) {
+    return ld4(p, e, e + 4);
+}
+template <typename Y>
+__device__ __forceinline__ void stw(f32x4 f, Y* p, size_t e) {
+    st4(f, p, e, e + 4);
+}
+
+template <typename X>
+__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire(const X* __restrict__ x,
                                                             int32_t* __restrict__ wire, size_t n,
                                                             float s, int vec) {
     const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * kBlk;
     const size_t n4 = vec ? n / 4 : 0;
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
     u32x4* w4 = reinterpret_cast<u32x4*>(wire);
     for (size_t i = tid; i < n4; i += stride) {
-        const f32x4 v = __builtin_nontemporal_load(x4 + i);
+        const f32x4 v = ldw(x, 4 * i);
         u32x4 r;
         r.x = (uint32_t)q16w(v.x, s); r.y = (uint32_t)q16w(v.y, s);
         r.z = (uint32_t)q16w(v.z, s); r.w = (uint32_t)q16w(v.w, s);
         stream_store(r, w4 + i);
     }
-    for (size_t i = 4 * n4 + tid; i < n; i += stride) wire[i] = q16w(x[i], s);
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) wire[i] = q16w(ld1(x, i), s);
 }
 
 // Summed wire shard -> int16 (out16) and/or dequantised fp32 (y), per-slot flags.
@@ -76,10 +91,11 @@ __global__ __launch_bounds__(kBlk) void k_quantize_i16_wire(const float* __restr
 // slot is V/4 adjacent lanes, and the group's first lane writes the slot's flag from a
 // wave ballot (one writer per slot: no atomics, no pre-zeroing).  The trip count is
 // uniform per wave so the ballot is convergent.
+template <typename Y>
 __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_vec(const int32_t* __restrict__ wsum,
                                                               size_t n, float inv, int lps, int V,
                                                               int16_t* __restrict__ out16,
-                                                              float* __restrict__ y,
+                                                              Y* __restrict__ y,
                                                               uint8_t* __restrict__ ovf) {
     const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * kBlk;
@@ -102,13 +118,13 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_vec(const int32_t* __r
             if (y) {
                 f32x4 f;
                 f.x = (float)a * inv; f.y = (float)b * inv; f.z = (float)c * inv; f.w = (float)d * inv;
-                stream_store(f, reinterpret_cast<f32x4*>(y + e));
+                stw(f, y, e);
             }
         } else if (e < n) {
             for (size_t j = e; j < n; ++j) {
                 const int32_t r = finish1((uint32_t)wsum[j], sat);
                 if (out16) out16[j] = (int16_t)r;
-                if (y) y[j] = (float)r * inv;
+                if (y) st1((float)r * inv, y, j);
             }
         }
         const unsigned long long m = __ballot(sat);
@@ -121,17 +137,18 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_vec(const int32_t* __r
 }
 
 // any alignment / any V: flags pre-zeroed by the caller, saturating elements store 1
+template <typename Y>
 __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_scalar(const int32_t* __restrict__ wsum,
                                                                  size_t n, float inv, int V,
                                                                  int16_t* __restrict__ out16,
-                                                                 float* __restrict__ y,
+                                                                 Y* __restrict__ y,
                                                                  uint8_t* __restrict__ ovf) {
     const size_t stride = (size_t)gridDim.x * kBlk;
     for (size_t i = (size_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += stride) {
         bool sat = false;
         const int32_t r = finish1((uint32_t)wsum[i], sat);
         if (out16) out16[i] = (int16_t)r;
-        if (y) y[i] = (float)r * inv;
+        if (y) st1((float)r * inv, y, i);
         if (sat && ovf) ovf[i / (size_t)V] = 1;
     }
 }
@@ -143,39 +160,42 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_scalar(const int32_t* 
 // adjacent lanes.  The loops are the siblings': whole chunks first, the ragged tail value by value.
 // A scale is read only for an element below n, so nothing outside kblk[0 .. ceil(n / V)) is touched.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire_blk(const float* __restrict__ x,
+template <typename X>
+__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire_blk(const X* __restrict__ x,
                                                                 const int8_t* __restrict__ kblk,
                                                                 int32_t* __restrict__ wire, size_t n,
                                                                 int shift) {
     const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * kBlk;
     const size_t n4 = n / 4;
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
     u32x4* w4 = reinterpret_cast<u32x4*>(wire);
     for (size_t i = tid; i < n4; i += stride) {
         const float s = pow2f(rd_k(kblk, i >> shift));
-        const f32x4 v = __builtin_nontemporal_load(x4 + i);
+        const f32x4 v = ldw(x, 4 * i);
         u32x4 r;
         r.x = (uint32_t)q16w(v.x, s); r.y = (uint32_t)q16w(v.y, s);
         r.z = (uint32_t)q16w(v.z, s); r.w = (uint32_t)q16w(v.w, s);
         stream_store(r, w4 + i);
     }
-    for (size_t i = 4 * n4 + tid; i < n; i += stride) wire[i] = q16w(x[i], pow2f(rd_k(kblk, i >> (shift + 2))));
+    for (size_t i = 4 * n4 + tid; i < n; i += stride)
+        wire[i] = q16w(ld1(x, i), pow2f(rd_k(kblk, i >> (shift + 2))));
 }
 
 // any alignment / any V
-__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire_blk_scalar(const float* __restrict__ x,
+template <typename X>
+__global__ __launch_bounds__(kBlk) void k_quantize_i16_wire_blk_scalar(const X* __restrict__ x,
                                                                        const int8_t* __restrict__ kblk,
                                                                        int32_t* __restrict__ wire, size_t n,
                                                                        int V) {
     const size_t stride = (size_t)gridDim.x * kBlk;
     for (size_t i = (size_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += stride)
-        wire[i] = q16w(x[i], pow2f(rd_k(kblk, i / (size_t)V)));
+        wire[i] = q16w(ld1(x, i), pow2f(rd_k(kblk, i / (size_t)V)));
 }
 
 // one whole chunk of the finish: 4 wire words at element e -> out16 / y
+template <typename Y>
 __device__ __forceinline__ void finish4(u32x4 w, float inv, size_t e, int16_t* __restrict__ out16,
-                                        float* __restrict__ y, bool& sat) {
+                                        Y* __restrict__ y, bool& sat) {
     const int32_t a = finish1(w.x, sat), b = finish1(w.y, sat);
     const int32_t c = finish1(w.z, sat), d = finish1(w.w, sat);
     if (out16) {
@@ -187,7 +207,7 @@ __device__ __forceinline__ void finish4(u32x4 w, float inv, size_t e, int16_t* _
     if (y) {
         f32x4 f;
         f.x = (float)a * inv; f.y = (float)b * inv; f.z = (float)c * inv; f.w = (float)d * inv;
-        stream_store(f, reinterpret_cast<f32x4*>(y + e));
+        stw(f, y, e);
     }
 }
 
@@ -195,10 +215,11 @@ __device__ __forceinline__ void finish4(u32x4 w, float inv, size_t e, int16_t* _
 // wave whose 64 chunks are all whole -- every wave but the bucket's last -- takes one wave-uniform
 // branch and no per-lane test against n; the last wave tests per lane and finishes the values past
 // the last whole chunk one by one.
+template <typename Y>
 __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_vec(const int32_t* __restrict__ wsum, size_t n,
                                                                   const int8_t* __restrict__ kblk, int shift,
                                                                   int16_t* __restrict__ out16,
-                                                                  float* __restrict__ y,
+                                                                  Y* __restrict__ y,
                                                                   uint8_t* __restrict__ ovf) {
     const size_t tid = (size_t)blockIdx.x * kBlk + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * kBlk;
@@ -220,7 +241,7 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_vec(const int32_t*
                 for (size_t j = e; j < n; ++j) {
                     const int32_t r = finish1((uint32_t)wsum[j], sat);
                     if (out16) out16[j] = (int16_t)r;
-                    if (y) y[j] = (float)r * inv;
+                    if (y) st1((float)r * inv, y, j);
                 }
             }
         }
@@ -234,10 +255,11 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_vec(const int32_t*
 }
 
 // any alignment / any V: flags pre-zeroed by the caller, saturating elements store 1
+template <typename Y>
 __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_scalar(const int32_t* __restrict__ wsum, size_t n,
                                                                      const int8_t* __restrict__ kblk, int V,
                                                                      int16_t* __restrict__ out16,
-                                                                     float* __restrict__ y,
+                                                                     Y* __restrict__ y,
                                                                      uint8_t* __restrict__ ovf) {
     const size_t stride = (size_t)gridDim.x * kBlk;
     for (size_t i = (size_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += stride) {
@@ -245,7 +267,7 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_scalar(const int32
         bool sat = false;
         const int32_t r = finish1((uint32_t)wsum[i], sat);
         if (out16) out16[i] = (int16_t)r;
-        if (y) y[i] = (float)r * pow2f(-rd_k(kblk, s));
+        if (y) st1((float)r * pow2f(-rd_k(kblk, s)), y, i);
         if (sat && ovf) ovf[s] = 1;
     }
 }
@@ -253,6 +275,82 @@ __global__ __launch_bounds__(kBlk) void k_i16_wire_finish_blk_scalar(const int32
 inline bool al(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }
 
 // (vec_v, the vector path's block sizes, is in ina_internal.h)
+
+// The launches, one copy for every element type; the entry points below check their arguments first.
+// A lane's access to a bucket of X is 4 * sizeof(X) bytes, and so is the alignment its vector path
+// needs.  cap: ew_grid_cap() for the fp32 calls; the 16-bit calls also keep under default_grid_cap().
+template <typename X>
+int launch_quantize_wire(const X* x, int32_t* wire, size_t n, int k, int cap, ina_stream_t stream) {
+    const int vec = al(x, 4 * sizeof(X)) && al(wire, 16);
+    hipLaunchKernelGGL(k_quantize_i16_wire<X>, dim3(grid_of(vec ? n / 4 + 1 : n, cap)), dim3(kBlk), 0, hs(stream), x,
+                       wire, n, ldexpf(1.0f, k), vec);
+    return check_launch("quantize_i16_wire");
+}
+
+template <typename Y>
+int launch_wire_finish(const int32_t* wire_sum, size_t n, int k, int V, int16_t* out16, Y* y,
+                       uint8_t* overflow_per_slot, int cap, ina_stream_t stream) {
+    hipStream_t s = hs(stream);
+    const float inv = ldexpf(1.0f, -k);
+    const int l = V / 4;
+    const bool ballot = V % 4 == 0 && l >= 1 && l <= 64 && (l & (l - 1)) == 0;
+    const bool vec = al(wire_sum, 16) && (!out16 || al(out16, 8)) && (!y || al(y, 4 * sizeof(Y)));
+    if (vec && (ballot || !overflow_per_slot)) {
+        hipLaunchKernelGGL(k_i16_wire_finish_vec<Y>, dim3(grid_of((n + 3) / 4, cap)), dim3(kBlk), 0, s, wire_sum, n,
+                           inv, ballot ? l : 1, V, out16, y, overflow_per_slot);
+    } else {
+        if (overflow_per_slot &&
+            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        hipLaunchKernelGGL(k_i16_wire_finish_scalar<Y>, dim3(grid_of(n, cap)), dim3(kBlk), 0, s, wire_sum, n, inv, V,
+                           out16, y, overflow_per_slot);
+    }
+    return check_launch("i16_wire_finish");
+}
+
+template <typename X>
+int launch_quantize_wire_blk(const X* x, const int8_t* kblk, int V, int32_t* wire, size_t n, int cap,
+                             ina_stream_t stream) {
+    int shift;
+    if (vec_v(V, shift) && al(x, 4 * sizeof(X)) && al(wire, 16)) {
+        hipLaunchKernelGGL(k_quantize_i16_wire_blk<X>, dim3(grid_of(n / 4 + 1, cap)), dim3(kBlk), 0, hs(stream), x,
+                           kblk, wire, n, shift);
+    } else {
+        hipLaunchKernelGGL(k_quantize_i16_wire_blk_scalar<X>, dim3(grid_of(n, cap)), dim3(kBlk), 0, hs(stream), x,
+                           kblk, wire, n, V);
+    }
+    return check_launch("quantize_blk_i16_wire");
+}
+
+template <typename Y>
+int launch_wire_finish_blk(const int32_t* wire_sum, size_t n, const int8_t* kblk, int V, int16_t* out16, Y* y,
+                           uint8_t* overflow_per_slot, int cap, ina_stream_t stream) {
+    hipStream_t s = hs(stream);
+    int shift;
+    if (vec_v(V, shift) && al(wire_sum, 16) && (!out16 || al(out16, 8)) && (!y || al(y, 4 * sizeof(Y)))) {
+        hipLaunchKernelGGL(k_i16_wire_finish_blk_vec<Y>, dim3(grid_of((n + 3) / 4, cap)), dim3(kBlk), 0, s, wire_sum,
+                           n, kblk, shift, out16, y, overflow_per_slot);
+    } else {
+        if (overflow_per_slot &&
+            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        hipLaunchKernelGGL(k_i16_wire_finish_blk_scalar<Y>, dim3(grid_of(n, cap)), dim3(kBlk), 0, s, wire_sum, n,
+                           kblk, V, out16, y, overflow_per_slot);
+    }
+    return check_launch("i16_wire_finish_blk");
+}
+
+// the 16-bit calls' grid cap: the elementwise one, held under tuning key 0 as well
+inline int x16_grid_cap() {
+    const int a = ew_grid_cap(), b = default_grid_cap();
+    return a < b ? a : b;
+}
+inline int check_al2(const void* p) {
+    if ((uintptr_t)p & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
+    return INA_OK;
+}
+using bf16 = h16<INA_X16_BF16>;
+using f16 = h16<INA_X16_F16>;
 
 }  // namespace
 }  // namespace ina
@@ -265,10 +363,7 @@ int ina_quantize_f32_i16_wire(const float* x, int32_t* wire, size_t n, int k, in
     if (int rc = check_k(k)) return rc;
     if (n == 0) return INA_OK;
     if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
-    const int vec = al(x, 16) && al(wire, 16);
-    hipLaunchKernelGGL(k_quantize_i16_wire, dim3(grid_of(vec ? n / 4 + 1 : n, ew_grid_cap())), dim3(kBlk), 0,
-                       hs(stream), x, wire, n, ldexpf(1.0f, k), vec);
-    return check_launch("quantize_i16_wire");
+    return launch_quantize_wire(x, wire, n, k, ew_grid_cap(), stream);
 }
 
 int ina_i16_wire_finish(const int32_t* wire_sum, size_t n, int k, int V, int16_t* out16, float* y,
@@ -277,22 +372,7 @@ int ina_i16_wire_finish(const int32_t* wire_sum, size_t n, int k, int V, int16_t
     if (V <= 0) return set_error(INA_EINVAL, "V must be > 0%s", "");
     if (n == 0) return INA_OK;
     if (!wire_sum) return set_error(INA_EINVAL, "null pointer%s", "");
-    hipStream_t s = hs(stream);
-    const float inv = ldexpf(1.0f, -k);
-    const int l = V / 4;
-    const bool ballot = V % 4 == 0 && l >= 1 && l <= 64 && (l & (l - 1)) == 0;
-    const bool vec = al(wire_sum, 16) && (!out16 || al(out16, 8)) && (!y || al(y, 16));
-    if (vec && (ballot || !overflow_per_slot)) {
-        hipLaunchKernelGGL(k_i16_wire_finish_vec, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, s,
-                           wire_sum, n, inv, ballot ? l : 1, V, out16, y, overflow_per_slot);
-    } else {
-        if (overflow_per_slot &&
-            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
-        hipLaunchKernelGGL(k_i16_wire_finish_scalar, dim3(grid_of(n, ew_grid_cap())), dim3(kBlk), 0, s, wire_sum, n,
-                           inv, V, out16, y, overflow_per_slot);
-    }
-    return check_launch("i16_wire_finish");
+    return launch_wire_finish(wire_sum, n, k, V, out16, y, overflow_per_slot, ew_grid_cap(), stream);
 }
 
 int ina_quantize_blk_f32_i16_wire(const float* x, const int8_t* kblk, int V, int32_t* wire, size_t n,
@@ -301,15 +381,7 @@ int ina_quantize_blk_f32_i16_wire(const float* x, const int8_t* kblk, int V, int
     if (n == 0) return INA_OK;
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
-    int shift;
-    if (vec_v(V, shift) && al(x, 16) && al(wire, 16)) {
-        hipLaunchKernelGGL(k_quantize_i16_wire_blk, dim3(grid_of(n / 4 + 1, ew_grid_cap())), dim3(kBlk), 0,
-                           hs(stream), x, kblk, wire, n, shift);
-    } else {
-        hipLaunchKernelGGL(k_quantize_i16_wire_blk_scalar, dim3(grid_of(n, ew_grid_cap())), dim3(kBlk), 0,
-                           hs(stream), x, kblk, wire, n, V);
-    }
-    return check_launch("quantize_blk_i16_wire");
+    return launch_quantize_wire_blk(x, kblk, V, wire, n, ew_grid_cap(), stream);
 }
 
 int ina_i16_wire_finish_blk(const int32_t* wire_sum, size_t n, const int8_t* kblk, int V, int16_t* out16,
@@ -318,19 +390,63 @@ int ina_i16_wire_finish_blk(const int32_t* wire_sum, size_t n, const int8_t* kbl
     if (n == 0) return INA_OK;
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     if (!wire_sum) return set_error(INA_EINVAL, "null pointer%s", "");
-    hipStream_t s = hs(stream);
-    int shift;
-    if (vec_v(V, shift) && al(wire_sum, 16) && (!out16 || al(out16, 8)) && (!y || al(y, 16))) {
-        hipLaunchKernelGGL(k_i16_wire_finish_blk_vec, dim3(grid_of((n + 3) / 4, ew_grid_cap())), dim3(kBlk), 0, s,
-                           wire_sum, n, kblk, shift, out16, y, overflow_per_slot);
-    } else {
-        if (overflow_per_slot &&
-            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
-        hipLaunchKernelGGL(k_i16_wire_finish_blk_scalar, dim3(grid_of(n, ew_grid_cap())), dim3(kBlk), 0, s,
-                           wire_sum, n, kblk, V, out16, y, overflow_per_slot);
-    }
-    return check_launch("i16_wire_finish_blk");
+    return launch_wire_finish_blk(wire_sum, n, kblk, V, out16, y, overflow_per_slot, ew_grid_cap(), stream);
+}
+
+// ---- include/ina_shard_x16.h: the four above with a 16-bit x / y ----
+
+int ina_quantize_x16_i16_wire(const void* x, int xtype, int32_t* wire, size_t n, int k, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (int rc = check_k(k)) return rc;
+    if (n == 0) return INA_OK;
+    if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (int rc = check_al2(x)) return rc;
+    if (xtype == INA_X16_BF16)
+        return launch_quantize_wire(static_cast<const bf16*>(x), wire, n, k, x16_grid_cap(), stream);
+    return launch_quantize_wire(static_cast<const f16*>(x), wire, n, k, x16_grid_cap(), stream);
+}
+
+int ina_i16_wire_finish_x16(const int32_t* wire_sum, size_t n, int k, int V, int16_t* out16, void* y, int ytype,
+                            uint8_t* overflow_per_slot, ina_stream_t stream) {
+    if (int rc = check_x16_type(ytype)) return rc;
+    if (int rc = check_k(k)) return rc;
+    if (V <= 0) return set_error(INA_EINVAL, "V must be > 0%s", "");
+    if (n == 0) return INA_OK;
+    if (!wire_sum) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (int rc = check_al2(y)) return rc;
+    if (ytype == INA_X16_BF16)
+        return launch_wire_finish(wire_sum, n, k, V, out16, static_cast<bf16*>(y), overflow_per_slot, x16_grid_cap(),
+                                  stream);
+    return launch_wire_finish(wire_sum, n, k, V, out16, static_cast<f16*>(y), overflow_per_slot, x16_grid_cap(),
+                              stream);
+}
+
+int ina_quantize_blk_x16_i16_wire(const void* x, int xtype, const int8_t* kblk, int V, int32_t* wire, size_t n,
+                                  ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (V < 1) return set_error(INA_EINVAL, "V must be >= 1%s", "");
+    if (n == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (int rc = check_al2(x)) return rc;
+    if (xtype == INA_X16_BF16)
+        return launch_quantize_wire_blk(static_cast<const bf16*>(x), kblk, V, wire, n, x16_grid_cap(), stream);
+    return launch_quantize_wire_blk(static_cast<const f16*>(x), kblk, V, wire, n, x16_grid_cap(), stream);
+}
+
+int ina_i16_wire_finish_blk_x16(const int32_t* wire_sum, size_t n, const int8_t* kblk, int V, int16_t* out16,
+                                void* y, int ytype, uint8_t* overflow_per_slot, ina_stream_t stream) {
+    if (int rc = check_x16_type(ytype)) return rc;
+    if (V < 1) return set_error(INA_EINVAL, "V must be >= 1%s", "");
+    if (n == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (!wire_sum) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (int rc = check_al2(y)) return rc;
+    if (ytype == INA_X16_BF16)
+        return launch_wire_finish_blk(wire_sum, n, kblk, V, out16, static_cast<bf16*>(y), overflow_per_slot,
+                                      x16_grid_cap(), stream);
+    return launch_wire_finish_blk(wire_sum, n, kblk, V, out16, static_cast<f16*>(y), overflow_per_slot,
+                                  x16_grid_cap(), stream);
 }
 
 }  // extern "C"

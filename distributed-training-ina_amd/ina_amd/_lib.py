@@ -166,6 +166,14 @@ SIGNATURES_BLK_X16 = {
     "ina_dequantize_blk_i16_x16": [_vp, _vp, _i, _vp, _i, _sz, _vp],
     "ina_quantize_pack_nga_multi_split_blk_x16": [_vp, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
 }
+# bf16 / fp16 buckets on the sharded int16 wire (include/ina_shard_x16.h): the wire siblings' arguments
+# with the type code after the 16-bit pointer (x of a quantiser, y of a finish)
+SIGNATURES_SHARD_X16 = {
+    "ina_quantize_x16_i16_wire": [_vp, _i, _vp, _sz, _i, _vp],
+    "ina_quantize_blk_x16_i16_wire": [_vp, _i, _vp, _i, _vp, _sz, _vp],
+    "ina_i16_wire_finish_x16": [_vp, _sz, _i, _i, _vp, _vp, _i, _vp, _vp],
+    "ina_i16_wire_finish_blk_x16": [_vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _vp],
+}
 # error feedback (include/ina_ef.h): the residual follows the base (the packs: the buckets)
 SIGNATURES_EF = {
     "ina_quantize_ef_f32_i32": [_vp, _vp, _vp, _vp, _sz, _i, _vp],
@@ -200,7 +208,7 @@ def open_library(path: str) -> C.CDLL:
     lib = C.CDLL(path)
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
-                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF}.items():
+                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -50,6 +50,18 @@ error_feedback=True (ShardedAggregator only; include/ina_shard_ef.h, ina_amd.ef)
 its rounding to the wire dropped in an fp32 residual on its GPU and adds it to the next step's
 bucket, in the quantiser's own launch.  The collectives, the decode and every byte on xGMI are those
 of the plain step: the residual never leaves the rank.
+
+bf16 / fp16 buckets (both classes; include/ina_shard_x16.h, ina_amd.wire, ina_amd.blk): a call takes a
+float32, bfloat16 or float16 bucket (RangeAggregator: slices, one dtype for all of them) and reads
+it as it is -- no widened fp32 copy.  Widening is exact, so with the default out_dtype=torch.float32
+the aggregate, the flags and `kblk` are bit for bit those of the same aggregator on grad.float().
+out_dtype=torch.bfloat16 / torch.float16 makes `full` and the decoded shard that dtype: the result is
+that fp32 aggregate rounded once to nearest even.  On the i32 wire the owner decodes its shard
+straight into 16 bits and the all-gather moves 2 bytes a value instead of 4 (gather_bytes says so);
+on the i16 wire the gather moves the int16 sums as before and the expand after it writes 16 bits;
+on one rank or after an all-reduce the whole-bucket decode writes them (wire.finish* with a 16-bit
+y).  Error feedback takes fp32 buckets only: a 16-bit bucket with error_feedback=True is refused at
+the call.
 """
 from __future__ import annotations
 
@@ -58,7 +70,8 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib, ef, ops
+from . import _lib, blk, ef, ops
+from . import wire as _wire          # (the aggregators' `wire` argument is the wire's name)
 
 
 class ShardPlan:
@@ -177,6 +190,15 @@ def _block_k(k) -> bool:
     return False
 
 
+_OUT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _out_dtype(out_dtype) -> torch.dtype:
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"out_dtype must be torch.float32, torch.bfloat16 or torch.float16, got {out_dtype!r}")
+    return out_dtype
+
+
 def all_gather_shards(shard: torch.Tensor, plan: ShardPlan, group=None, out=None,
                       async_op: bool = False):
     """[count] per rank -> [world * count] (count = plan.shard values, or its slot flags).
@@ -233,11 +255,15 @@ class ShardedAggregator:
     MIN; with chunks > 1 each chunk's quantise takes the matching slice of the residual.  Everything
     after the quantise -- collectives, decode, gather, gather_bytes, scale_bytes -- is unchanged,
     and with the default False so is every byte of the step.  Device buckets only.
+    A bucket may be float32, bfloat16 or float16 (not with error_feedback=True) and is read as it is;
+    out_dtype (float32, bfloat16 or float16) is the dtype of `full`, of the decoded shard and, on the
+    i32 wire, of the all-gather -- the module docstring states what equals what.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
                  wire: str = "i32", V: int = 256, collective: str = "rs_ag", chunks: int = 1,
-                 error_feedback: bool = False):
+                 error_feedback: bool = False, out_dtype: torch.dtype = torch.float32):
+        self.out_dtype = _out_dtype(out_dtype)
         if wire not in ("i32", "i16"):
             raise ValueError("wire must be 'i32' or 'i16'")
         if collective not in ("rs_ag", "a2a", "allreduce"):
@@ -275,7 +301,7 @@ class ShardedAggregator:
             tot = max(tot, self.cpad)
         # one allocation backs both the whole-bucket and the chunked views; pad stays 0
         self._qbuf = torch.zeros(tot, dtype=torch.int32, device=dev)
-        self._fbuf = torch.empty(tot, dtype=torch.float32, device=dev)
+        self._fbuf = torch.empty(tot, dtype=self.out_dtype, device=dev)
         self.q, self.full = self._qbuf[: self.plan.padded], self._fbuf[: self.plan.padded]
         # whole-bucket shard buffers (sum_shard, f_shard, s16_shard): used by the unchunked
         # step, aggregate_int and the phase_* methods; the pipelined step (chunks > 1) has
@@ -284,7 +310,7 @@ class ShardedAggregator:
         self._shard_bufs = {}
         if self.chunks == 1:                     # allocate now, outside any timed step
             self._shard_buf("sum", torch.int32)
-            self._shard_buf("f", torch.float32)
+            self._shard_buf("f", self.out_dtype)
         if wire == "i16":
             self.slots_per_shard = self.plan.shard // V
             self.ovf_shard = torch.empty(self.slots_per_shard, dtype=torch.uint8, device=dev)
@@ -308,7 +334,7 @@ class ShardedAggregator:
             m = self.chunks * self.sc
             self.sum_c = torch.empty(m, dtype=torch.int32, device=dev)
             if wire == "i32":
-                self.f_c = torch.empty(m, dtype=torch.float32, device=dev)
+                self.f_c = torch.empty(m, dtype=self.out_dtype, device=dev)
             else:
                 self.s16_c = torch.empty(m, dtype=torch.int16, device=dev)
                 self.ovf_c = torch.empty(m // V, dtype=torch.uint8, device=dev)
@@ -332,7 +358,7 @@ class ShardedAggregator:
 
     @property
     def f_shard(self) -> torch.Tensor:
-        return self._shard_buf("f", torch.float32)
+        return self._shard_buf("f", self.out_dtype)
 
     @property
     def s16_shard(self) -> torch.Tensor:
@@ -371,7 +397,7 @@ class ShardedAggregator:
         shard = self.chunks * self.sc if self.chunks > 1 else self.plan.shard
         if self.collective == "allreduce":
             return (self.world - 1) * shard * 4
-        per = shard * (2 if self.wire == "i16" else 4)
+        per = shard * (2 if self.wire == "i16" else self._fbuf.element_size())
         if self.wire == "i16":
             per += shard // self.V
         return (self.world - 1) * per
@@ -397,7 +423,7 @@ class ShardedAggregator:
         if self.world == 1 or self.collective == "allreduce":
             self._decode(self.q, self.full, self.ovf_full if self.wire == "i16" else None)
         elif self.blk and self.wire == "i32":
-            ops.dequantize_blk(self.sum_shard, self._kshard(), self.V, out=self.f_shard)
+            blk.dequantize(self.sum_shard, self._kshard(), self.V, out=self.f_shard)
         elif self.blk:
             ops.i16_wire_finish_blk(self.sum_shard, self._kshard(), self.V, out16=self.s16_shard,
                                     overflow=self.ovf_shard, want_y=False)
@@ -420,15 +446,22 @@ class ShardedAggregator:
         """i16 wire at world > 1: dequantise the gathered int16 sums on every rank."""
         if self.world > 1 and self.wire == "i16" and self.collective != "allreduce":
             if self.blk:
-                ops.dequantize_blk(self.s16_full, self._kbuf, self.V, out=self.full)
+                blk.dequantize(self.s16_full, self._kbuf, self.V, out=self.full)
             else:
                 ops.dequantize(self.s16_full, self.k, out=self.full)
 
+    def _bucket(self, grad: torch.Tensor) -> torch.Tensor:
+        """The call's bucket, flat: float32, bfloat16 or float16 (the quantisers dispatch on it)."""
+        if grad.numel() != self.plan.n:
+            raise ValueError("bucket size changed")
+        if self.error_feedback and isinstance(grad, torch.Tensor) and grad.dtype in (torch.bfloat16, torch.float16):
+            raise TypeError(f"error_feedback=True takes float32 buckets, got {grad.dtype}: the error-feedback wire "
+                            f"quantisers and block scales have no 16-bit source")
+        return grad.reshape(-1)
+
     def _quantize(self, grad: torch.Tensor):
         n = self.plan.n
-        if grad.numel() != n:
-            raise ValueError("bucket size changed")
-        x = grad.reshape(-1)
+        x = self._bucket(grad)
         r = self.residual
         if self.blk:
             # this rank's scales for `world` summands (error feedback: of x + residual), the MIN over
@@ -436,17 +469,17 @@ class ShardedAggregator:
             kb = self.kblk
             bits = 32 if self.wire == "i32" else 16
             if r is None:
-                ops.block_scales([x], self.V, bits=bits, degree=self.world, out=kb)
+                blk.block_scales([x], self.V, bits=bits, degree=self.world, out=kb)
             else:
                 ef.block_scales([x], [r], self.V, bits=bits, degree=self.world, out=kb)
             agree_block_scales(kb, self.group)
             if self.wire == "i32":
                 if r is None:
-                    ops.quantize_blk(x, kb, self.V, out=self.q[:n])
+                    blk.quantize(x, kb, self.V, out=self.q[:n])
                 else:
                     ef.quantize_blk(x, r, self.V, kblk=kb, out=self.q[:n])
             elif r is None:
-                ops.quantize_i16_wire_blk(x, kb, self.V, out=self.q[:n])
+                _wire.quantize_blk(x, kb, self.V, out=self.q[:n])
             else:
                 ef.quantize_i16_wire_blk(x, r, kb, self.V, out=self.q[:n])
         else:
@@ -461,26 +494,24 @@ class ShardedAggregator:
             else:
                 ef.quantize(x, r, self.k, out=out)
         elif r is None:
-            ops.quantize_i16_wire(x, self.k, out=out)
+            _wire.quantize(x, self.k, out=out)
         else:
             ef.quantize_i16_wire(x, r, self.k, out=out)
 
     def _decode(self, src: torch.Tensor, y: torch.Tensor, ovf=None):
         """The whole (padded) bucket: one rank, or after an all-reduce."""
         if self.blk and self.wire == "i32":
-            ops.dequantize_blk(src, self._kbuf, self.V, out=y)
+            blk.dequantize(src, self._kbuf, self.V, out=y)
         elif self.blk:
-            ops.i16_wire_finish_blk(src, self._kbuf, self.V, y=y, overflow=ovf, want_out16=False)
+            _wire.finish_blk(src, self._kbuf, self.V, y=y, overflow=ovf, want_out16=False)
         elif self.wire == "i32":
             ops.dequantize(src, self.k, out=y)
         else:
-            ops.i16_wire_finish(src, self.k, self.V, y=y, overflow=ovf, want_out16=False)
+            _wire.finish(src, self.k, self.V, y=y, overflow=ovf, want_out16=False)
 
     def _call_chunked(self, grad: torch.Tensor) -> torch.Tensor:
         n, L, sc, V = self.plan.n, self.cplan.padded, self.sc, self.V
-        if grad.numel() != n:
-            raise ValueError("bucket size changed")
-        x = grad.reshape(-1)
+        x = self._bucket(grad)
         rs = []
         for c in range(self.chunks):           # quantise chunk c, then its RS on RCCL's stream
             lo, hi = c * L, min((c + 1) * L, n)
@@ -512,8 +543,8 @@ class ShardedAggregator:
         return self._fbuf[:n]
 
     def __call__(self, grad: torch.Tensor) -> torch.Tensor:
-        """fp32 [n] local bucket -> fp32 [n] dequantised sum over all ranks (one rank:
-        the collectives are identities, quantise -> decode)."""
+        """[n] local bucket (float32, bfloat16 or float16) -> [n] dequantised sum over all ranks as
+        out_dtype (one rank: the collectives are identities, quantise -> decode)."""
         if self.chunks > 1:
             return self._call_chunked(grad)
         self.phase_quantize(grad)
@@ -524,7 +555,7 @@ class ShardedAggregator:
         return self.full[: self.plan.n]
 
     def aggregate_int(self, grad: torch.Tensor) -> torch.Tensor:
-        """fp32 [n] -> this rank's integer shard of the aggregate (no gather): the
+        """[n] bucket -> this rank's integer shard of the aggregate (no gather): the
         int32 wrapped sum, or on the i16 wire the int16 saturated sum (its slot flags
         in `ovf_shard`).  k="block": the integers are scaled per block; read `kblk` next to them.
         error_feedback=True: this is a step like any other -- it quantises grad + residual and
@@ -558,10 +589,14 @@ class RangeAggregator:
     residual of a slice lives with the worker that rounded it, not with the GPU that sums it (the
     reason include/ina_ef.h gives for leaving out the fused quantise + reduce calls).  A worker that
     wants it applies ina_amd.ef before it sends its slices.
+    The slices may be float32, bfloat16 or float16, one dtype for all of them, and are read as they
+    are; out_dtype (float32, bfloat16 or float16) is the dtype of `full` and of the decoded range, and
+    on the i32 wire the all-gather then moves 2 bytes a value.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
-                 wire: str = "i32", V: int = 256):
+                 wire: str = "i32", V: int = 256, out_dtype: torch.dtype = torch.float32):
+        self.out_dtype = _out_dtype(out_dtype)
         if wire not in ("i32", "i16"):
             raise ValueError("wire must be 'i32' or 'i16'")
         if V <= 0:
@@ -577,9 +612,9 @@ class RangeAggregator:
         self.lo, self.hi = self.plan.range_of(self.rank)
         sdt = torch.int32 if wire == "i32" else torch.int16
         self.sum_shard = torch.zeros(self.plan.shard, dtype=sdt, device=dev)
-        self.f_shard = torch.zeros(self.plan.shard, dtype=torch.float32, device=dev)   # pad stays 0
+        self.f_shard = torch.zeros(self.plan.shard, dtype=self.out_dtype, device=dev)   # pad stays 0
         # one rank: the gather is an identity, so the decode writes the aggregate in place
-        self.full = self.f_shard if self.world == 1 else torch.empty(self.plan.padded, dtype=torch.float32,
+        self.full = self.f_shard if self.world == 1 else torch.empty(self.plan.padded, dtype=self.out_dtype,
                                                                      device=dev)
         if wire == "i16":
             self.slots_per_shard = self.plan.shard // V
@@ -629,10 +664,10 @@ class RangeAggregator:
             return 0
         nb = -(-m // self.V)
         if self.blk and self.wire == "i32":
-            ops.quantize_reduce_blk(slices, self.V, out=self.sum_shard[:m], kblk_out=self.k_shard[:nb])
+            blk.quantize_reduce(slices, self.V, out=self.sum_shard[:m], kblk_out=self.k_shard[:nb])
         elif self.blk:
-            ops.quantize_reduce_i16_blk(slices, self.V, out=self.sum_shard[:m], overflow=self.ovf_shard[:nb],
-                                        kblk_out=self.k_shard[:nb])
+            blk.quantize_reduce_i16(slices, self.V, out=self.sum_shard[:m], overflow=self.ovf_shard[:nb],
+                                    kblk_out=self.k_shard[:nb])
         elif self.wire == "i32":
             ops.quantize_reduce(slices, self.k, out=self.sum_shard[:m])
         else:
@@ -645,7 +680,7 @@ class RangeAggregator:
         """Bytes the all-gather brings to each rank over xGMI (values + flags)."""
         if self.world == 1:
             return 0
-        per = self.plan.shard * (2 if self.wire == "i16" else 4)
+        per = self.plan.shard * (2 if self.wire == "i16" else self.f_shard.element_size())
         if self.wire == "i16":
             per += self.slots_per_shard
         if self.blk:
@@ -658,7 +693,7 @@ class RangeAggregator:
         m = self._reduce(slices)
         if m and (self.wire == "i32" or self.world == 1):
             if self.blk:
-                ops.dequantize_blk(self.sum_shard[:m], self.k_shard, self.V, out=self.f_shard[:m])
+                blk.dequantize(self.sum_shard[:m], self.k_shard, self.V, out=self.f_shard[:m])
             else:
                 ops.dequantize(self.sum_shard[:m], self.k, out=self.f_shard[:m])
         return m
@@ -678,19 +713,20 @@ class RangeAggregator:
         """i16 wire at world > 1: dequantise the gathered int16 sums on every rank."""
         if self.world > 1 and self.wire == "i16":
             if self.blk:
-                ops.dequantize_blk(self.s16_full, self.k_full, self.V, out=self.full)
+                blk.dequantize(self.s16_full, self.k_full, self.V, out=self.full)
             else:
                 ops.dequantize(self.s16_full, self.k, out=self.full)
 
     def __call__(self, slices) -> torch.Tensor:
-        """W fp32 slices of this rank's range -> fp32 [n] aggregate on every rank."""
+        """W slices of this rank's range (float32, bfloat16 or float16) -> [n] aggregate on every rank,
+        as out_dtype."""
         self.phase_reduce_decode(slices)
         self.phase_all_gather()
         self.phase_expand()
         return self.full[: self.plan.n]
 
     def aggregate_int(self, slices) -> torch.Tensor:
-        """W fp32 slices -> this rank's integer aggregate (int32 wrapped, or int16
+        """W slices -> this rank's integer aggregate (int32 wrapped, or int16
         saturated with its slot flags in `ovf_shard`), no gather.  k="block": scaled per block, the
         scales in `k_shard`."""
         m = self._reduce(slices)

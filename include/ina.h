@@ -402,6 +402,9 @@ int ina_switch_process(const ina_switch_state_t* st, uint8_t* pkts, size_t npkts
 /* Per-block scales on the int16 wire of a sharded bucket (the block-scaled wire quantiser and its
  * decode); the contract is stated in ina_shard_blk.h. */
 #include "ina_shard_blk.h"   /* the block-scaled int16 wire */
+/* bf16 / fp16 buckets on that wire (16-bit sources for both wire quantisers, a 16-bit y for both
+ * decodes); the contract is stated in ina_shard_x16.h. */
+#include "ina_shard_x16.h"   /* ina_quantize_x16_i16_wire ... ina_i16_wire_finish_blk_x16 */
 
 /* Diagnostic: which slot-sort path the last call over `scratch` took (a batch of npkts
  * packets, more than 768 of them; the one-workgroup small-batch paths do not record one; the

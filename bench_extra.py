@@ -372,6 +372,43 @@ def run_ef_shard(dev):
     return rows
 
 
+def run_sr(dev):
+    """Stochastic rounding (include/ina_sr.h) at the ResNet-50 size, cold caches, median of 20, the set
+    twice in this process (run 1 / run 2): sr.quantize, sr.quantize_i16 (V = 256) and sr.quantize_i16_wire
+    from fp32 and bf16 buckets, each beside its round-to-nearest sibling timed twice in the same run.  An
+    SR call moves its sibling's bytes, so what is reported is SR time over sibling time (the faster of
+    the sibling's two timings) next to the sibling's own spread.  Nothing is gated: no bar was known for
+    ten Philox rounds under these streams."""
+    from ina_amd import ops, sr, wire
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(29)
+    n, k, V, seed = 25_557_032, 9, 256, 0x1234
+    x32 = torch.randn(n, device=dev, generator=gen) * 1e-2
+    q32 = torch.empty(n, dtype=torch.int32, device=dev)
+    q16 = torch.empty(n, dtype=torch.int16, device=dev)
+    ovf = torch.empty((n + V - 1) // V, dtype=torch.uint8, device=dev)
+
+    def row(run, name, nbytes, f_sr, f_sib):
+        ta, ts, tb = _time(f_sib), _time(f_sr), _time(f_sib)
+        lo, hi = min(ta, tb), max(ta, tb)
+        rows.append(_row(f"{name} [sr, run {run}]", ts, nbytes, sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)],
+                         sibling_spread_us=round((hi - lo) * 1e6, 2), sr_over_sibling=round(ts / lo, 3),
+                         sr_over_slower_sibling=round(ts / hi, 3)))
+
+    for run in (1, 2):
+        for x, tag in ((x32, "f32"), (x32.to(torch.bfloat16), "bf16")):
+            b = x.element_size()
+            row(run, f"quantize {tag}->i32", (b + 4) * n, lambda: sr.quantize(x, k, seed, step=run, out=q32),
+                lambda: ops.quantize(x, k, out=q32))
+            row(run, f"quantize_i16 {tag}->i16 V={V}", (b + 2) * n + ovf.numel(),
+                lambda: sr.quantize_i16(x, k, V, seed, step=run, out=q16, overflow=ovf),
+                lambda: ops.quantize_i16(x, k, V, out=q16, overflow=ovf))
+            row(run, f"quantize_i16_wire {tag}->wire", (b + 4) * n,
+                lambda: sr.quantize_i16_wire(x, k, seed, step=run, out=q32), lambda: wire.quantize(x, k, out=q32))
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1067,6 +1104,7 @@ def run_extra(dev):
     rows += run_blk(dev)
     rows += run_ef(dev)
     rows += run_ef_shard(dev)
+    rows += run_sr(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

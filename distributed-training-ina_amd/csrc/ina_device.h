@@ -94,22 +94,24 @@ __device__ __forceinline__ void packet_store(T v, T* p) {
 // ---------------------------------------------------------------------------
 // quantiser (build-defined, see include/ina.h): sat(rne(x * 2^k)), NaN -> 0
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int32_t q32(float x, float s) {
-    float y = __builtin_rintf(x * s);
+// (each quantiser is its rounding, rintf(x * s), then the clamp / NaN handling of the rounded y: the
+// *_of functions, which the stochastic-rounding kernels of ina_sr.hip run on their own y)
+__device__ __forceinline__ int32_t q32_of(float y) {
     int32_t r = (int32_t)y;                         // in-range lanes only are selected
     r = (y >= 2147483648.0f) ? INT32_MAX : r;
     r = (y < -2147483648.0f) ? INT32_MIN : r;
     return (y != y) ? 0 : r;
 }
+__device__ __forceinline__ int32_t q32(float x, float s) { return q32_of(__builtin_rintf(x * s)); }
 
 // returns the int16 value widened to int32; *sat |= clamped-or-NaN
-__device__ __forceinline__ int32_t q16(float x, float s, bool& sat) {
-    float y = __builtin_rintf(x * s);
+__device__ __forceinline__ int32_t q16_of(float y, bool& sat) {
     // one v_med3_f32 clamps; a clamped value, +-inf or NaN differs from y
     const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);
     sat |= !(c == y);
     return (y != y) ? 0 : (int32_t)c;
 }
+__device__ __forceinline__ int32_t q16(float x, float s, bool& sat) { return q16_of(__builtin_rintf(x * s), sat); }
 
 __device__ __forceinline__ int32_t sat16(int32_t a, bool& sat) {
     bool hi = a > 32767, lo = a < -32768;
@@ -122,13 +124,13 @@ __device__ __forceinline__ int32_t sat16(int32_t a, bool& sat) {
 // it -- q16 + (sat << 22).  The one copy: the wire quantisers of ina_shard.hip and their
 // error-feedback siblings (the kernels of ina_blk.hip) run it.
 constexpr int kWireShift = INA_I16_WIRE_SHIFT;   // 22
-__device__ __forceinline__ int32_t q16w(float x, float s) {
-    const float y = __builtin_rintf(x * s);
+__device__ __forceinline__ int32_t q16w_of(float y) {
     const float c = __builtin_amdgcn_fmed3f(y, -32768.0f, 32767.0f);   // one v_med3_f32
     const int32_t v = (y != y) ? 0 : (int32_t)c;
     const int32_t sat = !(c == y);               // clamped, +-inf or NaN
     return v + (sat << kWireShift);
 }
+__device__ __forceinline__ int32_t q16w(float x, float s) { return q16w_of(__builtin_rintf(x * s)); }
 // q16 back out of one rank's word: its low 22 bits, sign-extended (|q16| <= 2^15, sat is 0 or 1)
 __device__ __forceinline__ int32_t wire_q16(int32_t w) {
     return (int32_t)((uint32_t)w << (32 - kWireShift)) >> (32 - kWireShift);

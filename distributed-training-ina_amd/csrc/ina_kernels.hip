@@ -2749,11 +2749,20 @@ int ina_absmax_multi_f32(const float* const* xs, int W, const float* base, size_
 int ina_scale_for(float absmax, int W, int bits, int* k_out) {
     // largest k with W * (absmax * 2^k + 1/2) <= 2^(bits-1) - 1: no worker value and no
     // W-way sum saturates (each quantised value rounds by at most 1/2)
+    return ina::scale_for_round(absmax, W, bits, 0.5, k_out);
+}
+
+}  // extern "C"
+
+// the largest k in [-126, 127] with W * (absmax * 2^k + round) <= 2^(bits-1) - 1, round what one
+// quantised value can gain by rounding: 1/2 to nearest (ina_scale_for), 1 stochastically
+// (ina_scale_for_sr, ina_sr.hip)
+int ina::scale_for_round(float absmax, int W, int bits, double round, int* k_out) {
     if (!k_out) return set_error(INA_EINVAL, "null k_out%s", "");
     if (W < 1 || (bits != 16 && bits != 32)) return set_error(INA_EINVAL, "W >= 1, bits 16 or 32%s", "");
     if (!(absmax >= 0.0f) || std::isinf(absmax))
         return set_error(INA_EINVAL, "absmax must be finite and >= 0%s", "");
-    const double lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)W - 0.5;
+    const double lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)W - round;
     if (lim <= 0.0) return set_error(INA_EINVAL, "too many workers for this width%s", "");
     if (absmax == 0.0f) {
         *k_out = 127;
@@ -2766,6 +2775,8 @@ int ina_scale_for(float absmax, int W, int bits, int* k_out) {
     *k_out = k;
     return INA_OK;
 }
+
+extern "C" {
 
 int ina_checksum_i32(const int32_t* x, size_t n, uint32_t* out_dev, ina_stream_t stream) {
     if (!out_dev) return set_error(INA_EINVAL, "null out%s", "");
@@ -2793,7 +2804,7 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (!count) return INA_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
-             ina::store_violations_x16() + ina::store_violations_blk();
+             ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_sr();
     return INA_OK;
 }
 #endif

@@ -9,9 +9,10 @@ outgrow one GPU go through ina_amd.dist (ShardedAggregator: reduce-scatter + all
 over RCCL; RangeAggregator: range-split worker slices, one all-gather).  ina_amd.blk holds
 the block-scaled ops for any gradient dtype (float32, bfloat16, float16); ina_amd.ef the
 quantisers and worker packs with error feedback (a residual carried on the device); ina_amd.wire
-the sharded int16 wire's quantisers and decodes for any gradient dtype.
+the sharded int16 wire's quantisers and decodes for any gradient dtype; ina_amd.sr the quantisers
+with unbiased stochastic rounding (counter-based, stateless, any gradient dtype).
 """
-from . import blk, ef, wire  # noqa: F401
+from . import blk, ef, sr, wire  # noqa: F401
 from ._lib import (ACT_DROP, ACT_FWD_ACK, ACT_FWD_AGG, ACT_FWD_COLLISION, ACT_FWD_OTHER,  # noqa: F401
                    C128_BYTES, C128_VALUES, FLAG_ACK, FLAG_COLLISION, FLAG_OVERFLOW,
                    FLAG_RESEND, InaError, LIB_PATH, MAX_WORKERS, NGA_HDR_BYTES, NUM_REGISTER)

@@ -65,6 +65,10 @@ class SwitchPs(C.Structure):             # include/ina.h ina_switch_ps_t
 INA_SWITCH_ALL, INA_SWITCH_SORT, INA_SWITCH_RUN = 0, 1, 2
 
 
+class SrParams(C.Structure):             # include/ina_sr.h ina_sr_t
+    _fields_ = [("seed", C.c_uint64), ("e0", C.c_uint64), ("step", C.c_uint32), ("sub", C.c_uint32)]
+
+
 # exported symbol -> argtypes (restype int unless listed in _RESTYPE)
 _vp, _sz, _i, _u32, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_double
 SIGNATURES = {
@@ -192,6 +196,17 @@ SIGNATURES_SHARD_EF = {
     "ina_quantize_ef_f32_i16_wire": [_vp, _vp, _vp, _sz, _i, _vp],
     "ina_quantize_ef_blk_f32_i16_wire": [_vp, _vp, _vp, _i, _vp, _sz, _vp],
 }
+# stochastic rounding (include/ina_sr.h): the round-to-nearest siblings' arguments with the ina_sr_t
+# before the stream (the first four: the base after x / xtype, as the error-feedback calls take it)
+SIGNATURES_SR = {
+    "ina_quantize_sr_f32_i32": [_vp, _vp, _vp, _sz, _i, C.POINTER(SrParams), _vp],
+    "ina_quantize_sr_f32_i16_sat": [_vp, _vp, _vp, _sz, _i, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_sr_x16_i32": [_vp, _i, _vp, _vp, _sz, _i, C.POINTER(SrParams), _vp],
+    "ina_quantize_sr_x16_i16_sat": [_vp, _i, _vp, _vp, _sz, _i, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_sr_f32_i16_wire": [_vp, _vp, _sz, _i, C.POINTER(SrParams), _vp],
+    "ina_quantize_sr_x16_i16_wire": [_vp, _i, _vp, _sz, _i, C.POINTER(SrParams), _vp],
+    "ina_scale_for_sr": [C.c_float, _i, _i, C.POINTER(C.c_int)],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -208,7 +223,7 @@ def open_library(path: str) -> C.CDLL:
     lib = C.CDLL(path)
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
-                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16}.items():
+                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -62,6 +62,12 @@ on the i16 wire the gather moves the int16 sums as before and the expand after i
 on one rank or after an all-reduce the whole-bucket decode writes them (wire.finish* with a 16-bit
 y).  Error feedback takes fp32 buckets only: a 16-bit bucket with error_feedback=True is refused at
 the call.
+
+rounding="stochastic" (ShardedAggregator only; include/ina_sr.h, ina_amd.sr): the rank's quantise to the
+wire rounds up with the probability of the fraction it would drop, from Philox4x32-10 under the key
+`seed` at (element index, step, rank).  Nothing is kept between steps but a step counter and no byte
+more moves, so it is there where error feedback is not: 16-bit buckets, and any out_dtype.  Global k
+only, and not together with error feedback.
 """
 from __future__ import annotations
 
@@ -70,7 +76,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib, blk, ef, ops
+from . import _lib, blk, ef, ops, sr
 from . import wire as _wire          # (the aggregators' `wire` argument is the wire's name)
 
 
@@ -258,12 +264,32 @@ class ShardedAggregator:
     A bucket may be float32, bfloat16 or float16 (not with error_feedback=True) and is read as it is;
     out_dtype (float32, bfloat16 or float16) is the dtype of `full`, of the decoded shard and, on the
     i32 wire, of the all-gather -- the module docstring states what equals what.
+    rounding="stochastic" (default "nearest", which leaves every byte of the step as it is): every
+    quantise is ina_amd.sr's with the key `seed`, sub = this rank and step = `step`, a counter that
+    starts at 0, advances by one per call (aggregate_int and phase_quantize included) and may be set,
+    so that a resumed job rounds as the uninterrupted one would; with chunks > 1 each chunk passes its
+    offset in the bucket as e0, so the bytes do not depend on chunks.  Any bucket dtype, any out_dtype,
+    both wires, every collective; everything after the quantise is unchanged.  Global k only, and not
+    with error_feedback=True.  Choose k with sr.scale_for, which leaves a whole quantum of headroom.
     """
 
     def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
                  wire: str = "i32", V: int = 256, collective: str = "rs_ag", chunks: int = 1,
-                 error_feedback: bool = False, out_dtype: torch.dtype = torch.float32):
+                 error_feedback: bool = False, out_dtype: torch.dtype = torch.float32,
+                 rounding: str = "nearest", seed: int = 0):
         self.out_dtype = _out_dtype(out_dtype)
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"rounding must be 'nearest' or 'stochastic', got {rounding!r}")
+        self.stochastic = rounding == "stochastic"
+        if self.stochastic and isinstance(k, str):
+            raise ValueError(f"rounding='stochastic' takes a global integer k, got k={k!r}: per-block scales "
+                             f"(k='block') go with rounding='nearest'")
+        if self.stochastic and error_feedback:
+            raise ValueError("rounding='stochastic' and error_feedback=True exclude each other: stochastic rounding "
+                             "is the stateless alternative to the residual")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
+        self.rounding, self.seed, self._step = rounding, seed, 0
         if wire not in ("i32", "i16"):
             raise ValueError("wire must be 'i32' or 'i16'")
         if collective not in ("rs_ag", "a2a", "allreduce"):
@@ -299,6 +325,9 @@ class ShardedAggregator:
             self.cplan = ShardPlan(self.world * self.sc, self.world, align=self.sc)
             self.cpad = self.chunks * self.cplan.padded
             tot = max(tot, self.cpad)
+            if self.stochastic and self.cplan.padded % 4:
+                raise ValueError(f"rounding='stochastic' with chunks > 1 needs chunks of a multiple of 4 values (a "
+                                 f"chunk's offset is its e0), got {self.cplan.padded}: use an align that is one")
         # one allocation backs both the whole-bucket and the chunked views; pad stays 0
         self._qbuf = torch.zeros(tot, dtype=torch.int32, device=dev)
         self._fbuf = torch.empty(tot, dtype=self.out_dtype, device=dev)
@@ -350,6 +379,22 @@ class ShardedAggregator:
         if self.residual is None:
             raise AttributeError("a residual exists only with error_feedback=True")
         self.residual.zero_()
+
+    @property
+    def step(self) -> int:
+        """rounding="stochastic": the step the next call rounds with (counter word 2 of include/ina_sr.h);
+        it advances by one per call, modulo 2^32."""
+        return self._step
+
+    @step.setter
+    def step(self, value: int):
+        if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 1 << 32:
+            raise ValueError(f"step must be an int in [0, 2^32), got {value!r}")
+        self._step = value
+
+    def _advance(self):
+        if self.stochastic:
+            self._step = (self._step + 1) & 0xFFFFFFFF
 
     @property
     def sum_shard(self) -> torch.Tensor:
@@ -484,11 +529,17 @@ class ShardedAggregator:
                 ef.quantize_i16_wire_blk(x, r, kb, self.V, out=self.q[:n])
         else:
             self._quantize_global(x, r, self.q[:n])
+        self._advance()
 
-    def _quantize_global(self, x: torch.Tensor, r, out: torch.Tensor):
+    def _quantize_global(self, x: torch.Tensor, r, out: torch.Tensor, e0: int = 0):
         """x (the bucket or a chunk of it) to the wire at the global k; r: the same values of the
-        residual, or None without error feedback."""
-        if self.wire == "i32":
+        residual, or None without error feedback; e0: x's offset in the bucket (stochastic rounding)."""
+        if self.stochastic:
+            if self.wire == "i32":
+                sr.quantize(x, self.k, self.seed, step=self._step, sub=self.rank, e0=e0, out=out)
+            else:
+                sr.quantize_i16_wire(x, self.k, self.seed, step=self._step, sub=self.rank, e0=e0, out=out)
+        elif self.wire == "i32":
             if r is None:
                 ops.quantize(x, self.k, out=out)
             else:
@@ -517,9 +568,10 @@ class ShardedAggregator:
             lo, hi = c * L, min((c + 1) * L, n)
             if hi > lo:         # (lo is a multiple of align: the slices stay on the vector path)
                 self._quantize_global(x[lo:hi], None if self.residual is None else self.residual[lo:hi],
-                                      self._qbuf[lo:hi])
+                                      self._qbuf[lo:hi], e0=lo)
             rs.append(reduce_scatter_sum(self._qbuf[c * L:(c + 1) * L], self.cplan, self.group,
                                          out=self.sum_c[c * sc:(c + 1) * sc], async_op=True)[1])
+        self._advance()
         ag = []
         for c in range(self.chunks):           # decode shard c once its RS is done, gather it
             _wait(rs[c])

@@ -295,6 +295,11 @@ int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npkts, i
 #include "ina_blk.h"   /* INA_BLK_GIVEN / INA_BLK_AUTO and the ina_*_blk_* entry points */
 /* The same on the packet path, where the block is the packet: the worker packs and the PS apply. */
 #include "ina_pkt_blk.h"   /* the block-scaled packs and ina_apply_completed_nga_blk */
+/* ---- stochastic rounding --------------------------------------------------------
+ * The global-k quantisers and the sharded int16 wire's with unbiased stochastic rounding from a
+ * counter-based generator (no state, no extra bytes, 16-bit buckets as they are); the contract is
+ * stated in ina_sr.h. */
+#include "ina_sr.h"   /* ina_sr_t, the ina_quantize_sr_* entry points and ina_scale_for_sr */
 
 /* C-128 pack (communicator.cc:23-37): npkts x 524-byte packet_t, all words htonl. */
 int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,

@@ -409,6 +409,76 @@ def run_sr(dev):
     return rows
 
 
+def run_sr_packets(dev):
+    """Stochastic rounding on the packet path (include/ina_pkt_sr.h) at the ResNet-50 size, cold caches,
+    median of 20, the set twice in this process (run 1 / run 2): the 8-worker split pack at V = 256 and
+    32 from fp32 and bf16 buckets, its block-scaled calls (scales given, and AUTO) from fp32, and the
+    single-worker packed call.  Each SR call is timed beside its round-to-nearest sibling, timed twice in
+    the same run (their difference is the spread), and beside the composition it replaces: per worker,
+    sr.quantize into a preallocated int32 buffer, then the plain pack of it.  Nothing is gated."""
+    from ina_amd import ops, sr
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(31)
+    n, k, W, seed = 25_557_032, 9, 8, 0x1234
+    xs32 = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(W)]
+    xs16 = [x.to(torch.bfloat16) for x in xs32]
+    base = torch.randn(n, device=dev, generator=gen) * 1e-3
+    q32 = torch.empty(n, dtype=torch.int32, device=dev)
+    bm = [1 << w for w in range(W)]
+
+    def row(run, name, nbytes, f_sr, f_sib, f_comp):
+        ta, ts, tc, tb = _time(f_sib), _time(f_sr), _time(f_comp), _time(f_sib)
+        lo, hi = min(ta, tb), max(ta, tb)
+        rows.append(_row(f"{name} [sr, run {run}]", ts, nbytes, sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)],
+                         sibling_spread_us=round((hi - lo) * 1e6, 2), composition_us=round(tc * 1e6, 2),
+                         sr_over_sibling=round(ts / lo, 3), sr_over_composition=round(ts / tc, 3),
+                         beats_composition_by_more_than_spread=bool(tc - ts > hi - lo)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            npk = (n + V - 1) // V
+            hs = [torch.zeros((npk, 16), dtype=torch.uint8, device=dev) for _ in range(W)]
+            ps = [torch.empty((npk, 4 * V), dtype=torch.uint8, device=dev) for _ in range(W)]
+            rows_b = W * npk * (16 + 4 * V)
+            kw = dict(base=base, hdrs=hs, pays=ps)
+
+            def comp(xs):
+                # (no SR quantiser takes block scales: for the block calls the global-k one stands in,
+                # the same bytes and the same Philox work)
+                for w in range(W):
+                    sr.quantize(xs[w], k, seed, step=run, sub=w, base=base, out=q32)
+                    ops.pack_nga_split(q32, V, bm[w], W, 1, 1, hdr=hs[w], pay=ps[w])
+
+            for xs, tag in ((xs32, "f32"), (xs16, "bf16")):
+                nb = W * n * xs[0].element_size() + 4 * n + rows_b
+                row(run, f"multi_split W=8 {tag} V={V}", nb,
+                    lambda: sr.quantize_pack_nga_multi_split(xs, k, V, bm, W, 1, 1, seed, step=run, **kw),
+                    lambda: ops.quantize_pack_nga_multi_split(xs, k, V, bm, W, 1, 1, **kw), lambda: comp(xs))
+            kblk = sr.block_scales(xs32, V, base=base)
+            kout = torch.empty_like(kblk)
+            nb = W * n * 4 + 4 * n + rows_b + npk
+            row(run, f"multi_split_blk GIVEN W=8 f32 V={V}", nb,
+                lambda: sr.quantize_pack_nga_multi_split(xs32, kblk, V, bm, W, 1, 1, seed, step=run, **kw),
+                lambda: ops.quantize_pack_nga_multi_split_blk(xs32, V, bm, W, 1, 1, kblk=kblk, **kw),
+                lambda: comp(xs32))
+            row(run, f"multi_split_blk AUTO W=8 f32 V={V}", nb,
+                lambda: sr.quantize_pack_nga_multi_split(xs32, None, V, bm, W, 1, 1, seed, step=run, kblk_out=kout, **kw),
+                lambda: ops.quantize_pack_nga_multi_split_blk(xs32, V, bm, W, 1, 1, kblk_out=kout, **kw),
+                lambda: comp(xs32))
+            stride = ops.nga_stride(V)
+            out = torch.empty((npk, stride), dtype=torch.uint8, device=dev)
+
+            def comp1():
+                sr.quantize(xs32[0], k, seed, step=run, base=base, out=q32)
+                ops.pack_nga(q32, V, 1, W, 1, 1, out=out)
+            row(run, f"packed one worker f32 V={V}", 8 * n + npk * stride,
+                lambda: sr.quantize_pack_nga(xs32[0], k, V, 1, W, 1, 1, seed, step=run, base=base, out=out),
+                lambda: ops.quantize_pack_nga(xs32[0], k, V, 1, W, 1, 1, base=base, out=out), comp1)
+            del hs, ps, out
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1105,6 +1175,7 @@ def run_extra(dev):
     rows += run_ef(dev)
     rows += run_ef_shard(dev)
     rows += run_sr(dev)
+    rows += run_sr_packets(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

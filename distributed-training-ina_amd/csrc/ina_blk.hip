@@ -54,10 +54,10 @@
 namespace ina {
 
 // ina_scale_for's rule for the number of summands
-int scale_lim(int degree, int bits, double& lim) {
+int scale_lim(int degree, int bits, double& lim, double round) {
     if (bits != 16 && bits != 32) return set_error(INA_EINVAL, "bits must be 16 or 32%s", "");
     if (degree < 1) return set_error(INA_EINVAL, "degree must be >= 1%s", "");
-    lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)degree - 0.5;
+    lim = (bits == 32 ? 2147483647.0 : 32767.0) / (double)degree - round;
     if (lim <= 0.0) return set_error(INA_EINVAL, "too many summands (degree) for this width%s", "");
     return INA_OK;
 }
@@ -548,13 +548,13 @@ using fp16_t = h16<INA_X16_F16>;
 #define INA_BLK_X16_CALL(xtype, F, ...) \
     ((xtype) == INA_X16_BF16 ? F<bf16_t>(__VA_ARGS__) : F<fp16_t>(__VA_ARGS__))
 
-// X: float (B = float) or h16<XT> (B = void, include/ina_x16_blk.h)
+// X: float (B = float) or h16<XT> (B = void, include/ina_x16_blk.h); round: scale_lim's
 template <typename X, typename B>
 int block_scales(const B* const* xs, int W, const float* base, size_t n, int V, int degree, int bits, int8_t* kblk,
-                 ina_stream_t stream) {
+                 ina_stream_t stream, double round = 0.5) {
     double lim;
     if (int rc = check_v(V)) return rc;
-    if (int rc = scale_lim(degree, bits, lim)) return rc;
+    if (int rc = scale_lim(degree, bits, lim, round)) return rc;
     if (n == 0) return INA_OK;
     SrcPlain<X> src;
     bool al;
@@ -767,6 +767,12 @@ extern "C" {
 int ina_block_scales_f32(const float* const* xs, int W, const float* base, size_t n, int V, int degree, int bits,
                          int8_t* kblk, ina_stream_t stream) {
     return block_scales<float>(xs, W, base, n, V, degree, bits, kblk, stream);
+}
+
+// the same kernels with ina_scale_for_sr's lim (include/ina_pkt_sr.h)
+int ina_block_scales_sr_f32(const float* const* xs, int W, const float* base, size_t n, int V, int degree, int bits,
+                            int8_t* kblk, ina_stream_t stream) {
+    return block_scales<float>(xs, W, base, n, V, degree, bits, kblk, stream, 1.0);
 }
 
 int ina_quantize_blk_f32_i32(const float* x, const int8_t* kblk, int V, int32_t* q, size_t n, ina_stream_t stream) {

@@ -32,8 +32,9 @@ int default_grid_cap();       // ina_kernels.hip: grid cap of the default-cap ke
 int stream_grid_cap();        // ina_kernels.hip: grid cap of the flat packet kernels (tuning key 4)
 int combine_ina_grid_cap();   // ina_kernels.hip: grid cap of the INA combines, blk one included (tuning key 6)
 // ina_blk.hip: ina_scale_for's rule for `degree` summands at `bits` (16 or 32): lim = (2^(bits-1) - 1) /
-// degree - 1/2, INA_EINVAL when it is not positive
-int scale_lim(int degree, int bits, double& lim);
+// degree - round, INA_EINVAL when it is not positive.  round: what one quantised value can gain by
+// rounding -- 1/2 to nearest, 1 stochastically (ina_scale_for_sr's rule, include/ina_pkt_sr.h)
+int scale_lim(int degree, int bits, double& lim, double round = 0.5);
 // ina_blk.hip: the block-scaled calls' checks of V (>= 1) and of mode / degree / kblk (lim as above
 // under INA_BLK_AUTO, else 1)
 int check_v(int V);

@@ -27,6 +27,7 @@
 #include "ina_internal.h"
 #include "ina_device.h"
 #include "ina_chunk.h"
+#include "ina_sr_device.h"
 
 namespace ina {
 
@@ -788,6 +789,67 @@ struct SrcQ32B {
         return SrcQ32{x, base, scale(e)}.four(e);
     }
 };
+// SrcQ32 / SrcX16 rounded stochastically (include/ina_pkt_sr.h): the word of element e is q32_of of
+// ina_sr.h's y on the delta.  a.i0 is the random-stream counter of the source's chunk 0 and a.sub the
+// worker's stream.  four(e) is one Philox call: e is a multiple of 4 on every vector path and
+// e0 % 4 == 0, so a chunk never straddles two calls.  one(e) is one call with the word picked by
+// selects: the tails, the byte path and the flat kernel's lane-63 neighbour value.
+template <typename LdT>
+struct SrcSr {
+    using Ld = LdT;
+    const typename Ld::X* __restrict__ x;
+    const float* __restrict__ base;   // may be null
+    float s;
+    SrKey a;
+    // off is a multiple of 4 (pack_nga_launch's packet ranges on the vector paths: V % 4 == 0)
+    SrcSr shifted(size_t off) const {
+        SrKey b = a;
+        b.i0 += off >> 2;
+        return SrcSr{x + off, base ? base + off : nullptr, s, b};
+    }
+    __device__ __forceinline__ uint32_t one(size_t e) const {
+        const float v = Ld::widen1(x[e]);
+        return (uint32_t)q32_of(sr_y(base ? __fsub_rn(v, base[e]) : v, s, word_of(a, e)));
+    }
+    __device__ __forceinline__ u32x4 four(size_t e) const {
+        f32x4 d = Ld::widen4(__builtin_nontemporal_load(reinterpret_cast<const typename Ld::Raw*>(x + e)));
+        if (base) {                                    // shared: default policy, as in SrcQ32
+            d = sub4(d, *reinterpret_cast<const f32x4*>(base + e));
+        }
+        return sr_q32x4(d, s, philox(a, a.i0 + (e >> 2)));
+    }
+};
+// SrcQ32B rounded stochastically: the packet's scale, then SrcSr's words
+struct SrcSrB {
+    const float* __restrict__ x;
+    const float* __restrict__ base;   // may be null
+    const int8_t* __restrict__ kblk;
+    uint32_t V;
+    int shift;
+    SrKey a;
+    // off is a whole number of packets and a multiple of 4
+    SrcSrB shifted(size_t off) const {
+        SrKey b = a;
+        b.i0 += off >> 2;
+        return SrcSrB{x + off, base ? base + off : nullptr, kblk + off / V, V, shift, b};
+    }
+    __device__ __forceinline__ float scale(size_t e) const {
+        return pow2f(rd_k(kblk, shift >= 0 ? e >> shift : e / V));
+    }
+    __device__ __forceinline__ uint32_t one(size_t e) const {
+        return SrcSr<LdF32>{x, base, scale(e), a}.one(e);
+    }
+    __device__ __forceinline__ u32x4 four(size_t e) const {
+        return SrcSr<LdF32>{x, base, scale(e), a}.four(e);
+    }
+};
+template <typename Src> constexpr bool kSrSrc = false;
+template <typename Ld> constexpr bool kSrSrc<SrcSr<Ld>> = true;
+// worker g of a group: its stream is the group's first worker's sub + g
+__host__ __device__ __forceinline__ SrKey sr_worker(SrKey a, int g) {
+    a.sub += (uint32_t)g;
+    return a;
+}
 // sources that quantise on the fly (the fused worker packs) against stored int32 words
 template <typename Src> constexpr bool kQuantSrc = !std::is_same_v<Src, SrcI32>;
 
@@ -1157,6 +1219,14 @@ template <typename X>
 struct QPackRows<X, true> : QPackRows<X, false> {
     float* resid[kQpGroup];
 };
+// stochastic rounding (include/ina_pkt_sr.h): the same rows and the call's key, sr.sub the stream of
+// the group's first worker
+template <typename X>
+struct QPackRowsSr : QPackRows<X, false> {
+    SrKey sr;
+};
+template <typename X, bool EF, bool SR>
+using QPackRowsOf = std::conditional_t<SR, QPackRowsSr<X>, QPackRows<X, EF>>;
 // (the error-feedback step of the EF packs on one chunk is ina_chunk.h's: ef_v4, then ef_r4 once the
 // chunk is quantised)
 // the bucket's last chunk under EF, value by value: the words for the payload (0 past n), residuals
@@ -1176,8 +1246,11 @@ __device__ __forceinline__ u32x4 ef_tail4(const float* __restrict__ x, const flo
 }
 // Src: SrcQ32, or SrcX16<XT>; its Ld loads and widens the worker chunks.  EF (fp32 buckets): each
 // worker's residual chunk is one more 16-byte load and one 16-byte write-through store.
+// Src = SrcSr<Ld> (include/ina_pkt_sr.h): the base chunk still shared, one Philox call per worker
+// chunk under that worker's stream a.sr.sub + g; the key and its bumps are wave-uniform (scalar
+// registers), the counter is the chunk's index.
 template <typename Src, int G, bool EF = false>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<typename Src::Ld::X, EF> a, const float* __restrict__ base,
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRowsOf<typename Src::Ld::X, EF, kSrSrc<Src>> a, const float* __restrict__ base,
                                                                   size_t n, float s, uint32_t num_slots,
                                                                   size_t nch, size_t np) {
     using Ld = typename Src::Ld;
@@ -1220,13 +1293,18 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 const f32x4 y = Ld::widen4(x[g]);
-                const u32x4 q = q32x4(base ? sub4(y, b) : y, s);
+                u32x4 q;
+                if constexpr (kSrSrc<Src>) q = sr_q32x4(base ? sub4(y, b) : y, s, philox(sr_worker(a.sr, g), a.sr.i0 + t));
+                else q = q32x4(base ? sub4(y, b) : y, s);
                 packet_store(bswap4(q), a.pay[g] + t);
             }
         } else {                                       // the bucket's last chunk: zero tail
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                packet_store(bswap4(tail4<4>(Src{a.x[g], base, s}, e0, n)), a.pay[g] + t);
+                if constexpr (kSrSrc<Src>)
+                    packet_store(bswap4(tail4<4>(Src{a.x[g], base, s, sr_worker(a.sr, g)}, e0, n)), a.pay[g] + t);
+                else
+                    packet_store(bswap4(tail4<4>(Src{a.x[g], base, s}, e0, n)), a.pay[g] + t);
             }
         }
     }
@@ -1251,8 +1329,11 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split(QPackRows<type
 // (include/ina_x16_blk.h): 8-byte worker loads widened in registers, the held deltas fp32 either way.
 // EF (include/ina_ef.h, fp32 buckets): the held chunks are v = delta + r, so AUTO takes the packet's
 // max over |v|, and each worker's r' goes back in place once its chunk is quantised.
-template <typename Ld, int G, bool AUTO, bool EF = false>
-__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<typename Ld::X, EF> a, const float* __restrict__ base,
+// SR (include/ina_pkt_sr.h, fp32 buckets): the held chunks are rounded stochastically, one Philox call
+// per worker chunk under the stream a.sr.sub + g at the counter of chunk t; lim is ina_scale_for_sr's.
+// The last chunk's values past n are held as 0, which every word rounds to 0.
+template <typename Ld, int G, bool AUTO, bool EF = false, bool SR = false>
+__global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRowsOf<typename Ld::X, EF, SR> a, const float* __restrict__ base,
                                                                       size_t n, int8_t* __restrict__ kblk,
                                                                       double lim, int shift, uint32_t L,
                                                                       uint32_t num_slots, size_t nch, size_t np) {
@@ -1269,7 +1350,9 @@ __global__ __launch_bounds__(kBlock) void k_qpack_nga_multi_split_blk(QPackRows<
         if constexpr (!AUTO) k = rd_k(kblk, shift >= 0 ? t >> shift : t / L);
         // worker g's chunk of deltas, quantised with 2^kk, into its payload row
         auto put = [&](int g, f32x4 y, int kk) {
-            const u32x4 q = q32x4(y, pow2f(kk));
+            u32x4 q;
+            if constexpr (SR) q = sr_q32x4(y, pow2f(kk), philox(sr_worker(a.sr, g), a.sr.i0 + t));
+            else q = q32x4(y, pow2f(kk));
             packet_store(bswap4(q), a.pay[g] + t);
             if constexpr (EF) {
                 const f32x4 r = ef_r4(y, q, pow2f(-kk));
@@ -1893,20 +1976,30 @@ static void with_group(int G, F&& f) {
     else if constexpr (g < kQpGroup) with_group<g + 1>(G, f);
 }
 
-template <typename Src>
-static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina_nga_params_t* prm,
-                           const uint8_t* ovf, uint8_t* pkts, size_t pstride, hipStream_t s,
-                           uint64_t* desc = nullptr, int cap = 0) {
-    // cap > 0 (the block-scaled pack): the vector kernels' grids are held under it as well, so
-    // tuning key 0 reaches their grid-stride loops
+// pack_nga_launch's argument checks.  npk = 0 with INA_OK: an empty bucket, nothing to write.
+static int pack_nga_args(size_t n, const ina_nga_params_t* prm, const uint8_t* pkts, size_t pstride, size_t& npk) {
+    npk = 0;
     if (!prm || prm->V <= 0 || prm->num_slots == 0)
         return set_error(INA_EINVAL, "bad nga params%s", "");
     const int V = prm->V;
     if (pstride < (size_t)INA_NGA_HDR_BYTES + 4u * (size_t)V)
         return set_error(INA_EINVAL, "stride < 15 + 4V%s", "");
-    size_t npk = (n + (size_t)V - 1) / (size_t)V;
+    npk = (n + (size_t)V - 1) / (size_t)V;
     if (npk == 0) return INA_OK;
     if (!pkts) return set_error(INA_EINVAL, "null pointer%s", "");
+    return INA_OK;
+}
+
+template <typename Src>
+static int pack_nga_launch(const Src& src, bool src_aligned, size_t n, const ina_nga_params_t* prm,
+                           const uint8_t* ovf, uint8_t* pkts, size_t pstride, hipStream_t s,
+                           uint64_t* desc = nullptr, int cap = 0) {
+    // cap > 0 (the block-scaled and the stochastic packs): the vector kernels' grids are held under
+    // it as well, so tuning key 0 reaches their grid-stride loops
+    size_t npk;
+    if (int rc = pack_nga_args(n, prm, pkts, pstride, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    const int V = prm->V;
     NgaHdr h{prm->bitmap, prm->seq0, prm->num_slots, nga_fcs(*prm), V};
     if (pstride % 16 == 0 && V % 4 == 0 && src_aligned && aligned16(pkts)) {
         // 32-bit chunk indices: huge buckets go in packet ranges
@@ -1987,10 +2080,13 @@ static int check_resid(float* const* resid, int W) {
     return INA_OK;
 }
 // workers [w0, w0 + G) of a split multi call as one kernel argument (EF: with their residuals)
-template <typename X, bool EF = false, typename XV>
-static QPackRows<X, EF> fill_rows(int w0, int G, const XV* const* x, const ina_nga_params_t* prm, uint8_t* const* hdr,
-                                  uint8_t* const* pay, ina_nga_desc_t* const* desc, float* const* resid = nullptr) {
-    QPackRows<X, EF> a{};
+// (SR: with the call's key, its stream advanced to the group's first worker)
+template <typename X, bool EF = false, bool SR = false, typename XV>
+static QPackRowsOf<X, EF, SR> fill_rows(int w0, int G, const XV* const* x, const ina_nga_params_t* prm,
+                                        uint8_t* const* hdr, uint8_t* const* pay, ina_nga_desc_t* const* desc,
+                                        float* const* resid = nullptr, const SrKey* key = nullptr) {
+    QPackRowsOf<X, EF, SR> a{};
+    if constexpr (SR) a.sr = sr_worker(*key, w0);
     for (int g = 0; g < G; ++g) {
         a.x[g] = static_cast<const X*>(x[w0 + g]);
         a.hdr[g] = reinterpret_cast<u32x4*>(hdr[w0 + g]);
@@ -2002,19 +2098,21 @@ static QPackRows<X, EF> fill_rows(int w0, int G, const XV* const* x, const ina_n
     return a;
 }
 // the fp32 and 16-bit split multi packs: groups of up to kQpGroup workers, a launch each
-// (EF: resid checked by the caller; the grid under the default cap, tuning key 0)
+// (EF: resid checked by the caller; the grid under the default cap, tuning key 0.  Src = SrcSr<Ld>:
+// key is the call's checked *sr, and the grid is under the default cap as well)
 template <typename Src, bool EF = false, typename XV>
 static int qpack_multi_split(const char* what, const XV* const* x, int W, const float* base, size_t n, int k,
                              const ina_nga_params_t* prm, uint8_t* const* hdr, uint8_t* const* pay,
                              ina_nga_desc_t* const* desc, size_t npk, ina_stream_t stream,
-                             float* const* resid = nullptr) {
+                             float* const* resid = nullptr, const SrKey* key = nullptr) {
     using X = typename Src::Ld::X;
+    constexpr bool SR = kSrSrc<Src>;
     const float sc = ldexpf(1.0f, k);
     const size_t nch = npk * (size_t)prm[0].V / 4;
-    const dim3 grid(grid_for(std::max(nch, npk), 1, EF ? 0 : ew_grid_cap())), blk(kBlock);
+    const dim3 grid(grid_for(std::max(nch, npk), 1, EF || SR ? 0 : ew_grid_cap())), blk(kBlock);
     for (int w0 = 0; w0 < W; w0 += kQpGroup) {
         const int G = std::min(kQpGroup, W - w0);
-        const QPackRows<X, EF> a = fill_rows<X, EF>(w0, G, x, prm, hdr, pay, desc, resid);
+        const QPackRowsOf<X, EF, SR> a = fill_rows<X, EF, SR>(w0, G, x, prm, hdr, pay, desc, resid, key);
         with_group(G, [&](auto g) {
             hipLaunchKernelGGL((k_qpack_nga_multi_split<Src, g.value, EF>), grid, blk, 0, hs(stream), a, base, n, sc,
                                prm[0].num_slots, nch, npk);
@@ -2025,23 +2123,29 @@ static int qpack_multi_split(const char* what, const XV* const* x, int W, const 
 
 // the fp32 and 16-bit block-scaled split multi packs (xtype: 0 for fp32 buckets)
 // EF (fp32 buckets): with the workers' residuals; AUTO's two-step route takes its scales over |v|
-template <typename Ld, bool EF = false, typename XV>
+// SR (fp32 buckets, include/ina_pkt_sr.h): sr checked last; AUTO's scales under ina_scale_for_sr's rule
+template <typename Ld, bool EF = false, bool SR = false, typename XV>
 static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype, int W, const float* base, size_t n,
                                  int8_t* kblk, int mode, int degree, const ina_nga_params_t* prm, uint8_t* const* hdr,
                                  uint8_t* const* pay, ina_nga_desc_t* const* desc, ina_stream_t stream,
-                                 float* const* resid = nullptr) {
+                                 float* const* resid = nullptr, const ina_sr_t* sr = nullptr) {
     using X = typename Ld::X;
+    static_assert(!(EF && SR), "stochastic rounding is not combined with error feedback");
     if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
         return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
     double lim = 1.0;
     if (mode == INA_BLK_AUTO) {
-        if (int rc = scale_lim(degree, 32, lim)) return rc;
+        if (int rc = scale_lim(degree, 32, lim, SR ? 1.0 : 0.5)) return rc;
     }
     size_t npk;
     if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, true, kblk, npk)) return rc;
     if (npk == 0) return INA_OK;
     if constexpr (EF) {
         if (int rc = check_resid(resid, W)) return rc;
+    }
+    [[maybe_unused]] SrKey key{};
+    if constexpr (SR) {
+        if (int rc = sr_key(sr, key)) return rc;
     }
     const int V = prm[0].V;
     const uint32_t L = (uint32_t)V / 4;
@@ -2053,6 +2157,7 @@ static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype
     if (autok && !(shift >= 1 && W <= kQpGroup)) {
         int rc;
         if constexpr (EF) rc = ina_block_scales_ef_f32(x, resid, W, base, n, V, degree, 32, kblk, stream);
+        else if constexpr (SR) rc = ina_block_scales_sr_f32(x, W, base, n, V, degree, 32, kblk, stream);
         else if constexpr (std::is_same_v<X, float>) rc = ina_block_scales_f32(x, W, base, n, V, degree, 32, kblk, stream);
         else rc = ina_block_scales_x16(x, xtype, W, base, n, V, degree, 32, kblk, stream);
         if (rc) return rc;
@@ -2064,10 +2169,10 @@ static int qpack_multi_split_blk(const char* what, const XV* const* x, int xtype
     const dim3 grid(grid_for(std::max(nch, npk), 1)), blk(kBlock);
     for (int w0 = 0; w0 < W; w0 += kQpGroup) {
         const int G = std::min(kQpGroup, W - w0);
-        const QPackRows<X, EF> a = fill_rows<X, EF>(w0, G, x, prm, hdr, pay, desc, resid);
+        const QPackRowsOf<X, EF, SR> a = fill_rows<X, EF, SR>(w0, G, x, prm, hdr, pay, desc, resid, &key);
         with_group(G, [&](auto g) {
-            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<Ld, g.value, true, EF>
-                                 : &k_qpack_nga_multi_split_blk<Ld, g.value, false, EF>;
+            auto* kernel = autok ? &k_qpack_nga_multi_split_blk<Ld, g.value, true, EF, SR>
+                                 : &k_qpack_nga_multi_split_blk<Ld, g.value, false, EF, SR>;
             hipLaunchKernelGGL(kernel, grid, blk, 0, hs(stream), a, base, n, kblk, lim, shift, L, prm[0].num_slots,
                                nch, npk);
         });
@@ -2656,6 +2761,104 @@ int ina_quantize_pack_nga_multi_split_ef_blk(const float* const* x, float* const
                                              ina_nga_desc_t* const* desc, ina_stream_t stream) {
     return qpack_multi_split_blk<LdF32, true>("quantize_pack_nga_multi_split_ef_blk", x, 0, W, base, n, kblk, mode,
                                               degree, prm, hdr, pay, desc, stream, resid);
+}
+
+// ---- stochastic rounding on the worker packs (include/ina_pkt_sr.h; the quantisers are in ina_sr.hip) ----
+// each: the sibling's checks in its order, the n == 0 no-op where it has it, then sr; the grids under
+// the default cap (tuning key 0)
+int ina_quantize_pack_nga_sr_desc(const float* x, const float* base, size_t n, int k, const ina_nga_params_t* prm,
+                                  uint8_t* pkts, size_t pstride, ina_nga_desc_t* desc, const ina_sr_t* sr,
+                                  ina_stream_t stream) {
+    if (int rc = check_k(k)) return rc;
+    if (n && !x) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (desc && ((uintptr_t)desc & 7u)) return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
+    size_t npk;
+    if (int rc = pack_nga_args(n, prm, pkts, pstride, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    SrKey key;
+    if (int rc = sr_key(sr, key)) return rc;
+    const bool al = aligned16(x) && (!base || aligned16(base));
+    return pack_nga_launch(SrcSr<LdF32>{x, base, ldexpf(1.0f, k), key}, al, n, prm, nullptr, pkts, pstride, hs(stream),
+                           desc, default_grid_cap());
+}
+
+int ina_quantize_pack_nga_x16_sr_desc(const void* x, int xtype, const float* base, size_t n, int k,
+                                      const ina_nga_params_t* prm, uint8_t* pkts, size_t pstride,
+                                      ina_nga_desc_t* desc, const ina_sr_t* sr, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (int rc = check_k(k)) return rc;
+    if (n && !x) return set_error(INA_EINVAL, "null pointer%s", "");
+    if ((uintptr_t)x & 1u) return set_error(INA_EINVAL, "16-bit buffers must be 2-byte aligned%s", "");
+    if (desc && ((uintptr_t)desc & 7u)) return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
+    size_t npk;
+    if (int rc = pack_nga_args(n, prm, pkts, pstride, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    SrKey key;
+    if (int rc = sr_key(sr, key)) return rc;
+    const bool al = aligned16(x) && (!base || aligned16(base));
+    const uint16_t* h = static_cast<const uint16_t*>(x);
+    const float sc = ldexpf(1.0f, k);
+    if (xtype == INA_X16_BF16)
+        return pack_nga_launch(SrcSr<LdX16<INA_X16_BF16>>{h, base, sc, key}, al, n, prm, nullptr, pkts, pstride,
+                               hs(stream), desc, default_grid_cap());
+    return pack_nga_launch(SrcSr<LdX16<INA_X16_F16>>{h, base, sc, key}, al, n, prm, nullptr, pkts, pstride, hs(stream),
+                           desc, default_grid_cap());
+}
+
+int ina_quantize_pack_nga_blk_sr_desc(const float* x, const float* base, size_t n, const int8_t* kblk,
+                                      const ina_nga_params_t* prm, uint8_t* pkts, size_t pstride,
+                                      ina_nga_desc_t* desc, const ina_sr_t* sr, ina_stream_t stream) {
+    if (n && (!x || !kblk)) return set_error(INA_EINVAL, "null pointer%s", "");
+    if (desc && ((uintptr_t)desc & 7u)) return set_error(INA_EINVAL, "descriptors must be 8-byte aligned%s", "");
+    size_t npk;
+    if (int rc = pack_nga_args(n, prm, pkts, pstride, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    SrKey key;
+    if (int rc = sr_key(sr, key)) return rc;
+    const uint32_t V = (uint32_t)prm->V;
+    const bool al = aligned16(x) && (!base || aligned16(base));
+    return pack_nga_launch(SrcSrB{x, base, kblk, V, log2_exact(V), key}, al, n, prm, nullptr, pkts, pstride, hs(stream),
+                           desc, default_grid_cap());
+}
+
+int ina_quantize_pack_nga_multi_split_sr(const float* const* x, int W, const float* base, size_t n, int k,
+                                         const ina_nga_params_t* prm, uint8_t* const* hdr, uint8_t* const* pay,
+                                         ina_nga_desc_t* const* desc, const ina_sr_t* sr, ina_stream_t stream) {
+    if (int rc = check_k(k)) return rc;
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, false, nullptr, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    SrKey key;
+    if (int rc = sr_key(sr, key)) return rc;
+    return qpack_multi_split<SrcSr<LdF32>>("quantize_pack_nga_multi_split_sr", x, W, base, n, k, prm, hdr, pay, desc,
+                                           npk, stream, nullptr, &key);
+}
+
+int ina_quantize_pack_nga_multi_split_x16_sr(const void* const* x, int xtype, int W, const float* base, size_t n,
+                                             int k, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                             uint8_t* const* pay, ina_nga_desc_t* const* desc, const ina_sr_t* sr,
+                                             ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (int rc = check_k(k)) return rc;
+    size_t npk;
+    if (int rc = check_multi_split(x, W, base, n, prm, hdr, pay, desc, false, nullptr, npk)) return rc;
+    if (npk == 0) return INA_OK;
+    SrKey key;
+    if (int rc = sr_key(sr, key)) return rc;
+    const char* what = "quantize_pack_nga_multi_split_x16_sr";
+    if (xtype == INA_X16_BF16)
+        return qpack_multi_split<SrcSr<LdX16<INA_X16_BF16>>>(what, x, W, base, n, k, prm, hdr, pay, desc, npk, stream,
+                                                             nullptr, &key);
+    return qpack_multi_split<SrcSr<LdX16<INA_X16_F16>>>(what, x, W, base, n, k, prm, hdr, pay, desc, npk, stream, nullptr,
+                                                        &key);
+}
+
+int ina_quantize_pack_nga_multi_split_blk_sr(const float* const* x, int W, const float* base, size_t n, int8_t* kblk,
+                                             int mode, int degree, const ina_nga_params_t* prm, uint8_t* const* hdr,
+                                             uint8_t* const* pay, ina_nga_desc_t* const* desc, const ina_sr_t* sr,
+                                             ina_stream_t stream) {
+    return qpack_multi_split_blk<LdF32, false, true>("quantize_pack_nga_multi_split_blk_sr", x, 0, W, base, n, kblk, mode,
+                                                     degree, prm, hdr, pay, desc, stream, nullptr, sr);
 }
 
 int ina_apply_completed_nga_blk(const uint8_t* rows, const uint8_t* pay, size_t npk, int V, size_t pstride,

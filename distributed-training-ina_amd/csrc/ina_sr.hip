@@ -25,56 +25,15 @@
 #include "ina_internal.h"
 #include "ina_device.h"
 #include "ina_chunk.h"
+#include "ina_sr_device.h"
 
 namespace ina {
 namespace {
 
 constexpr int kBlk = kHostBlock;
 
-// *sr as the kernels take it: the key, counter words 2 and 3, and e0 / 4 (the counter of chunk 0)
-struct SrKey {
-    uint32_t k0, k1, step, sub;
-    uint64_t i0;
-};
-
-// Philox4x32-10 at counter (idx, step, sub)
-__device__ __forceinline__ u32x4 philox(const SrKey& a, uint64_t idx) {
-    uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = a.step, c3 = a.sub;
-    uint32_t k0 = a.k0, k1 = a.k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) {
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-    }
-    return u32x4{c0, c1, c2, c3};
-}
-// the word of element e (its index in the bucket), for the value-by-value paths; picked with
-// selects, so the four words stay in registers
-__device__ __forceinline__ uint32_t word_of(const SrKey& a, size_t e) {
-    const u32x4 w = philox(a, a.i0 + (e >> 2));
-    const uint32_t lo = (e & 1) ? w.y : w.x, hi = (e & 1) ? w.w : w.z;
-    return (e & 2) ? hi : lo;
-}
-
-// y of the contract: explicit roundings, no FMA
-__device__ __forceinline__ float sr_y(float d, float s, uint32_t word) {
-    const float t = __fmul_rn(d, s);
-    const float f = __builtin_floorf(t);
-    const float p = __fsub_rn(t, f);
-    const float u = __fmul_rn((float)(word >> 8), 0x1p-24f);    // exact
-    return __fadd_rn(f, u < p ? 1.0f : 0.0f);
-}
-__device__ __forceinline__ f32x4 sr_y4(f32x4 d, float s, u32x4 w) {
-    return f32x4{sr_y(d.x, s, w.x), sr_y(d.y, s, w.y), sr_y(d.z, s, w.z), sr_y(d.w, s, w.w)};
-}
+// (SrKey, philox, word_of, sr_y, sr_y4 and the host's sr_key are in ina_sr_device.h: the stochastic
+// worker packs of ina_kernels.hip run the same ones)
 
 // a whole chunk of the delta at element e (checked against n by the caller), and one value of it
 template <typename X>
@@ -163,14 +122,6 @@ __global__ __launch_bounds__(kBlk) void k_sr_i16_scalar(const X* __restrict__ x,
 }
 
 inline bool al(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }
-
-// the checks every call ends with, then *sr as the kernels take it
-int sr_key(const ina_sr_t* sr, SrKey& a) {
-    if (!sr) return set_error(INA_EINVAL, "null sr%s", "");
-    if (sr->e0 & 3u) return set_error(INA_EINVAL, "e0 must be a multiple of 4%s", "");
-    a = SrKey{(uint32_t)sr->seed, (uint32_t)(sr->seed >> 32), sr->step, sr->sub, sr->e0 >> 2};
-    return INA_OK;
-}
 
 template <typename X, bool WIRE>
 int launch_i32(const X* x, const float* base, int32_t* q, size_t n, int k, const ina_sr_t* sr, ina_stream_t stream) {

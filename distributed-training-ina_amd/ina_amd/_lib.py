@@ -207,6 +207,21 @@ SIGNATURES_SR = {
     "ina_quantize_sr_x16_i16_wire": [_vp, _i, _vp, _sz, _i, C.POINTER(SrParams), _vp],
     "ina_scale_for_sr": [C.c_float, _i, _i, C.POINTER(C.c_int)],
 }
+# stochastic rounding on the packet path (include/ina_pkt_sr.h): the worker packs' arguments with the
+# ina_sr_t before the stream; the scales call is its sibling's
+SIGNATURES_PKT_SR = {
+    "ina_quantize_pack_nga_sr_desc": [_vp, _vp, _sz, _i, C.POINTER(NgaParams), _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_pack_nga_x16_sr_desc": [_vp, _i, _vp, _sz, _i, C.POINTER(NgaParams), _vp, _sz, _vp,
+                                          C.POINTER(SrParams), _vp],
+    "ina_quantize_pack_nga_blk_sr_desc": [_vp, _vp, _sz, _vp, C.POINTER(NgaParams), _vp, _sz, _vp,
+                                          C.POINTER(SrParams), _vp],
+    "ina_quantize_pack_nga_multi_split_sr": [_vp, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_pack_nga_multi_split_x16_sr": [_vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, C.POINTER(SrParams),
+                                                 _vp],
+    "ina_quantize_pack_nga_multi_split_blk_sr": [_vp, _i, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                                 C.POINTER(SrParams), _vp],
+    "ina_block_scales_sr_f32": [_vp, _i, _vp, _sz, _i, _i, _i, _vp, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -223,7 +238,8 @@ def open_library(path: str) -> C.CDLL:
     lib = C.CDLL(path)
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
-                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR}.items():
+                       **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
+                       **SIGNATURES_PKT_SR}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -23,7 +23,7 @@ import time
 
 import torch
 
-from . import _lib, control, ef, ops, ps
+from . import _lib, control, ef, ops, ps, sr
 from .nic import PacketRing, send_device_packets
 
 
@@ -99,15 +99,32 @@ class SwitchStandIn:
         return self.out[: self.n]
 
 
+def _check_rounding(rounding: str, error_feedback: bool):
+    if rounding not in ("nearest", "stochastic"):
+        raise ValueError(f"unknown rounding {rounding!r}: 'nearest' or 'stochastic'")
+    if rounding == "stochastic" and error_feedback:
+        raise ValueError("stochastic rounding is the stateless alternative to error feedback: "
+                         "rounding='stochastic' is not combined with error_feedback / a residual")
+
+
 def worker_send(sock, params: torch.Tensor, base: torch.Tensor, worker_id: int, W: int, V: int,
                 k, seq0: int, switch_id: int = 1, num_slots: int = _lib.NUM_REGISTER,
-                residual: torch.Tensor | None = None) -> int:
+                residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                step: int = 0, sub: int = 0) -> int:
     """Worker data plane: quantise(params - base) + NGA-V pack in one GPU pass, then
     sendmmsg.  num_slots must be the aggregator's pool size (index = seq mod num_slots,
     DataManager.py:119).  k: the global exponent, or an int8 tensor of one exponent per packet
     (agree_block_scales).  residual: the worker's error-feedback buffer (ef.new_residual), added
     before the quantiser and updated in place (include/ina_ef.h) -- the EF quantiser, then the
-    pack: two launches, in a flow the socket bounds."""
+    pack: two launches, in a flow the socket bounds.  rounding="stochastic": the quantiser rounds up
+    with the probability of the fraction it would drop (include/ina_pkt_sr.h), from the random stream
+    (seed, step, sub), still one launch; not combined with a residual."""
+    _check_rounding(rounding, residual is not None)
+    if rounding == "stochastic":
+        pk = sr.quantize_pack_nga(params.reshape(-1).contiguous(), k, V, bitmap=worker_id, count=W,
+                                  switch_id=switch_id, seq0=seq0, seed=seed, step=step, sub=sub,
+                                  base=base.reshape(-1).contiguous(), num_slots=num_slots)
+        return send_device_packets(sock, pk, _lib.NGA_HDR_BYTES + 4 * V)
     if residual is not None:
         x, b = params.reshape(-1).contiguous(), base.reshape(-1).contiguous()
         if isinstance(k, torch.Tensor):
@@ -197,11 +214,17 @@ def ps_serve(model, W: int, epochs: int, tcp_port: int, data_path: str, k=16,
 
 
 def worker_serve(idx: int, W: int, tcp_port: int, data_path: str, make_model, train_step,
-                 device="cuda", error_feedback: bool = False):
+                 device="cuda", error_feedback: bool = False, rounding: str = "nearest", seed: int = 0):
     """Worker side (worker_loop, launch.py:248-322, with the INA data plane).  error_feedback: the
     worker keeps what its quantiser dropped in one residual buffer across the epochs and adds it to
     the next update (include/ina_ef.h); under k = "block" the scales it offers are those of update +
-    residual."""
+    residual.  rounding="stochastic" (not with error_feedback): the worker's pack rounds stochastically
+    (include/ina_pkt_sr.h) under the key `seed`, with the epoch as the step and idx as the stream, so
+    workers that share a seed round independently; under k = "block" the scales it offers leave the
+    extra quantum (sr.block_scales)."""
+    _check_rounding(rounding, error_feedback)
+    if rounding == "stochastic":
+        sr.check_seed(seed)
     ctl = socket.create_connection(("127.0.0.1", tcp_port))
     data = socket.socket(socket.AF_UNIX, socket.SOCK_DGRAM)
     data.connect(data_path)
@@ -218,11 +241,15 @@ def worker_serve(idx: int, W: int, tcp_port: int, data_path: str, make_model, tr
             p = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
             ke = k
             if k == "block":
-                mine = (ef.block_scales([p], [resid], V, bits=32, degree=W, base=glob) if error_feedback
-                        else ops.block_scales([p], V, bits=32, degree=W, base=glob))
+                if rounding == "stochastic":
+                    mine = sr.block_scales([p], V, bits=32, degree=W, base=glob)
+                else:
+                    mine = (ef.block_scales([p], [resid], V, bits=32, degree=W, base=glob) if error_feedback
+                            else ops.block_scales([p], V, bits=32, degree=W, base=glob))
                 ke = agree_block_scales(ctl, mine)
             worker_send(data, p, glob, idx + 1, W, V, ke, seq_base(epoch, npk),
-                        num_slots=cfg["num_slots"], residual=resid)
+                        num_slots=cfg["num_slots"], residual=resid, rounding=rounding, seed=seed, step=epoch,
+                        sub=idx)
             glob = ps.get_data(ctl).to(device)
             torch.nn.utils.vector_to_parameters(glob, model.parameters())
     finally:

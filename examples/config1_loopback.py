@@ -97,7 +97,8 @@ def _worker(idx, W, port, path, args):
     ARGS = args
     sys.path.insert(0, os.path.join(REPO, "distributed-training-ina_amd"))
     from ina_amd.loopback import worker_serve
-    worker_serve(idx, W, port, path, ResNet50, train_step, error_feedback=args.error_feedback)
+    worker_serve(idx, W, port, path, ResNet50, train_step, error_feedback=args.error_feedback,
+                 rounding=args.rounding, seed=args.seed)
 
 
 def main():
@@ -113,7 +114,13 @@ def main():
                          "agreed by the workers each epoch")
     ap.add_argument("--error-feedback", action="store_true",
                     help="each worker keeps what its quantiser dropped and adds it to its next update")
+    ap.add_argument("--rounding", choices=("nearest", "stochastic"), default="nearest",
+                    help="stochastic: each worker's pack rounds up with the probability of the fraction it "
+                         "would drop (not with --error-feedback)")
+    ap.add_argument("--seed", type=int, default=0, help="the key of the stochastic rounding's random stream")
     ARGS = args = ap.parse_args()
+    if args.rounding == "stochastic" and args.error_feedback:
+        ap.error("--rounding stochastic is not combined with --error-feedback")
     from ina_amd.loopback import ps_serve
     torch.manual_seed(0)
     model = ResNet50().cuda()

@@ -479,6 +479,60 @@ def run_sr_packets(dev):
     return rows
 
 
+def run_sr_reduce(dev):
+    """Stochastic rounding in the fused quantise + reduce calls (include/ina_reduce_sr.h) at the ResNet-50
+    size with W = 8 workers, cold caches, median of 20, the set twice in this process (run 1 / run 2):
+    sr.quantize_reduce at config 2's k and sr.quantize_reduce_i16 at config 4's k and V, from fp32 and
+    bf16 buckets.  Each SR call is timed beside its round-to-nearest sibling, timed twice in the same run
+    (their difference is the spread), and beside the composition it replaces: W x sr.quantize /
+    sr.quantize_i16 into W preallocated temporaries, then ops.sum_reduce / ops.sum_reduce_i16 (the flags
+    of the composition are not OR-ed: that would only add to it).  Nothing is gated here; DESIGN 4.1m
+    reads the rows."""
+    from ina_amd import ops, sr
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(37)
+    n, W, V, seed = 25_557_032, 8, 256, 0x1234
+    xs32 = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(W)]
+    xs16 = [x.to(torch.bfloat16) for x in xs32]
+    o32 = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    ovf = torch.empty((n + V - 1) // V, dtype=torch.uint8, device=dev)
+    t32 = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(W)]    # the composition's scratch
+    t16 = [torch.empty(n, dtype=torch.int16, device=dev) for _ in range(W)]
+    tov = torch.empty_like(ovf)
+
+    def row(run, name, nbytes, f_sr, f_sib, f_comp):
+        ta, ts, tc, tb = _time(f_sib), _time(f_sr), _time(f_comp), _time(f_sib)
+        lo, hi = min(ta, tb), max(ta, tb)
+        rows.append(_row(f"{name} [sr, run {run}]", ts, nbytes, sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)],
+                         sibling_spread_us=round((hi - lo) * 1e6, 2), composition_us=round(tc * 1e6, 2),
+                         sr_over_sibling=round(ts / lo, 3), sr_over_composition=round(ts / tc, 3),
+                         beats_composition_by_more_than_spread=bool(tc - ts > hi - lo)))
+
+    for run in (1, 2):
+        for xs, tag in ((xs32, "f32"), (xs16, "bf16")):
+            b = xs[0].element_size()
+
+            def comp32(k=16):
+                for w in range(W):
+                    sr.quantize(xs[w], k, seed, step=run, sub=w, out=t32[w])
+                ops.sum_reduce(t32, out=o32)
+
+            def comp16(k=13):
+                for w in range(W):
+                    sr.quantize_i16(xs[w], k, V, seed, step=run, sub=w, out=t16[w], overflow=tov)
+                ops.sum_reduce_i16(t16, V, out=o16, overflow=ovf)
+
+            row(run, f"quantize_reduce W={W} {tag}->i32 (C2 size, k=16)", (W * b + 4) * n,
+                lambda: sr.quantize_reduce(xs, 16, seed, step=run, out=o32),
+                lambda: ops.quantize_reduce(xs, 16, out=o32), comp32)
+            row(run, f"quantize_reduce_i16 W={W} {tag}->i16 V={V} (C4 size, k=13)", (W * b + 2) * n + ovf.numel(),
+                lambda: sr.quantize_reduce_i16(xs, 13, V, seed, step=run, out=o16, overflow=ovf),
+                lambda: ops.quantize_reduce_i16(xs, 13, V, out=o16, overflow=ovf), comp16)
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1176,6 +1230,7 @@ def run_extra(dev):
     rows += run_ef_shard(dev)
     rows += run_sr(dev)
     rows += run_sr_packets(dev)
+    rows += run_sr_reduce(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

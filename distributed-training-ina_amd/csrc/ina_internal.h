@@ -76,6 +76,7 @@ unsigned long long store_violations_switch();    // ina_switch.hip
 unsigned long long store_violations_x16();       // ina_x16.hip
 unsigned long long store_violations_blk();       // ina_blk.hip
 unsigned long long store_violations_sr();        // ina_sr.hip
+unsigned long long store_violations_reduce_sr(); // ina_reduce_sr.hip
 // ina_kernels.hip: ina_scale_for with `round` for its 1/2 -- the largest k in [-126, 127] with
 // W * (absmax * 2^k + round) <= 2^(bits-1) - 1; ina_scale_for's refusals
 int scale_for_round(float absmax, int W, int bits, double round, int* k_out);

@@ -3007,7 +3007,8 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (!count) return INA_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
-             ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_sr();
+             ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_sr() +
+             ina::store_violations_reduce_sr();
     return INA_OK;
 }
 #endif

@@ -67,7 +67,9 @@ rounding="stochastic" (ShardedAggregator only; include/ina_sr.h, ina_amd.sr): th
 wire rounds up with the probability of the fraction it would drop, from Philox4x32-10 under the key
 `seed` at (element index, step, rank).  Nothing is kept between steps but a step counter and no byte
 more moves, so it is there where error feedback is not: 16-bit buckets, and any out_dtype.  Global k
-only, and not together with error feedback.
+only, and not together with error feedback.  Layout B has it as a class of its own,
+StochasticRangeAggregator (include/ina_reduce_sr.h): the fused quantise + reduce rounds worker w's slice
+on stream w, so its integer aggregate is the sharded step's, bit for bit.
 """
 from __future__ import annotations
 
@@ -783,3 +785,60 @@ class RangeAggregator:
         scales in `k_shard`."""
         m = self._reduce(slices)
         return self.sum_shard[:m]
+
+
+class StochasticRangeAggregator(RangeAggregator):
+    """RangeAggregator with every summand rounded stochastically (include/ina_reduce_sr.h, ina_amd.sr): layout
+    B's answer to ShardedAggregator(rounding="stochastic").  The reduce is sr.quantize_reduce /
+    sr.quantize_reduce_i16 with the key `seed`, sub = 0 -- worker w of the slices draws from stream w --
+    e0 = this rank's `lo` and step = `step`, a counter that starts at 0, advances by one per __call__ /
+    aggregate_int / phase_reduce_decode (modulo 2^32) and may be set, so that a resumed job rounds as the
+    uninterrupted one would.  With worker w's slices coming from the rank-w bucket of a sharded step, this
+    rank's integer aggregate is bit for bit that range of ShardedAggregator(rounding="stochastic", seed)'s
+    at the same step, on both wires: the two layouts of config 5 agree.  Everything after the reduce --
+    decode, gather, gather_bytes -- is RangeAggregator's.  Global k only (choose it with sr.scale_for), and
+    `lo` must be a multiple of 4: a plan whose align is one gives that.  A class of its own, since
+    RangeAggregator's arguments are fixed."""
+
+    def __init__(self, n: int, k: int = 16, group=None, device=None, align: int = 1024,
+                 wire: str = "i32", V: int = 256, out_dtype: torch.dtype = torch.float32, seed: int = 0):
+        if isinstance(k, str) or k is None or isinstance(k, torch.Tensor):
+            raise ValueError(f"StochasticRangeAggregator takes a global integer k, got k={k!r}: per-block scales "
+                             f"(k='block') go with RangeAggregator, which rounds to nearest")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
+        super().__init__(n, k=k, group=group, device=device, align=align, wire=wire, V=V, out_dtype=out_dtype)
+        if self.hi > self.lo and self.lo % 4:
+            raise ValueError(f"this rank's range starts at {self.lo}, not a multiple of 4 (it is the e0 of the "
+                             f"rounding): use an align that is a multiple of 4")
+        self.rounding, self.seed, self._step = "stochastic", seed, 0
+
+    @property
+    def step(self) -> int:
+        """The step the next call rounds with (counter word 2 of include/ina_sr.h); it advances by one per
+        call, modulo 2^32."""
+        return self._step
+
+    @step.setter
+    def step(self, value: int):
+        if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 1 << 32:
+            raise ValueError(f"step must be an int in [0, 2^32), got {value!r}")
+        self._step = value
+
+    def _reduce(self, slices) -> int:
+        # (the slice normalisation and the length check are RangeAggregator._reduce's, repeated here
+        # because that class stays as it is; a change to either belongs in both)
+        m = self.hi - self.lo
+        if isinstance(slices, torch.Tensor):
+            slices = list(slices.unbind(0)) if slices.dim() > 1 else [slices]
+        slices = [t.reshape(-1) for t in slices]
+        if not slices or any(t.numel() != m for t in slices):
+            raise ValueError(f"every worker slice must hold this rank's {m} values")
+        if m:                         # more ranks than ranges: nothing here, zeros gathered
+            if self.wire == "i32":
+                sr.quantize_reduce(slices, self.k, self.seed, step=self._step, e0=self.lo, out=self.sum_shard[:m])
+            else:
+                sr.quantize_reduce_i16(slices, self.k, self.V, self.seed, step=self._step, e0=self.lo,
+                                       out=self.sum_shard[:m], overflow=self.ovf_shard[: -(-m // self.V)])
+        self._step = (self._step + 1) & 0xFFFFFFFF
+        return m

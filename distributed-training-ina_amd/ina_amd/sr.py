@@ -27,6 +27,14 @@ On the packet path (include/ina_pkt_sr.h) the worker packs round the same way in
 the rows of ops.pack_nga / ops.pack_nga_split on sr.quantize's words, worker w of a multi-worker call
 drawing from stream sub + w.  With per-packet scales (k an int8 tensor, or None to compute them) the
 buckets are float32, and sr.block_scales gives the scales with sr.scale_for's extra quantum.
+
+On the GPU that sums W workers' buckets (include/ina_reduce_sr.h) the fused quantise + reduce rounds every
+summand the same way in its one launch, worker w on stream sub + w:
+
+    s = sr.quantize_reduce(grads, k, seed, step=t)                       # ops.sum_reduce of W sr.quantize
+    s16, ovf = sr.quantize_reduce_i16(slices, k, V, seed, step=t, e0=lo)  # that range of the bucket's result
+
+Global k only.  dist.StochasticRangeAggregator is layout B of config 5 on these two calls.
 """
 from __future__ import annotations
 
@@ -122,6 +130,69 @@ def quantize_i16_wire(x: torch.Tensor, k: int, seed: int, step: int = 0, sub: in
         rc = load().ina_quantize_sr_f32_i16_wire(x.data_ptr(), out.data_ptr(), x.numel(), k, C.byref(prm), _stream(x))
     check(rc, "sr.quantize_i16_wire")
     return out
+
+
+# ---- the fused quantise + reduce calls (include/ina_reduce_sr.h) ---------------------------------
+def _global_k(k, what: str) -> int:
+    """The fused reduces round stochastically under one global k: scales per block are refused by name."""
+    if k is None or isinstance(k, (str, torch.Tensor)):
+        raise ValueError(f"{what} takes a global integer k, got {'an int8 tensor' if isinstance(k, torch.Tensor) else repr(k)}: "
+                         f"block scales are not combined with stochastic rounding on the fused reduces "
+                         f"(blk.quantize_reduce rounds to nearest)")
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise TypeError(f"k must be an int, got {type(k).__name__}")
+    return int(k)
+
+
+def quantize_reduce(bufs, k: int, seed: int, step: int = 0, sub: int = 0, e0: int = 0,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """ops.quantize_reduce with every summand rounded stochastically, one launch: the int32 sum (mod 2^32)
+    over w of sr.quantize(bufs[w], k, seed, step, sub + w, e0) -- worker w draws from stream sub + w.  The
+    buckets are float32, bfloat16 or float16, one dtype per call."""
+    k = _global_k(k, "sr.quantize_reduce")
+    bufs, n, xt = ops._grad_bufs(bufs)
+    prm = _params(seed, step, sub, e0)
+    out = torch.empty(n, dtype=torch.int32, device=bufs[0].device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int32, "out")
+    _same_device(bufs[0], out)
+    if xt:
+        rc = load().ina_quantize_reduce_sr_x16_i32(_ptrs(bufs), xt, len(bufs), out.data_ptr(), n, k, C.byref(prm),
+                                                   _stream(out))
+    else:
+        rc = load().ina_quantize_reduce_sr_f32_i32(_ptrs(bufs), len(bufs), out.data_ptr(), n, k, C.byref(prm),
+                                                   _stream(out))
+    check(rc, "sr.quantize_reduce")
+    return out
+
+
+def quantize_reduce_i16(bufs, k: int, V: int, seed: int, step: int = 0, sub: int = 0, e0: int = 0, out=None,
+                        overflow=None):
+    """ops.quantize_reduce_i16 with every summand rounded stochastically, one launch: (out int16, overflow) --
+    each summand saturated at int16, the sum saturated once, one flag per slot of V values (1 where a
+    summand or the sum saturated or a value was NaN).  With e0 != 0 the caller keeps e0 a multiple of V."""
+    k = _global_k(k, "sr.quantize_reduce_i16")
+    bufs, n, xt = ops._grad_bufs(bufs)
+    prm = _params(seed, step, sub, e0)
+    if isinstance(V, bool) or not isinstance(V, numbers.Integral) or V <= 0:
+        raise ValueError("V must be > 0")
+    dev = bufs[0].device
+    out = torch.empty(n, dtype=torch.int16, device=dev) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int16, "out")
+    nslot = (n + V - 1) // V
+    overflow = torch.empty(nslot, dtype=torch.uint8, device=dev) if overflow is None else overflow
+    _fits(overflow, nslot, "overflow")
+    _req(overflow, torch.uint8, "overflow")
+    _same_device(bufs[0], out, overflow)
+    if xt:
+        rc = load().ina_quantize_reduce_sr_x16_i16_sat(_ptrs(bufs), xt, len(bufs), out.data_ptr(), n, k, V,
+                                                       overflow.data_ptr(), C.byref(prm), _stream(out))
+    else:
+        rc = load().ina_quantize_reduce_sr_f32_i16_sat(_ptrs(bufs), len(bufs), out.data_ptr(), n, k, V,
+                                                       overflow.data_ptr(), C.byref(prm), _stream(out))
+    check(rc, "sr.quantize_reduce_i16")
+    return out, overflow
 
 
 def scale_for(amax: float, W: int, bits: int) -> int:

@@ -36,8 +36,9 @@
  * and W <= 8 runs ina_block_scales_sr_f32 first and then the GIVEN kernels, as the sibling does:
  * identical scales and rows.  *sr is copied into the kernel arguments during the call.
  *
- * Not here: 16-bit buckets with block scales, stochastic rounding combined with error feedback, the
- * packed-row multi-worker pack (ina_quantize_pack_nga_multi) and the fused quantise + reduce calls.
+ * Not here: 16-bit buckets with block scales, stochastic rounding combined with error feedback and the
+ * packed-row multi-worker pack (ina_quantize_pack_nga_multi).  The fused quantise + reduce calls are in
+ * ina_reduce_sr.h.
  */
 #ifndef INA_PKT_SR_H
 #define INA_PKT_SR_H

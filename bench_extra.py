@@ -533,6 +533,68 @@ def run_sr_reduce(dev):
     return rows
 
 
+def run_blk_sr(dev):
+    """Stochastic rounding with per-block scales (include/ina_blk_sr.h) at the ResNet-50 size, cold caches,
+    median of 20, the set twice in this process (run 1 / run 2): blk_sr.quantize_reduce at W = 8 and
+    blk_sr.quantize_reduce_i16 at W = 4 and W = 16, V = 256 and 32, from fp32 and bf16 buckets, scales given
+    and computed (AUTO).  Each call is timed beside its round-to-nearest block sibling, timed twice in the
+    same run (their difference is the spread), its global-k stochastic sibling, and the composition it
+    replaces: blk_sr.block_scales where AUTO, then W x blk_sr.quantize into W preallocated int32
+    temporaries, then ops.sum_reduce.  Nothing is gated here; DESIGN 4.1n reads the rows."""
+    from ina_amd import blk, blk_sr, ops, sr
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(41)
+    n, seed = 25_557_032, 0x1234
+    xs32 = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(16)]
+    xs16 = [x.to(torch.bfloat16) for x in xs32]
+    o32 = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    t32 = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(16)]   # the composition's scratch
+
+    def row(run, name, nbytes, f_sr, f_sib, f_glob, f_comp):
+        ta, ts, tg, tc, tb = _time(f_sib), _time(f_sr), _time(f_glob), _time(f_comp), _time(f_sib)
+        lo, hi = min(ta, tb), max(ta, tb)
+        rows.append(_row(f"{name} [blk sr, run {run}]", ts, nbytes,
+                         sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], sibling_spread_us=round((hi - lo) * 1e6, 2),
+                         global_k_sr_us=round(tg * 1e6, 2), composition_us=round(tc * 1e6, 2),
+                         sr_over_sibling=round(ts / lo, 3), sr_over_global_k_sr=round(ts / tg, 3),
+                         sr_over_composition=round(ts / tc, 3),
+                         beats_composition_by_more_than_spread=bool(tc - ts > hi - lo)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = (n + V - 1) // V
+            ovf = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kout = torch.empty(nblk, dtype=torch.int8, device=dev)
+            for bits, W in ((32, 8), (16, 4), (16, 16)):
+                k = sr.scale_for(0.06, W, bits)                     # the buckets' range: 6 sigma
+                for src, tag in ((xs32, "f32"), (xs16, "bf16")):
+                    xs, b = src[:W], src[0].element_size()
+                    kb = blk_sr.block_scales(xs, V, bits=bits, degree=W)
+                    for auto in (False, True):
+                        kw = dict(kblk=None if auto else kb, kblk_out=kout)
+
+                        def comp():
+                            kk = blk_sr.block_scales(xs, V, bits=bits, degree=W, out=kout) if auto else kb
+                            for w in range(W):
+                                blk_sr.quantize(xs[w], kk, V, seed, step=run, sub=w, out=t32[w])
+                            ops.sum_reduce(t32[:W], out=o32)
+
+                        mode = "AUTO" if auto else "GIVEN"
+                        if bits == 32:
+                            row(run, f"quantize_reduce_blk W={W} {tag}->i32 V={V} {mode}", (W * b + 4) * n + nblk,
+                                lambda: blk_sr.quantize_reduce(xs, V, seed, step=run, out=o32, **kw),
+                                lambda: blk.quantize_reduce(xs, V, out=o32, **kw),
+                                lambda: sr.quantize_reduce(xs, k, seed, step=run, out=o32), comp)
+                        else:
+                            row(run, f"quantize_reduce_i16_blk W={W} {tag}->i16 V={V} {mode}", (W * b + 2) * n + 2 * nblk,
+                                lambda: blk_sr.quantize_reduce_i16(xs, V, seed, step=run, out=o16, overflow=ovf, **kw),
+                                lambda: blk.quantize_reduce_i16(xs, V, out=o16, overflow=ovf, **kw),
+                                lambda: sr.quantize_reduce_i16(xs, k, V, seed, step=run, out=o16, overflow=ovf), comp)
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1231,6 +1293,7 @@ def run_extra(dev):
     rows += run_sr(dev)
     rows += run_sr_packets(dev)
     rows += run_sr_reduce(dev)
+    rows += run_blk_sr(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

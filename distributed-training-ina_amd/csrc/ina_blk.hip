@@ -41,6 +41,13 @@
 // once v is quantised, and a third scale mode, the call's one k.  No kernel of its own.  The EF
 // quantisers of the sharded int16 wire (include/ina_shard_ef.h) are the int32 instances with the
 // SrcEfWire source: the wire word q16 + (sat << 22) where those run q32, q16 into the carry.
+//
+// Stochastic rounding (include/ina_blk_sr.h): the same kernels with the SrcSr value source, which reads
+// what the plain source reads and carries the call's Philox key.  Where the source says kSr, a chunk is
+// rounded by sr_y4 (ina_sr_device.h) with the words of one Philox call at the chunk's counter, worker w
+// on stream sub + w, in place of rintf; the clamps, the sums, the scales, the flags and every load and
+// store are the round-to-nearest instances'.  No kernel of its own; the sharded int16 wire's stochastic
+// block quantiser is the int32 instance at W = 1 with the wire word, as the error-feedback one is.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -50,6 +57,7 @@
 #include "ina_internal.h"
 #include "ina_device.h"
 #include "ina_chunk.h"
+#include "ina_sr_device.h"
 
 namespace ina {
 
@@ -78,6 +86,7 @@ template <typename X>
 struct SrcPlain {
     static constexpr bool kEf = false;
     static constexpr bool kWire = false;
+    static constexpr bool kSr = false;
     using Elem = X;
     PtrPack<X> in;
     __device__ __forceinline__ f32x4 four(int w, size_t e, size_t n) const { return ld4(in.p[w], e, n); }
@@ -94,6 +103,7 @@ template <typename X, int N>
 struct SrcEf {
     static constexpr bool kEf = true;
     static constexpr bool kWire = false;
+    static constexpr bool kSr = false;
     using Elem = X;
     const X* x[N];
     float* resid[N];
@@ -119,6 +129,18 @@ struct SrcEf {
 // carry is handed the word's q16, never the word with its count bits.
 struct SrcEfWire : SrcEf<float, 1> {
     static constexpr bool kWire = true;
+};
+// Stochastic rounding (include/ina_blk_sr.h): the plain source's values, and the random words that round
+// them -- Philox4x32-10 under the call's key at the counter of the chunk at element e (i0 + e / 4),
+// worker w on stream sub + w.  The block's scale has no part in them.  WIRE: the int32 kernels write
+// the sharded int16 wire's word.
+template <typename X, bool WIRE = false>
+struct SrcSr : SrcPlain<X> {
+    static constexpr bool kWire = WIRE;
+    static constexpr bool kSr = true;
+    SrKey key;
+    __device__ __forceinline__ u32x4 words(int w, size_t e) const { return philox(stream_of(key, w), key.i0 + (e >> 2)); }
+    __device__ __forceinline__ uint32_t word(int w, size_t j) const { return word_of(stream_of(key, w), j); }
 };
 
 // ---------------------------------------------------------------------------
@@ -205,7 +227,11 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i32(Src in, int Wd, int kg, int
         u32x4 acc = {0u, 0u, 0u, 0u};
         // worker w's chunk: quantised, summed, and handed back to the source
         auto add = [&](int w, f32x4 x) {
-            if constexpr (Src::kWire) {
+            if constexpr (Src::kSr) {
+                const u32x4 r = in.words(w, e);
+                if constexpr (Src::kWire) acc += sr_q16wx4(x, s, r);
+                else acc += sr_q32x4(x, s, r);
+            } else if constexpr (Src::kWire) {
                 const u32x4 word = q16wx4(x, s);
                 acc += word;
                 in.carry(w, x, wire_q16x4(word), inv, e, n);
@@ -363,17 +389,22 @@ __global__ __launch_bounds__(kBlk) void k_qr_blk_i16(Src in, int Wd, int kg, int
         [[maybe_unused]] const float invA = pow2f(-kA), invB = pow2f(-kB);   // the EF carry's
         bool sa = false, sb = false;
         int32_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+        // worker w's chunk at element e: quantised and added to the half's sums
+        auto add = [&](int w, f32x4 x, size_t e, float s, int32_t* acc, bool& sat) {
+            if constexpr (Src::kSr) q16x4_add_sr(x, s, in.words(w, e), acc, sat);
+            else q16x4_add(x, s, acc, sat);
+        };
         if constexpr (HOLD) {
 #pragma unroll
             for (int w = 0; w < W; ++w) {
-                q16x4_add(u[w], sA, a, sa);
-                q16x4_add(v[w], sB, b, sb);
+                add(w, u[w], eA, sA, a, sa);
+                add(w, v[w], eB, sB, b, sb);
             }
         } else {
 #pragma unroll UNR
             for (int w = 0; w < nw; ++w) {
-                q16x4_add(in.four(w, eA, n), sA, a, sa);
-                q16x4_add(in.four(w, eB, n), sB, b, sb);
+                add(w, in.four(w, eA, n), eA, sA, a, sa);
+                add(w, in.four(w, eB, n), eB, sB, b, sb);
             }
         }
         if constexpr (!Src::kEf) {
@@ -456,7 +487,10 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<Src> a) {
                 uint32_t acc = 0u;
                 for (int w = 0; w < a.W; ++w) {
                     const float x = a.in.one(w, j);
-                    if constexpr (Src::kWire) {
+                    if constexpr (Src::kSr) {
+                        const float y = sr_y(x, sc, a.in.word(w, j));
+                        acc += (uint32_t)(Src::kWire ? q16w_of(y) : q32_of(y));
+                    } else if constexpr (Src::kWire) {
                         const int32_t word = q16w(x, sc);
                         acc += (uint32_t)word;
                         a.in.carry1(w, x, wire_q16(word), inv, j);
@@ -471,7 +505,9 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<Src> a) {
                 int32_t acc = 0;
                 for (int w = 0; w < a.W; ++w) {
                     const float x = a.in.one(w, j);
-                    const int32_t q = q16(x, sc, sat);
+                    int32_t q;
+                    if constexpr (Src::kSr) q = q16_of(sr_y(x, sc, a.in.word(w, j)), sat);
+                    else q = q16(x, sc, sat);
                     acc += q;
                     a.in.carry1(w, x, q, inv, j);
                 }
@@ -505,12 +541,12 @@ __global__ __launch_bounds__(kBlk) void k_blk_scalar(ScalarArgs<Src> a) {
 // there for ina_ef.hip)
 }  // namespace
 int check_v(int V) { return V < 1 ? set_error(INA_EINVAL, "V must be >= 1%s", "") : INA_OK; }
-int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim) {
+int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim, double round) {
     lim = 1.0;
     if (mode != INA_BLK_GIVEN && mode != INA_BLK_AUTO)
         return set_error(INA_EINVAL, "mode must be INA_BLK_GIVEN (0) or INA_BLK_AUTO (1)%s", "");
     if (mode == INA_BLK_AUTO) {
-        if (int rc = scale_lim(degree, bits, lim)) return rc;
+        if (int rc = scale_lim(degree, bits, lim, round)) return rc;
     }
     if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
     return INA_OK;
@@ -572,64 +608,76 @@ int block_scales(const B* const* xs, int W, const float* base, size_t n, int V, 
     return launched();
 }
 
-template <typename X, typename B>
+// SR (include/ina_blk_sr.h): every summand rounded stochastically under *sr, the scales under
+// ina_scale_for_sr's rule, the stochastic checks after the sibling's, every grid under the default cap
+template <typename X, bool SR = false, typename B>
 int reduce_i32(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int32_t* out, size_t n,
-               ina_stream_t stream) {
+               ina_stream_t stream, const ina_sr_t* sr = nullptr) {
+    using Src = std::conditional_t<SR, SrcSr<X>, SrcPlain<X>>;
     double lim;
     if (int rc = check_v(V)) return rc;
-    if (int rc = check_mode(mode, kblk, degree, 32, lim)) return rc;
+    if (int rc = check_mode(mode, kblk, degree, 32, lim, SR ? 1.0 : 0.5)) return rc;
     if (n == 0) return INA_OK;
-    SrcPlain<X> src;
+    Src src;
     bool al;
     if (int rc = fill_pack(src.in, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
+    if constexpr (SR) {
+        if (int rc = sr_key(sr, src.key)) return rc;
+    }
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
     if (vec_v(V, shift) && src_aligned(src.in, W) && aligned16(out)) {
         // the sibling's grids: covering for W <= 8, the streaming cap beyond
-        const dim3 g(grid_of((n + 3) / 4, W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
+        const dim3 g(grid_of((n + 3) / 4, SR ? default_grid_cap() : W <= 8 ? ew_grid_cap() : stream_grid_cap())), b(kBlk);
 #define L(WW)                                                                                                 \
     do {                                                                                                      \
-        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<SrcPlain<X>, WW, K_AUTO>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift); \
-        else hipLaunchKernelGGL((k_qr_blk_i32<SrcPlain<X>, WW, K_GIVEN>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift); \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i32<Src, WW, K_AUTO>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift); \
+        else hipLaunchKernelGGL((k_qr_blk_i32<Src, WW, K_GIVEN>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift); \
     } while (0)
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs<SrcPlain<X>> a{src, W, 0, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
+        ScalarArgs<Src> a{src, W, 0, nullptr, nullptr, kblk, lim, out, n, (size_t)V, nullptr, 0.f};
         if (autok) launch_scalar<S_Q32, K_AUTO>(a, s);
         else launch_scalar<S_Q32, K_GIVEN>(a, s);
     }
     return launched();
 }
 
-template <typename X, typename B>
+template <typename X, bool SR = false, typename B>
 int reduce_i16(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, int V, int16_t* out, size_t n,
-               uint8_t* ovf, ina_stream_t stream) {
+               uint8_t* ovf, ina_stream_t stream, const ina_sr_t* sr = nullptr) {
+    using Src = std::conditional_t<SR, SrcSr<X>, SrcPlain<X>>;
     double lim;
     if (int rc = check_v(V)) return rc;
-    if (int rc = check_mode(mode, kblk, degree, 16, lim)) return rc;
+    if (int rc = check_mode(mode, kblk, degree, 16, lim, SR ? 1.0 : 0.5)) return rc;
     if (n == 0) return INA_OK;
-    SrcPlain<X> src;
+    Src src;
     bool al;
     if (int rc = fill_pack(src.in, bufs, W, al)) return rc;
     if (!out) return set_error(INA_EINVAL, "null out%s", "");
+    if constexpr (SR) {
+        if (int rc = sr_key(sr, src.key)) return rc;
+    }
     hipStream_t s = hs(stream);
     const bool autok = mode == INA_BLK_AUTO;
     int shift;
     // (out is stored 8 bytes a lane; beside fp32 buckets it keeps the 16-byte rule it always had)
+    // W = 16: AUTO takes the re-read instance, for its registers; under stochastic rounding so do the
+    // given scales, whose unrolled W = 16 instance with its 32 Philox calls came out at one wave a SIMD
     if (vec_v(V, shift) && src_aligned(src.in, W) && (uintptr_t)out % (4 * sizeof(X)) == 0) {
         const dim3 g(grid_of((n + 511) / 512 * 64, default_grid_cap())), b(kBlk);
 #define L(WW)                                                                                                          \
     do {                                                                                                               \
-        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<SrcPlain<X>, (WW <= 8 ? WW : 0), K_AUTO>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift, V, ovf); \
-        else hipLaunchKernelGGL((k_qr_blk_i16<SrcPlain<X>, WW, K_GIVEN>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift, V, ovf); \
+        if (autok) hipLaunchKernelGGL((k_qr_blk_i16<Src, (WW <= 8 ? WW : 0), K_AUTO>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift, V, ovf); \
+        else hipLaunchKernelGGL((k_qr_blk_i16<Src, ((SR && WW > 8) ? 0 : WW), K_GIVEN>), g, b, 0, s, src, W, 0, kblk, lim, out, n, shift, V, ovf); \
     } while (0)
         INA_BLK_W_SWITCH(W, L)
 #undef L
     } else {
-        ScalarArgs<SrcPlain<X>> a{src, W, 0, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
+        ScalarArgs<Src> a{src, W, 0, nullptr, nullptr, kblk, lim, out, n, (size_t)V, ovf, 0.f};
         if (autok) launch_scalar<S_Q16, K_AUTO>(a, s);
         else launch_scalar<S_Q16, K_GIVEN>(a, s);
     }
@@ -637,13 +685,41 @@ int reduce_i16(const B* const* bufs, int W, int8_t* kblk, int mode, int degree, 
 }
 
 // one bucket with given scales: the reduce of one
-template <typename X, typename B>
-int quantize_i32(const B* x, const int8_t* kblk, int V, int32_t* q, size_t n, ina_stream_t stream) {
+template <typename X, bool SR = false, typename B>
+int quantize_i32(const B* x, const int8_t* kblk, int V, int32_t* q, size_t n, ina_stream_t stream,
+                 const ina_sr_t* sr = nullptr) {
     if (int rc = check_v(V)) return rc;
     if (n == 0) return INA_OK;
     if (!x || !q || !kblk) return set_error(INA_EINVAL, "null pointer%s", "");
     const B* one[1] = {x};
-    return reduce_i32<X>(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, stream);
+    return reduce_i32<X, SR>(one, 1, const_cast<int8_t*>(kblk), INA_BLK_GIVEN, 1, V, q, n, stream, sr);
+}
+// the sharded int16 wire's words of one bucket, rounded stochastically (include/ina_blk_sr.h): the
+// round-to-nearest sibling's checks (ina_shard.hip), then the stochastic ones
+template <typename X, typename B>
+int quantize_wire_sr(const B* x, const int8_t* kblk, int V, int32_t* wire, size_t n, const ina_sr_t* sr,
+                     ina_stream_t stream) {
+    using Src = SrcSr<X, true>;
+    if (int rc = check_v(V)) return rc;
+    if (n == 0) return INA_OK;
+    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
+    if (!x || !wire) return set_error(INA_EINVAL, "null pointer%s", "");
+    Src src;
+    bool al;
+    const B* one[1] = {x};
+    if (int rc = fill_pack(src.in, one, 1, al)) return rc;
+    if (int rc = sr_key(sr, src.key)) return rc;
+    hipStream_t s = hs(stream);
+    int8_t* kb = const_cast<int8_t*>(kblk);
+    int shift;
+    if (vec_v(V, shift) && src_aligned(src.in, 1) && aligned16(wire)) {
+        hipLaunchKernelGGL((k_qr_blk_i32<Src, 1, K_GIVEN>), dim3(grid_of((n + 3) / 4, default_grid_cap())), dim3(kBlk), 0,
+                           s, src, 1, 0, kb, 1.0, wire, n, shift);
+    } else {
+        ScalarArgs<Src> a{src, 1, 0, nullptr, nullptr, kb, 1.0, wire, n, (size_t)V, nullptr, 0.f};
+        launch_scalar<S_Q32, K_GIVEN>(a, s);
+    }
+    return launched();
 }
 template <typename X, typename B>
 int quantize_i16(const B* x, const int8_t* kblk, int V, int16_t* q, size_t n, uint8_t* ovf, ina_stream_t stream) {
@@ -845,6 +921,63 @@ int ina_dequantize_blk_i16_x16(const int16_t* sv, const int8_t* kblk, int V, voi
                                ina_stream_t stream) {
     if (int rc = check_x16_type(ytype)) return rc;
     return INA_BLK_X16_CALL(ytype, dequantize, sv, kblk, V, y, n, stream);
+}
+
+// ---- stochastic rounding (include/ina_blk_sr.h): the siblings above with the ina_sr_t before the stream ----
+int ina_block_scales_sr_x16(const void* const* xs, int xtype, int W, const float* base, size_t n, int V, int degree,
+                            int bits, int8_t* kblk, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    return INA_BLK_X16_CALL(xtype, block_scales, xs, W, base, n, V, degree, bits, kblk, stream, 1.0);
+}
+
+int ina_quantize_blk_sr_f32_i32(const float* x, const int8_t* kblk, int V, int32_t* q, size_t n, const ina_sr_t* sr,
+                                ina_stream_t stream) {
+    return quantize_i32<float, true>(x, kblk, V, q, n, stream, sr);
+}
+
+int ina_quantize_blk_sr_x16_i32(const void* x, int xtype, const int8_t* kblk, int V, int32_t* q, size_t n,
+                                const ina_sr_t* sr, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (xtype == INA_X16_BF16) return quantize_i32<bf16_t, true>(x, kblk, V, q, n, stream, sr);
+    return quantize_i32<fp16_t, true>(x, kblk, V, q, n, stream, sr);
+}
+
+int ina_quantize_blk_sr_f32_i16_wire(const float* x, const int8_t* kblk, int V, int32_t* wire, size_t n,
+                                     const ina_sr_t* sr, ina_stream_t stream) {
+    return quantize_wire_sr<float>(x, kblk, V, wire, n, sr, stream);
+}
+
+int ina_quantize_blk_sr_x16_i16_wire(const void* x, int xtype, const int8_t* kblk, int V, int32_t* wire, size_t n,
+                                     const ina_sr_t* sr, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (xtype == INA_X16_BF16) return quantize_wire_sr<bf16_t>(x, kblk, V, wire, n, sr, stream);
+    return quantize_wire_sr<fp16_t>(x, kblk, V, wire, n, sr, stream);
+}
+
+int ina_quantize_reduce_blk_sr_f32_i32(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V,
+                                       int32_t* out, size_t n, const ina_sr_t* sr, ina_stream_t stream) {
+    return reduce_i32<float, true>(bufs, W, kblk, mode, degree, V, out, n, stream, sr);
+}
+
+int ina_quantize_reduce_blk_sr_f32_i16_sat(const float* const* bufs, int W, int8_t* kblk, int mode, int degree, int V,
+                                           int16_t* out, size_t n, uint8_t* ovf, const ina_sr_t* sr,
+                                           ina_stream_t stream) {
+    return reduce_i16<float, true>(bufs, W, kblk, mode, degree, V, out, n, ovf, stream, sr);
+}
+
+int ina_quantize_reduce_blk_sr_x16_i32(const void* const* bufs, int xtype, int W, int8_t* kblk, int mode, int degree,
+                                       int V, int32_t* out, size_t n, const ina_sr_t* sr, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (xtype == INA_X16_BF16) return reduce_i32<bf16_t, true>(bufs, W, kblk, mode, degree, V, out, n, stream, sr);
+    return reduce_i32<fp16_t, true>(bufs, W, kblk, mode, degree, V, out, n, stream, sr);
+}
+
+int ina_quantize_reduce_blk_sr_x16_i16_sat(const void* const* bufs, int xtype, int W, int8_t* kblk, int mode,
+                                           int degree, int V, int16_t* out, size_t n, uint8_t* ovf,
+                                           const ina_sr_t* sr, ina_stream_t stream) {
+    if (int rc = check_x16_type(xtype)) return rc;
+    if (xtype == INA_X16_BF16) return reduce_i16<bf16_t, true>(bufs, W, kblk, mode, degree, V, out, n, ovf, stream, sr);
+    return reduce_i16<fp16_t, true>(bufs, W, kblk, mode, degree, V, out, n, ovf, stream, sr);
 }
 
 int ina_ps_apply_blk_i32(const float* local, const int32_t* sum_int, const int8_t* kblk, int V, double weight_step,

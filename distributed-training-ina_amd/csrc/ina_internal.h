@@ -36,9 +36,9 @@ int combine_ina_grid_cap();   // ina_kernels.hip: grid cap of the INA combines, 
 // rounding -- 1/2 to nearest, 1 stochastically (ina_scale_for_sr's rule, include/ina_pkt_sr.h)
 int scale_lim(int degree, int bits, double& lim, double round = 0.5);
 // ina_blk.hip: the block-scaled calls' checks of V (>= 1) and of mode / degree / kblk (lim as above
-// under INA_BLK_AUTO, else 1)
+// under INA_BLK_AUTO with scale_lim's round, else 1)
 int check_v(int V);
-int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim);
+int check_mode(int mode, const int8_t* kblk, int degree, int bits, double& lim, double round = 0.5);
 // ina_blk.hip: where a block kernel's k comes from -- the call's one k (the error-feedback calls only),
 // kblk[block] read, or the block's max |value| in the launch with kblk[block] written
 enum { K_GLOBAL, K_GIVEN, K_AUTO };

@@ -38,12 +38,8 @@ namespace {
 
 constexpr int kBlk = kHostBlock;
 
-// worker w's stream: counter word 3 is sub + w (mod 2^32)
-__device__ __forceinline__ SrKey stream_of(const SrKey& a, int w) {
-    SrKey b = a;
-    b.sub = a.sub + (uint32_t)w;
-    return b;
-}
+// (stream_of, worker w's stream, and q16x4_add_sr are in ina_sr_device.h: the block-scaled instances of
+// ina_blk.hip run the same ones)
 
 // one value of the sum at element j, every worker: the value-by-value paths
 template <typename X>
@@ -86,11 +82,6 @@ __global__ __launch_bounds__(kBlk) void k_qr_sr_i32(PtrPack<X> in, int Wd, int32
     for (size_t j = 4 * n4 + tid; j < n; j += stride) out[j] = (int32_t)sum1_q32(in, nw, j, s, a);
 }
 
-// one worker's chunk at element e of a whole region added to the 4 widened sums
-__device__ __forceinline__ void q16x4_add_sr(f32x4 v, float s, u32x4 word, int32_t* acc, bool& sat) {
-    const f32x4 y = sr_y4(v, s, word);
-    acc[0] += q16_of(y.x, sat); acc[1] += q16_of(y.y, sat); acc[2] += q16_of(y.z, sat); acc[3] += q16_of(y.w, sat);
-}
 // the 4 sums of every worker's chunk at element e
 template <typename X, int W>
 __device__ __forceinline__ void sum4_q16(const PtrPack<X>& in, int nw, size_t e, float s, const SrKey& a,

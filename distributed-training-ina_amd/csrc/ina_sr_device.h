@@ -1,6 +1,7 @@
 // ina_sr_device.h -- the generator and the rounding step of stochastic rounding (include/ina_sr.h
-// states the contract): the one copy, run by the quantisers of ina_sr.hip and by the stochastic
-// worker packs of ina_kernels.hip (include/ina_pkt_sr.h).
+// states the contract): the one copy, run by the quantisers of ina_sr.hip, by the stochastic worker
+// packs of ina_kernels.hip (include/ina_pkt_sr.h), by the fused reduces of ina_reduce_sr.hip and by the
+// stochastic instances of the block kernels of ina_blk.hip (include/ina_blk_sr.h).
 //
 // word is Philox4x32-10 under the key (seed) at the counter ((e0 + e) >> 2, step, sub), output word
 // (e0 + e) & 3: one call serves the 4 values a lane owns, and e0 % 4 == 0 keeps a lane's chunk inside
@@ -60,6 +61,23 @@ __device__ __forceinline__ f32x4 sr_y4(f32x4 d, float s, u32x4 w) {
 __device__ __forceinline__ u32x4 sr_q32x4(f32x4 d, float s, u32x4 w) {
     const f32x4 y = sr_y4(d, s, w);
     return u32x4{(uint32_t)q32_of(y.x), (uint32_t)q32_of(y.y), (uint32_t)q32_of(y.z), (uint32_t)q32_of(y.w)};
+}
+
+// the int16 wire's words (q16 + (sat << 22)) of the same
+__device__ __forceinline__ u32x4 sr_q16wx4(f32x4 d, float s, u32x4 w) {
+    const f32x4 y = sr_y4(d, s, w);
+    return u32x4{(uint32_t)q16w_of(y.x), (uint32_t)q16w_of(y.y), (uint32_t)q16w_of(y.z), (uint32_t)q16w_of(y.w)};
+}
+// one worker's chunk rounded with the words of one Philox call and added to the 4 widened int16 sums
+__device__ __forceinline__ void q16x4_add_sr(f32x4 v, float s, u32x4 word, int32_t* acc, bool& sat) {
+    const f32x4 y = sr_y4(v, s, word);
+    acc[0] += q16_of(y.x, sat); acc[1] += q16_of(y.y, sat); acc[2] += q16_of(y.z, sat); acc[3] += q16_of(y.w, sat);
+}
+// worker w's stream of a fused call: counter word 3 is sub + w (mod 2^32)
+__device__ __forceinline__ SrKey stream_of(const SrKey& a, int w) {
+    SrKey b = a;
+    b.sub = a.sub + (uint32_t)w;
+    return b;
 }
 
 // the checks every stochastic call ends with, then *sr as the kernels take it

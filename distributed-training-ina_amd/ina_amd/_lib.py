@@ -230,6 +230,20 @@ SIGNATURES_REDUCE_SR = {
     "ina_quantize_reduce_sr_x16_i32": [_vp, _i, _i, _vp, _sz, _i, C.POINTER(SrParams), _vp],
     "ina_quantize_reduce_sr_x16_i16_sat": [_vp, _i, _i, _vp, _sz, _i, _i, _vp, C.POINTER(SrParams), _vp],
 }
+# stochastic rounding with per-block scales (include/ina_blk_sr.h): the round-to-nearest block siblings'
+# arguments with the ina_sr_t before the stream; the scales call is its sibling's
+SIGNATURES_BLK_SR = {
+    "ina_block_scales_sr_x16": [_vp, _i, _i, _vp, _sz, _i, _i, _i, _vp, _vp],
+    "ina_quantize_blk_sr_f32_i32": [_vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_blk_sr_x16_i32": [_vp, _i, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_blk_sr_f32_i16_wire": [_vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_blk_sr_x16_i16_wire": [_vp, _i, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_reduce_blk_sr_f32_i32": [_vp, _i, _vp, _i, _i, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_reduce_blk_sr_f32_i16_sat": [_vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_reduce_blk_sr_x16_i32": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_reduce_blk_sr_x16_i16_sat": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp, C.POINTER(SrParams),
+                                               _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -247,7 +261,7 @@ def open_library(path: str) -> C.CDLL:
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
-                       **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR}.items():
+                       **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -70,6 +70,12 @@ more moves, so it is there where error feedback is not: 16-bit buckets, and any 
 only, and not together with error feedback.  Layout B has it as a class of its own,
 StochasticRangeAggregator (include/ina_reduce_sr.h): the fused quantise + reduce rounds worker w's slice
 on stream w, so its integer aggregate is the sharded step's, bit for bit.
+
+Per-block scales and stochastic rounding together (include/ina_blk_sr.h, ina_amd.blk_sr) are two classes of
+their own, since the constructors above refuse the pair by name: BlockStochasticAggregator (layout A: the
+ranks' scales under sr.scale_for's rule, their MIN, the stochastic block quantise on stream `rank`) and
+BlockStochasticRangeAggregator (layout B: the fused AUTO reduce with sub = 0, e0 = lo), whose integers, flags
+and scales agree bit for bit on both wires.
 """
 from __future__ import annotations
 
@@ -78,7 +84,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib, blk, ef, ops, sr
+from . import _lib, blk, blk_sr, ef, ops, sr
 from . import wire as _wire          # (the aggregators' `wire` argument is the wire's name)
 
 
@@ -840,5 +846,86 @@ class StochasticRangeAggregator(RangeAggregator):
             else:
                 sr.quantize_reduce_i16(slices, self.k, self.V, self.seed, step=self._step, e0=self.lo,
                                        out=self.sum_shard[:m], overflow=self.ovf_shard[: -(-m // self.V)])
+        self._step = (self._step + 1) & 0xFFFFFFFF
+        return m
+
+
+def _check_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
+    return seed
+
+
+class BlockStochasticAggregator(ShardedAggregator):
+    """ShardedAggregator(k="block") with the rank's quantise rounded stochastically (include/ina_blk_sr.h,
+    ina_amd.blk_sr): per-block scales and unbiased rounding together, the pair an int16 job of many ranks
+    wants.  Every rank takes blk_sr.block_scales of its bucket for `world` summands (sr.scale_for's rule: a
+    whole quantum of headroom per summand), the ranks agree on the element-wise MIN (agree_block_scales --
+    sr.scale_for is monotone in amax, so the MIN is the scale of the ranks' joint max), and the rank
+    quantises with blk_sr.quantize (wire="i32") or blk_sr.quantize_i16_wire (wire="i16") under the key
+    `seed` with sub = this rank, e0 = 0 and step = `step`, the counter of
+    ShardedAggregator(rounding="stochastic"): it starts at 0, advances by one per call (aggregate_int and
+    phase_quantize included) and may be set, so that a resumed job rounds as the uninterrupted one would.
+    Everything after the quantise -- the collectives, the decode, gather_bytes, scale_bytes -- is the
+    k="block" step's, unchanged.  Every collective, both wires, any bucket dtype, any out_dtype.  No
+    chunks and no error feedback, and no such arguments; a class of its own, since ShardedAggregator
+    refuses rounding="stochastic" with k="block" by name."""
+
+    def __init__(self, n: int, group=None, device=None, align: int = 1024, wire: str = "i32", V: int = 256,
+                 collective: str = "rs_ag", out_dtype: torch.dtype = torch.float32, seed: int = 0):
+        _check_seed(seed)
+        super().__init__(n, k="block", group=group, device=device, align=align, wire=wire, V=V,
+                         collective=collective, out_dtype=out_dtype, seed=seed)
+        self.rounding, self.stochastic = "stochastic", True      # the step counter advances
+
+    def _quantize(self, grad: torch.Tensor):
+        n = self.plan.n
+        x = self._bucket(grad)
+        kb = self.kblk
+        blk_sr.block_scales([x], self.V, bits=32 if self.wire == "i32" else 16, degree=self.world, out=kb)
+        agree_block_scales(kb, self.group)
+        fn = blk_sr.quantize if self.wire == "i32" else blk_sr.quantize_i16_wire
+        fn(x, kb, self.V, self.seed, step=self._step, sub=self.rank, e0=0, out=self.q[:n])
+        self._advance()
+
+
+class BlockStochasticRangeAggregator(RangeAggregator):
+    """RangeAggregator(k="block") with every summand rounded stochastically (include/ina_blk_sr.h,
+    ina_amd.blk_sr): layout B's answer to BlockStochasticAggregator.  The reduce is the AUTO
+    blk_sr.quantize_reduce / blk_sr.quantize_reduce_i16 with degree = W (the number of slices), the key
+    `seed`, sub = 0 -- worker w of the slices draws from stream w -- e0 = this rank's `lo` and
+    step = `step`, StochasticRangeAggregator's counter.  With worker w's slices coming from the rank-w
+    bucket of a BlockStochasticAggregator step of W ranks, this rank's integer aggregate, flags and
+    scales are bit for bit that range of the sharded step's, on both wires.  Everything after the reduce
+    is RangeAggregator's.  `lo` must be a multiple of 4: a plan whose align is one gives that."""
+
+    def __init__(self, n: int, group=None, device=None, align: int = 1024, wire: str = "i32", V: int = 256,
+                 out_dtype: torch.dtype = torch.float32, seed: int = 0):
+        _check_seed(seed)
+        super().__init__(n, k="block", group=group, device=device, align=align, wire=wire, V=V, out_dtype=out_dtype)
+        if self.hi > self.lo and self.lo % 4:
+            raise ValueError(f"this rank's range starts at {self.lo}, not a multiple of 4 (it is the e0 of the "
+                             f"rounding): use an align that is a multiple of 4")
+        self.rounding, self.seed, self._step = "stochastic", seed, 0
+
+    step = StochasticRangeAggregator.step
+
+    def _reduce(self, slices) -> int:
+        # (the slice normalisation and the length check are RangeAggregator._reduce's, as in
+        # StochasticRangeAggregator)
+        m = self.hi - self.lo
+        if isinstance(slices, torch.Tensor):
+            slices = list(slices.unbind(0)) if slices.dim() > 1 else [slices]
+        slices = [t.reshape(-1) for t in slices]
+        if not slices or any(t.numel() != m for t in slices):
+            raise ValueError(f"every worker slice must hold this rank's {m} values")
+        if m:                         # more ranks than ranges: nothing here, zeros gathered
+            nb = -(-m // self.V)
+            kw = dict(degree=len(slices), step=self._step, sub=0, e0=self.lo, out=self.sum_shard[:m],
+                      kblk_out=self.k_shard[:nb])
+            if self.wire == "i32":
+                blk_sr.quantize_reduce(slices, self.V, self.seed, **kw)
+            else:
+                blk_sr.quantize_reduce_i16(slices, self.V, self.seed, overflow=self.ovf_shard[:nb], **kw)
         self._step = (self._step + 1) & 0xFFFFFFFF
         return m

@@ -301,7 +301,8 @@ int ina_unpack_nga_split(const uint8_t* hdr, const uint8_t* pay, size_t npkts, i
  * stated in ina_sr.h. */
 #include "ina_sr.h"   /* ina_sr_t, the ina_quantize_sr_* entry points and ina_scale_for_sr */
 #include "ina_pkt_sr.h"   /* the same on the packet path: the ina_quantize_pack_nga_*_sr worker packs */
-#include "ina_reduce_sr.h"   /* and in the fused quantise + reduce calls: ina_quantize_reduce_sr_* */
+#include "ina_reduce_sr.h"   /* and in the fused quantise + reduce calls: ina_quantize_reduce_sr_*; it ends by
+                              * including the same with per-block scales, the ina_*blk_sr_* entry points */
 
 /* C-128 pack (communicator.cc:23-37): npkts x 524-byte packet_t, all words htonl. */
 int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,

@@ -48,7 +48,8 @@
  * and the int16 out 8-byte aligned and, for the slot flags, V with a ballot layout (V % 8 == 0, V / 8
  * a power of two <= 64); anything else takes a value-by-value path with identical results.
  *
- * Not here: block scales (ina_quantize_reduce_blk_*), a base, error feedback, and the PS combine.
+ * Not here: a base, error feedback, and the PS combine.  Stochastic rounding with block scales
+ * (ina_quantize_reduce_blk_sr_*) is in ina_blk_sr.h, which this header includes as its last line.
  */
 #ifndef INA_REDUCE_SR_H
 #define INA_REDUCE_SR_H
@@ -68,5 +69,8 @@ int ina_quantize_reduce_sr_x16_i32(const void* const* bufs, int xtype, int W, in
 int ina_quantize_reduce_sr_x16_i16_sat(const void* const* bufs, int xtype, int W, int16_t* out, size_t n, int k,
                                        int V, uint8_t* overflow_per_slot, const ina_sr_t* sr,
                                        ina_stream_t stream);
+
+#include "ina_blk_sr.h" /* the same with per-block scales; from here, since ina.h names no block-scale header
+                         * with an infix */
 
 #endif /* INA_REDUCE_SR_H */

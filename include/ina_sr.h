@@ -52,9 +52,9 @@
  * int16 outputs 8-byte aligned, and, for the slot flags, V with a ballot layout (V % 8 == 0, V / 8 a
  * power of two <= 64); any other alignment or V takes a value-by-value path with identical results.
  *
- * Not here: block scales on the bulk quantisers and the sharded wires, and stochastic rounding
- * combined with error feedback.  The worker packs of the packet path, per-packet scales included, are
- * in ina_pkt_sr.h; the fused quantise + reduce calls in ina_reduce_sr.h.
+ * Not here: stochastic rounding combined with error feedback.  The worker packs of the packet path,
+ * per-packet scales included, are in ina_pkt_sr.h; the fused quantise + reduce calls in ina_reduce_sr.h;
+ * block scales on the bulk quantisers, the fused calls and the sharded wires in ina_blk_sr.h.
  */
 #ifndef INA_SR_H
 #define INA_SR_H

@@ -595,6 +595,59 @@ def run_blk_sr(dev):
     return rows
 
 
+def run_rot(dev):
+    """The randomised Hadamard rotation (include/ina_rot.h) at the ResNet-50 size (rounded down to a multiple
+    of 256), cold caches, median of 20, the set twice in this process (run 1 / run 2): the rotated AUTO
+    reduces -- int32 at W = 8, int16 at W = 4 and W = 16, V = 256 and 32, fp32 and bf16 buckets -- both
+    decodes and the PS combine at W = 8.  Each call moves its unrotated block-scaled sibling's bytes and is
+    timed beside it; the sibling is timed twice, and the bar is its faster time plus the spread of the two.
+    Nothing is gated here; DESIGN 4.1o reads the rows."""
+    from ina_amd import blk, ops, rot
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(43)
+    n, seed = 25_557_032 // 256 * 256, 0x1234
+    xs32 = [torch.randn(n, device=dev, generator=gen) * 1e-2 for _ in range(16)]
+    xs16 = [x.to(torch.bfloat16) for x in xs32]
+    o32 = torch.empty(n, dtype=torch.int32, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    y = torch.empty(n, device=dev)
+
+    def row(run, name, nbytes, f_rot, f_sib):
+        ta, tr, tb = _time(f_sib), _time(f_rot), _time(f_sib)
+        lo, spread = min(ta, tb), abs(ta - tb)
+        rows.append(_row(f"{name} [rot, run {run}]", tr, nbytes,
+                         sibling_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], sibling_spread_us=round(spread * 1e6, 2),
+                         rot_over_sibling=round(tr / lo, 3), bar_met=bool(tr <= lo + spread)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = n // V
+            ovf = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kout = torch.empty(nblk, dtype=torch.int8, device=dev)
+            for bits, W in ((32, 8), (16, 4), (16, 16)):
+                for src, tag in ((xs32, "f32"), (xs16, "bf16")):
+                    xs, b = src[:W], src[0].element_size()
+                    if bits == 32:
+                        row(run, f"quantize_reduce W={W} {tag}->i32 V={V} AUTO", (W * b + 4) * n + nblk,
+                            lambda: rot.quantize_reduce(xs, V, seed, step=run, out=o32, kblk_out=kout),
+                            lambda: blk.quantize_reduce(xs, V, out=o32, kblk_out=kout))
+                    else:
+                        row(run, f"quantize_reduce_i16 W={W} {tag}->i16 V={V} AUTO", (W * b + 2) * n + 2 * nblk,
+                            lambda: rot.quantize_reduce_i16(xs, V, seed, step=run, out=o16, overflow=ovf, kblk_out=kout),
+                            lambda: blk.quantize_reduce_i16(xs, V, out=o16, overflow=ovf, kblk_out=kout))
+            rot.quantize_reduce(xs32[:8], V, seed, step=run, out=o32, kblk_out=kout)
+            row(run, f"dequantize i32->f32 V={V}", 8 * n + nblk,
+                lambda: rot.dequantize(o32, kout, V, seed, step=run, out=y), lambda: blk.dequantize(o32, kout, V, out=y))
+            rot.quantize_reduce_i16(xs32[:4], V, seed, step=run, out=o16, overflow=ovf, kblk_out=kout)
+            row(run, f"dequantize i16->f32 V={V}", 6 * n + nblk,
+                lambda: rot.dequantize(o16, kout, V, seed, step=run, out=y), lambda: blk.dequantize(o16, kout, V, out=y))
+            row(run, f"ps_combine_ina W=8 V={V}", 10 * 4 * n,
+                lambda: rot.ps_combine_ina(xs32[8], xs32[:8], V, 0.01, seed, step=run, out=y),
+                lambda: ops.ps_combine_ina_blk(xs32[8], xs32[:8], V, 0.01, out=y))
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1294,6 +1347,7 @@ def run_extra(dev):
     rows += run_sr_packets(dev)
     rows += run_sr_reduce(dev)
     rows += run_blk_sr(dev)
+    rows += run_rot(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

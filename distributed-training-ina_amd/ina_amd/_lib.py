@@ -244,6 +244,16 @@ SIGNATURES_BLK_SR = {
     "ina_quantize_reduce_blk_sr_x16_i16_sat": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp, C.POINTER(SrParams),
                                                _vp],
 }
+# the randomised Hadamard rotation in front of the block-scaled quantise and reduce (include/ina_rot.h): the
+# type code (0: fp32) follows the buckets, the ina_sr_t precedes the stream
+SIGNATURES_ROT = {
+    "ina_block_scales_rot": [_vp, _i, _i, _sz, _i, _i, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_reduce_rot_i32": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_quantize_reduce_rot_i16_sat": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+    "ina_dequantize_rot_i32": [_vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_dequantize_rot_i16": [_vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+    "ina_ps_combine_ina_rot_f32": [_vp, _vp, _i, _i, _d, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -261,7 +271,8 @@ def open_library(path: str) -> C.CDLL:
     for name, args in {**SIGNATURES, **SIGNATURES_X16, **SIGNATURES_BLK, **SIGNATURES_PKT_BLK,
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
-                       **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR}.items():
+                       **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR,
+                       **SIGNATURES_ROT}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

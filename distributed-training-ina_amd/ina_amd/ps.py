@@ -87,15 +87,23 @@ def aggregate(global_model, worker_list, step_size, worker_num: int | None = Non
     return out
 
 
-def combine_ina(local: torch.Tensor, paras, k, weight_step: float, out=None, block: int = 256):
+def combine_ina(local: torch.Tensor, paras, k, weight_step: float, out=None, block: int = 256, rotate=None):
     """local + float(weight_step) * dequant(sum_w q(paras[w] - local)) on the GPU.
     k="auto": the largest scale at which no delta and no W-way sum saturates
     (ops.scale_for_workers over the deltas; one host read).
     k="block": that scale per block of `block` values, computed on the device in the same
-    pass (ina_ps_combine_ina_blk_f32): one enqueue, no host read."""
+    pass (ina_ps_combine_ina_blk_f32): one enqueue, no host read.
+    rotate=seed (with k="block"): each block of deltas is rotated -- random signs under `seed`, then a
+    Walsh-Hadamard transform -- before it is quantised and rotated back after the sum, in the same one
+    launch (ina_amd.rot, ina_ps_combine_ina_rot_f32)."""
     from . import _lib
     if isinstance(k, str) and k not in ("auto", "block"):
         raise ValueError(f"unknown k {k!r}: an int, \"auto\" or \"block\"")
+    if rotate is not None:
+        if k != "block":
+            raise ValueError("rotate needs k=\"block\": the rotation is per block")
+        from . import rot
+        return rot.ps_combine_ina(local, paras, block, weight_step, rotate, out=out)
     if k == "block":
         return ops.ps_combine_ina_blk(local, paras, block, weight_step, out=out)
     ops._req(local, torch.float32, "local")

@@ -68,7 +68,8 @@
  *
  * Not here: a standalone int16 quantiser (the W = 1 fused call, ina_quantize_reduce_blk_sr_*_i16_sat
  * with INA_BLK_GIVEN, is that operation), a base, error feedback combined with stochastic rounding, the
- * PS combine, and a pipelined sharded step (chunks > 1).
+ * PS combine, and a pipelined sharded step (chunks > 1).  A rotation of each block in front of the
+ * round-to-nearest quantiser is in ina_rot.h, which this header includes as its last line.
  */
 #ifndef INA_BLK_SR_H
 #define INA_BLK_SR_H
@@ -106,5 +107,7 @@ int ina_quantize_reduce_blk_sr_x16_i16_sat(const void* const* bufs, int xtype, i
                                            int degree, int V, int16_t* out, size_t n,
                                            uint8_t* overflow_per_slot, const ina_sr_t* sr,
                                            ina_stream_t stream);
+
+#include "ina_rot.h" /* a randomised Hadamard rotation in front of the block-scaled quantise and reduce */
 
 #endif /* INA_BLK_SR_H */

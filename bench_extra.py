@@ -648,6 +648,62 @@ def run_rot(dev):
     return rows
 
 
+def run_i8(dev):
+    """The 8-bit wire (include/ina_i8.h) at the ResNet-50 size (rounded down to a multiple of 256), cold caches,
+    median of 20, the set twice in this process (run 1 / run 2): i8.quantize and i8.block_scales on fp32 and bf16
+    buckets at V = 256 and 32, rotated and plain, and i8.sum_slices at G = 8 and 64.  Bars, each the parent's
+    own kernel timed twice in the same process (its faster time plus the spread of the two): the rotated
+    quantiser against rot.quantize_reduce_i16 (W = 1, GIVEN, same V and dtype), which runs the same butterfly
+    and writes twice the bytes; the slice sum at G = 8 against ops.sum_reduce_i16 at W = 8, which moves 18
+    bytes a value against 10.  Nothing is gated here; DESIGN 4.1p reads the rows."""
+    from ina_amd import i8, ops, rot
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(47)
+    n, seed = 25_557_032 // 256 * 256, 0x1234
+    x32 = torch.randn(n, device=dev, generator=gen) * 1e-2
+    srcs = ((x32, "f32"), (x32.to(torch.bfloat16), "bf16"))
+    q8 = torch.empty(n, dtype=torch.int8, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    parts = [torch.randint(-128, 128, (n,), dtype=torch.int8, device=dev, generator=gen) for _ in range(64)]
+    s16 = [torch.randint(-4000, 4000, (n,), dtype=torch.int16, device=dev, generator=gen) for _ in range(8)]
+
+    def row(run, name, nbytes, f_new, f_bar=None, bar_name=None):
+        if f_bar is None:
+            rows.append(_row(f"{name} [i8, run {run}]", _time(f_new), nbytes))
+            return
+        ta, tn, tb = _time(f_bar), _time(f_new), _time(f_bar)
+        lo, spread = min(ta, tb), abs(ta - tb)
+        rows.append(_row(f"{name} [i8, run {run}]", tn, nbytes, bar=bar_name,
+                         bar_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], bar_spread_us=round(spread * 1e6, 2),
+                         over_bar=round(tn / lo, 3), bar_met=bool(tn <= lo + spread)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = n // V
+            ovf = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kout = torch.empty(nblk, dtype=torch.int8, device=dev)
+            for x, tag in srcs:
+                b = x.element_size()
+                kb8 = i8.block_scales([x], V, rotate=seed, step=run)
+                kb16 = rot.block_scales([x], V, seed, bits=16, degree=1, step=run)
+                row(run, f"quantize {tag}->i8 V={V} rot", (b + 1) * n + 2 * nblk,
+                    lambda: i8.quantize(x, kb8, V, rotate=seed, step=run, out=q8, overflow=ovf),
+                    lambda: rot.quantize_reduce_i16([x], V, seed, kblk=kb16, step=run, out=o16, overflow=ovf),
+                    "rot.quantize_reduce_i16 W=1 GIVEN")
+                kbp = i8.block_scales([x], V)
+                row(run, f"quantize {tag}->i8 V={V} plain", (b + 1) * n + 2 * nblk,
+                    lambda: i8.quantize(x, kbp, V, out=q8, overflow=ovf))
+                row(run, f"block_scales {tag} V={V} rot", b * n + nblk,
+                    lambda: i8.block_scales([x], V, rotate=seed, step=run, out=kout))
+                row(run, f"block_scales {tag} V={V} plain", b * n + nblk, lambda: i8.block_scales([x], V, out=kout))
+        ovf = torch.empty(n // 256, dtype=torch.uint8, device=dev)
+        row(run, "sum_slices G=8", 10 * n, lambda: i8.sum_slices(parts[:8], out=o16),
+            lambda: ops.sum_reduce_i16(s16, 256, out=o16, overflow=ovf), "ops.sum_reduce_i16 W=8")
+        row(run, "sum_slices G=64", 66 * n, lambda: i8.sum_slices(parts, out=o16))
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1348,6 +1404,7 @@ def run_extra(dev):
     rows += run_sr_reduce(dev)
     rows += run_blk_sr(dev)
     rows += run_rot(dev)
+    rows += run_i8(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

@@ -254,6 +254,14 @@ SIGNATURES_ROT = {
     "ina_dequantize_rot_i16": [_vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
     "ina_ps_combine_ina_rot_f32": [_vp, _vp, _i, _i, _d, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
 }
+# the 8-bit wire of the sharded step (include/ina_i8.h): the type code follows the bucket(s); the ina_sr_t (NULL:
+# no rotation) precedes the stream
+SIGNATURES_I8 = {
+    "ina_scale_for_i8": [C.c_float, C.POINTER(C.c_int)],
+    "ina_block_scales_i8": [_vp, _i, _i, _sz, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_i8_wire": [_vp, _i, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+    "ina_sum_i8_slices": [_vp, _i, _vp, _sz, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -272,7 +280,7 @@ def open_library(path: str) -> C.CDLL:
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
                        **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR,
-                       **SIGNATURES_ROT}.items():
+                       **SIGNATURES_ROT, **SIGNATURES_I8}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

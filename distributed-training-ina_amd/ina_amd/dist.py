@@ -76,6 +76,10 @@ their own, since the constructors above refuse the pair by name: BlockStochastic
 ranks' scales under sr.scale_for's rule, their MIN, the stochastic block quantise on stream `rank`) and
 BlockStochasticRangeAggregator (layout B: the fused AUTO reduce with sub = 0, e0 = lo), whose integers, flags
 and scales agree bit for bit on both wires.
+
+The 8-bit wire (include/ina_i8.h, ina_amd.i8) is a class of its own, ByteWireAggregator: rotated blocks as bytes
+over one all-to-all, the owner's exact int16 sum of the G received slices, an all-gather of the int16 sums and
+the rotation's decode -- 1 + 2 bytes a value on the links where the wires above move 4 + 2 and 4 + 4.
 """
 from __future__ import annotations
 
@@ -84,7 +88,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib, blk, blk_sr, ef, ops, sr
+from . import _lib, blk, blk_sr, ef, i8, ops, rot, sr
 from . import wire as _wire          # (the aggregators' `wire` argument is the wire's name)
 
 
@@ -929,3 +933,120 @@ class BlockStochasticRangeAggregator(RangeAggregator):
                 blk_sr.quantize_reduce_i16(slices, self.V, self.seed, overflow=self.ovf_shard[:nb], **kw)
         self._step = (self._step + 1) & 0xFFFFFFFF
         return m
+
+
+class ByteWireAggregator:
+    """Layout A on an 8-bit wire (include/ina_i8.h, ina_amd.i8): the wire word is one byte, which an all-to-all
+    can carry because it only moves bytes and the owner sums on its device.  One step, in order:
+    i8.block_scales of the rank's bucket (i8.scale_for's rule, which does not depend on the number of ranks);
+    agree_block_scales (the MIN over ranks); i8.quantize into the int8 [padded] buffer `q8` (its pad stays 0,
+    the pad's scales 127); one all_to_all_single of its uint8 view (host-staged under gloo, like
+    reduce_scatter_a2a); i8.sum_slices of the G received slices into the int16 `s16_shard` -- exact, 64 * 128
+    fits, so nothing saturates on the owner and no flag travels; all_gather_shards of the int16 shard into
+    `s16_full`; rot.dequantize (rotate=True) or blk.dequantize of the gathered sums into the fp32 `full` on
+    every rank.  On one rank the collectives are identities and the same kernels run.
+    rotate=True (default) rotates every block of V values under the key `seed` at step = `step`, sub = 0,
+    e0 = 0 -- one stream for all ranks; `step` starts at 0, advances by one per call and may be set, as on the
+    stochastic aggregators.  rotate=False is the plain byte wire, there for comparison: 8 bits resolve a
+    block only once it is flat.  Buckets are float32, bfloat16 or float16; the output is float32.
+    `kblk` holds the agreed scales of the last call and `local_overflow` this rank's flags (1 where a value
+    of the block clamped at +-127 under the agreed scale or was NaN; rank-local, never sent).  `wire_bytes`,
+    `gather_bytes` and `scale_bytes` are what one step brings to each rank over the links: (G-1) x shard x 1,
+    (G-1) x shard x 2, and one byte per block.  Shards are aligned to the lcm of `align`, V and 128, so every
+    shard starts where a rotated call may start (e0).  No chunks, no error feedback, no stochastic rounding,
+    no layout B."""
+
+    def __init__(self, n: int, V: int = 256, group=None, device=None, align: int = 1024, rotate: bool = True,
+                 seed: int = 0):
+        self.seed = _check_seed(seed)
+        V = int(V)
+        if V < 8 or V > 256 or V & (V - 1):
+            raise ValueError(f"V must be a power of two in [8, 256], got {V}")
+        self.rotate = bool(rotate)
+        if self.rotate and n % V:
+            raise ValueError(f"rotate=True needs n to be a multiple of V: {n} values in blocks of {V}")
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        if self.world > _lib.MAX_WORKERS:
+            raise ValueError(f"the byte wire sums at most {_lib.MAX_WORKERS} ranks into an int16, got {self.world}")
+        self.plan = ShardPlan(n, self.world, math.lcm(align, V, 128))
+        self.V, self.group, self._step = V, group, 0
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        tot, nblk = self.plan.padded, self.plan.padded // V
+        self.q8 = torch.zeros(tot, dtype=torch.int8, device=dev)
+        self._kbuf = torch.full((nblk,), 127, dtype=torch.int8, device=dev)
+        self._obuf = torch.zeros(nblk, dtype=torch.uint8, device=dev)
+        self._recv = torch.empty(tot, dtype=torch.int8, device=dev) if self.world > 1 else None
+        self.s16_shard = torch.empty(self.plan.shard, dtype=torch.int16, device=dev)
+        self.s16_full = torch.empty(tot, dtype=torch.int16, device=dev)
+        self.full = torch.empty(tot, dtype=torch.float32, device=dev)
+        self._stage = None           # rotate=False with n % V: the bucket padded with zeros to whole blocks
+
+    step = ShardedAggregator.step
+
+    @property
+    def kblk(self) -> torch.Tensor:
+        """The agreed scales of the last call (ceil(n / V) int8)."""
+        return self._kbuf[: -(-self.plan.n // self.V)]
+
+    @property
+    def local_overflow(self) -> torch.Tensor:
+        """This rank's per-block flags of the last call (ceil(n / V) bytes)."""
+        return self._obuf[: -(-self.plan.n // self.V)]
+
+    @property
+    def scale_bytes(self) -> int:
+        return -(-self.plan.n // self.V) if self.world > 1 else 0
+
+    @property
+    def wire_bytes(self) -> int:
+        """Bytes the all-to-all brings to each rank: one per value of the other ranks' slices."""
+        return (self.world - 1) * self.plan.shard
+
+    @property
+    def gather_bytes(self) -> int:
+        """Bytes the all-gather brings to each rank: the other shards' int16 sums."""
+        return (self.world - 1) * self.plan.shard * 2
+
+    def _bucket(self, grad: torch.Tensor) -> torch.Tensor:
+        if grad.numel() != self.plan.n:
+            raise ValueError("bucket size changed")
+        x = grad.reshape(-1)
+        if self.plan.n % self.V:
+            if self._stage is None or self._stage.dtype != x.dtype:
+                self._stage = torch.zeros(-(-self.plan.n // self.V) * self.V, dtype=x.dtype, device=x.device)
+            self._stage[: self.plan.n].copy_(x)
+            x = self._stage
+        return x
+
+    def _exchange(self):
+        """Slice j of `q8` to rank j; the G slices this rank now holds."""
+        if self.world == 1:
+            return [self.q8]
+        send = self.q8.view(torch.uint8)
+        if send.is_cuda and _host_staged(self.group):
+            h = torch.empty(self.plan.padded, dtype=torch.uint8)
+            dist.all_to_all_single(h, send.cpu(), group=self.group)
+            self._recv.copy_(h.view(torch.int8))
+        else:
+            dist.all_to_all_single(self._recv.view(torch.uint8), send, group=self.group)
+        return [self._recv[r * self.plan.shard:(r + 1) * self.plan.shard] for r in range(self.world)]
+
+    def __call__(self, grad: torch.Tensor) -> torch.Tensor:
+        """[n] local bucket -> [n] float32 decoded sum over all ranks."""
+        V = self.V
+        x = self._bucket(grad)
+        nb = x.numel() // V
+        key = dict(rotate=self.seed if self.rotate else None, step=self._step)
+        kb = self._kbuf[:nb]
+        i8.block_scales([x], V, out=kb, **key)
+        agree_block_scales(kb, self.group)
+        i8.quantize(x, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
+        i8.sum_slices(self._exchange(), out=self.s16_shard)
+        all_gather_shards(self.s16_shard, self.plan, self.group, out=self.s16_full)
+        if self.rotate:
+            rot.dequantize(self.s16_full, self._kbuf, V, self.seed, step=self._step, out=self.full)
+        else:
+            blk.dequantize(self.s16_full, self._kbuf, V, out=self.full)
+        self._step = (self._step + 1) & 0xFFFFFFFF
+        return self.full[: self.plan.n]

@@ -1,0 +1,90 @@
+"""The 8-bit wire of the sharded step (include/ina_i8.h), for float32, bfloat16 or float16 buckets.
+
+A rank quantises its bucket to bytes in [-127, 127] under per-block scales -- with `rotate=seed` after
+ina_amd.rot's rotation of each block of V values, which is what makes 8 bits enough -- sends slice j to rank j
+in one all-to-all, and the owner adds the G bytes of every value into an int16, exactly (64 * 128 fits).  The
+sums decode with rot.dequantize (rotated) or blk.dequantize (plain) under the agreed scales.
+dist.ByteWireAggregator runs the step; tests/_i8_ref.py replays the contract.
+
+    kblk = i8.block_scales([grad], V, rotate=seed, step=t)          # then MIN across ranks
+    q8 = i8.quantize(grad, kblk, V, rotate=seed, step=t)            # int8, one byte a value
+    s16 = i8.sum_slices(received)                                   # int16, exact
+    g = rot.dequantize(gathered, kblk, V, seed, step=t)
+
+`rotate` is None (no rotation) or the seed.  n must be a multiple of V for the block calls, buffers 16-byte
+aligned, e0 a multiple of 128 and of V; no base; no CPU fallback and no value-by-value path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from ._lib import MAX_WORKERS, check, load
+from .ops import _blk_scales_arg, _fits, _grad_bufs, _ptrs, _req, _req_grad, _same_device, _stream
+from .rot import _key, _v
+
+
+def scale_for(absmax: float) -> int:
+    """The largest k in [-126, 127] with absmax * 2^k + 1/2 <= 127, whatever the number of ranks: the sum's
+    headroom is the int16 accumulator's."""
+    k = C.c_int(0)
+    check(load().ina_scale_for_i8(float(absmax), C.byref(k)), "i8.scale_for")
+    return k.value
+
+
+def _sr(rotate, step, sub, e0, V):
+    """The ina_sr_t of a rotated call, or None (a NULL sr) for rotate=None."""
+    return None if rotate is None else C.byref(_key(rotate, step, sub, e0, V))
+
+
+def block_scales(xs, V: int, rotate: int | None = None, step: int = 0, sub: int = 0, e0: int = 0,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """int8 [n / V]: for each block scale_for(max |r|) over the given buckets, r the rotated values under
+    `rotate`.  Ranks of one job agree on a block's scale by taking the MIN of theirs."""
+    xs, n, xt = _grad_bufs(xs, "xs")
+    V = _v(V, n)
+    prm = _sr(rotate, step, sub, e0, V)
+    out = _blk_scales_arg(out, n // V, xs[0], "out")
+    check(load().ina_block_scales_i8(_ptrs(xs), xt, len(xs), n, V, out.data_ptr(), prm, _stream(xs[0])),
+          "i8.block_scales")
+    return out
+
+
+def quantize(x: torch.Tensor, kblk: torch.Tensor, V: int, rotate: int | None = None, step: int = 0, sub: int = 0,
+             e0: int = 0, out: torch.Tensor | None = None, overflow: torch.Tensor | None = None):
+    """(int8 [n], flags): clamp(rne(r * 2^kblk[block]), -127, 127), NaN -> 0; one rank-local flag per block,
+    1 where a value clamped or was NaN."""
+    xt = _req_grad(x, "x")
+    n = x.numel()
+    V = _v(V, n)
+    prm = _sr(rotate, step, sub, e0, V)
+    kblk = _blk_scales_arg(kblk, n // V, x, given=True)
+    out = torch.empty(n, dtype=torch.int8, device=x.device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int8, "out")
+    overflow = torch.empty(n // V, dtype=torch.uint8, device=x.device) if overflow is None else overflow
+    _fits(overflow, n // V, "overflow")
+    _req(overflow, torch.uint8, "overflow")
+    _same_device(x, out, overflow)
+    check(load().ina_quantize_i8_wire(x.data_ptr(), xt, kblk.data_ptr(), V, out.data_ptr(), n, overflow.data_ptr(),
+                                      prm, _stream(x)), "i8.quantize")
+    return out, overflow
+
+
+def sum_slices(parts, out: torch.Tensor | None = None) -> torch.Tensor:
+    """int16 [n]: the exact element-wise sum of 1..64 int8 slices of n values each (any n)."""
+    parts = list(parts.unbind(0)) if isinstance(parts, torch.Tensor) and parts.dim() > 1 else list(parts)
+    if not 1 <= len(parts) <= MAX_WORKERS:
+        raise ValueError(f"1..{MAX_WORKERS} slices, got {len(parts)}")
+    for p in parts:
+        _req(p, torch.int8, "parts")
+    n = parts[0].numel()
+    if any(p.numel() != n for p in parts):
+        raise ValueError("every slice must hold the same number of values")
+    out = torch.empty(n, dtype=torch.int16, device=parts[0].device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int16, "out")
+    _same_device(out, *parts)
+    check(load().ina_sum_i8_slices(_ptrs(parts), len(parts), out.data_ptr(), n, _stream(out)), "i8.sum_slices")
+    return out

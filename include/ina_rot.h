@@ -52,7 +52,8 @@
  * default cap (ina_set_tuning key 0).
  *
  * Not here: the rotation combined with stochastic rounding or error feedback, a base, the sharded wires,
- * the packet path, and V > 256.
+ * the packet path, and V > 256.  A sharded wire that takes the rotation -- 8 bits a value over an
+ * all-to-all -- is in ina_i8.h, which this header includes as its last line.
  */
 #ifndef INA_ROT_H
 #define INA_ROT_H
@@ -81,5 +82,7 @@ int ina_dequantize_rot_i16(const int16_t* sv, const int8_t* kblk, int V, float* 
 /* ina_ps_combine_ina_blk_f32 with the rotation on both sides of the integer sum */
 int ina_ps_combine_ina_rot_f32(const float* local, const float* const* paras, int W, int V, double weight_step,
                                float* out, size_t n, int8_t* kblk_out, const ina_sr_t* sr, ina_stream_t stream);
+
+#include "ina_i8.h" /* an 8-bit wire for sharded buckets: rotated blocks as bytes, byte slices summed to int16 */
 
 #endif /* INA_ROT_H */

@@ -24,7 +24,10 @@
  *     sr == NULL, r = x.
  *   ina_block_scales_i8.  kblk[s] = ina_scale_for_i8(max |r| of block s over the W buffers); an all-zero or
  *     all-NaN block gives 127, a block holding +-inf gives -126.  Ranks agree on the MIN of their scales
- *     before they quantise, as on the other block-scaled wires.
+ *     before they quantise, as on the other block-scaled wires.  With sr != NULL these rules are about the
+ *     rotated values r, as in ina_rot.h: finite inputs whose butterfly overflows give -126 (and clamp, so
+ *     the quantiser raises the block's flag), and an input inf whose r are all NaN no longer decides the
+ *     scale.
  *   ina_quantize_i8_wire.  q8[e] = clamp(rne(r[e] * 2^kblk[e/V]), -127, 127); NaN -> 0; -128 is never
  *     written.  The scales are given (a scale of -127 or -128 is read as -126).  overflow_per_slot may be
  *     NULL; otherwise every block's flag is written: 1 where a value of the block clamped or was NaN, else 0.

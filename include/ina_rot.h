@@ -30,6 +30,10 @@
  *     INA_BLK_AUTO computes kblk[s] in the launch as ina_scale_for(max |r| over the call's W buffers,
  *     degree, bits) and writes it (all zero or all NaN: 127; a block holding +-inf: -126);
  *     ina_block_scales_rot computes the same scales alone, for the MIN agreement between ranks.
+ *     Both rules are about the rotated values r, not the inputs.  The butterfly adds up to V values before
+ *     the normalisation, so a block of finite inputs near the top of the fp32 range has r = +-inf (and NaN
+ *     where inf - inf meets): it gets -126 and, on the int16 side, its flag.  An input +-inf whose r are
+ *     all NaN (inf - inf in every output) counts as all NaN: it no longer decides the scale.
  *   Inverse.  y = float(sum) * 2^-kblk[s]; the same m stages in the same order give u;
  *     xhat = sigma * (u * 2^-floor(m/2)).
  *   PS combine.  ina_ps_combine_ina_rot_f32 is, bit for bit, ina_quantize_reduce_rot_i32 (INA_BLK_AUTO,

@@ -347,12 +347,13 @@ def ops():
 
 
 def dev(a, off=0):
-    """A device copy of a 1-D array / tensor; off = 1: a view one element past a 16-byte boundary."""
+    """A device copy of a 1-D array / tensor; off = 1: a view one element past a 16-byte boundary (off
+    elements in general: 16 bytes' worth is aligned again)."""
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
     buf = torch.empty(t.numel() + off, dtype=t.dtype, device=DEV)
     v = buf[off:]
     v.copy_(t)
-    assert v.data_ptr() % 16 == off * t.element_size()
+    assert v.data_ptr() % 16 == off * t.element_size() % 16
     return v
 
 
@@ -365,7 +366,7 @@ def dev_rows(x, off=0):
     buf = torch.zeros((W, pitch), dtype=t.dtype, device=DEV)
     buf[:, off:off + n].copy_(t)
     rows = [buf[w, off:off + n] for w in range(W)]
-    assert all(r.data_ptr() % 16 == off * t.element_size() and r.is_contiguous() for r in rows)
+    assert all(r.data_ptr() % 16 == off * t.element_size() % 16 and r.is_contiguous() for r in rows)
     return rows
 
 

@@ -128,6 +128,13 @@ inline int check_k(int k) {
     return INA_OK;
 }
 
+// ina_kernels.hip: nbytes of device memory to zero, queued on `s` as a kernel launch.  The entry points
+// that clear overflow flags or an atomic word in front of their kernel use it where they used
+// hipMemsetAsync: a call captured into a hipGraph then records kernel nodes only, which is the form the
+// replay tests (tests/test_gpu_graph_bulk.py) run; a captured memset node is not tested anywhere.
+// Returns the launch's error.
+hipError_t clear_async(void* p, size_t nbytes, hipStream_t s);
+
 // after a launch: INA_OK, or INA_EHIP with "<what>: <the runtime's error string>"
 inline int check_launch(const char* what) {
     const hipError_t e = hipGetLastError();

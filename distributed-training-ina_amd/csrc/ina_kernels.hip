@@ -43,6 +43,17 @@ int set_error(int code, const char* fmt, const char* detail) {
     return code;
 }
 
+// clear_async (ina_internal.h): flags or one atomic word to zero, as a launch on the caller's stream
+__global__ __launch_bounds__(kBlock) void k_clear_bytes(uint8_t* __restrict__ p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) p[i] = 0;
+}
+hipError_t clear_async(void* p, size_t nbytes, hipStream_t s) {
+    if (nbytes == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_clear_bytes, dim3(grid_of(nbytes, 1024)), dim3(kBlock), 0, s, static_cast<uint8_t*>(p),
+                       nbytes);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // tuning (grid cap / unroll), overridable for sweeps through ina_set_tuning()
 // ---------------------------------------------------------------------------
@@ -2272,8 +2283,8 @@ int ina_quantize_f32_i16_sat(const float* x, int16_t* q, size_t n, int k, int V,
         hipLaunchKernelGGL(k_quantize_i16_vec, dim3(grid_for((n + 7) / 8, 1)), dim3(kBlock), 0, s,
                            x, q, n, sc, V, lps, ovf);
     } else {
-        if (ovf && hipMemsetAsync(ovf, 0, (n + V - 1) / V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        if (ovf && clear_async(ovf, (n + V - 1) / V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_quantize_i16_scalar, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, x, q, n,
                            sc, V, ovf);
     }
@@ -2314,8 +2325,8 @@ int ina_sum_reduce_i16_sat(const int16_t* const* bufs, int W, int16_t* out, size
         hipLaunchKernelGGL(k_sum_reduce_i16, dim3(grid_for((n + 7) / 8, 1)), dim3(kBlock), 0, s, pk, W,
                            out, n, V, lps, ovf);
     } else {
-        if (ovf && hipMemsetAsync(ovf, 0, (n + V - 1) / V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        if (ovf && clear_async(ovf, (n + V - 1) / V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_sum_reduce_i16_scalar, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, pk, W,
                            out, n, V, ovf);
     }
@@ -2371,8 +2382,8 @@ int ina_quantize_reduce_f32_i16_sat(const float* const* bufs, int W, int16_t* ou
             default: hipLaunchKernelGGL(k_quant_reduce_i16<0>, dim3(g), dim3(kBlock), 0, s, pk, W, out, n, sc, V, lps, ovf);
         }
     } else {
-        if (ovf && hipMemsetAsync(ovf, 0, (n + V - 1) / V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        if (ovf && clear_async(ovf, (n + V - 1) / V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_quant_reduce_i16_scalar, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, pk, W,
                            out, n, sc, V, ovf);
     }
@@ -2919,8 +2930,8 @@ int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id, uint3
 int ina_absmax_f32(const float* x, const float* base, size_t n, float* out_dev, ina_stream_t stream) {
     if (!out_dev) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
-    if (hipMemsetAsync(out_dev, 0, sizeof(float), s) != hipSuccess)
-        return set_error(INA_EHIP, "memset absmax%s", "");
+    if (clear_async(out_dev, sizeof(float), s) != hipSuccess)
+        return set_error(INA_EHIP, "clear absmax%s", "");
     if (n == 0) return INA_OK;
     if (!x) return set_error(INA_EINVAL, "null pointer%s", "");
     const int vec = aligned16(x) && (!base || aligned16(base));
@@ -2940,8 +2951,8 @@ int ina_absmax_multi_f32(const float* const* xs, int W, const float* base, size_
     bool al;
     if (int rc = fill_pack(pk, xs, W, al)) return rc;
     hipStream_t s = hs(stream);
-    if (hipMemsetAsync(out_dev, 0, sizeof(float), s) != hipSuccess)
-        return set_error(INA_EHIP, "memset absmax%s", "");
+    if (clear_async(out_dev, sizeof(float), s) != hipSuccess)
+        return set_error(INA_EHIP, "clear absmax%s", "");
     if (n == 0) return INA_OK;
     const int vec = al && (!base || aligned16(base));
     hipLaunchKernelGGL(k_absmax_multi_f32, dim3(grid_for(vec ? n / 4 + 1 : n, 1, kAbsmaxMultiBlocks)),
@@ -2984,8 +2995,8 @@ extern "C" {
 int ina_checksum_i32(const int32_t* x, size_t n, uint32_t* out_dev, ina_stream_t stream) {
     if (!out_dev) return set_error(INA_EINVAL, "null out%s", "");
     hipStream_t s = hs(stream);
-    if (hipMemsetAsync(out_dev, 0, sizeof(uint32_t), s) != hipSuccess)
-        return set_error(INA_EHIP, "memset checksum%s", "");
+    if (clear_async(out_dev, sizeof(uint32_t), s) != hipSuccess)
+        return set_error(INA_EHIP, "clear checksum%s", "");
     if (n == 0) return INA_OK;
     if (!x) return set_error(INA_EINVAL, "null pointer%s", "");
     int vec = aligned16(x);

@@ -184,8 +184,8 @@ int launch_i16(const PtrPack<X>& pk, int W, int16_t* out, size_t n, int k, int V
             default: hipLaunchKernelGGL((k_qr_sr_i16_vec<X, 0>), g, b, 0, s, pk, W, out, n, sc, V, ovf, a);
         }
     } else {
-        if (ovf && hipMemsetAsync(ovf, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        if (ovf && clear_async(ovf, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_qr_sr_i16_scalar<X>, dim3(grid_of(n, default_grid_cap())), dim3(kBlk), 0, s, pk, W, out, n,
                            sc, V, ovf, a);
     }

@@ -300,8 +300,8 @@ int launch_wire_finish(const int32_t* wire_sum, size_t n, int k, int V, int16_t*
                            inv, ballot ? l : 1, V, out16, y, overflow_per_slot);
     } else {
         if (overflow_per_slot &&
-            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+            clear_async(overflow_per_slot, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_i16_wire_finish_scalar<Y>, dim3(grid_of(n, cap)), dim3(kBlk), 0, s, wire_sum, n, inv, V,
                            out16, y, overflow_per_slot);
     }
@@ -332,8 +332,8 @@ int launch_wire_finish_blk(const int32_t* wire_sum, size_t n, const int8_t* kblk
                            n, kblk, shift, out16, y, overflow_per_slot);
     } else {
         if (overflow_per_slot &&
-            hipMemsetAsync(overflow_per_slot, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+            clear_async(overflow_per_slot, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_i16_wire_finish_blk_scalar<Y>, dim3(grid_of(n, cap)), dim3(kBlk), 0, s, wire_sum, n,
                            kblk, V, out16, y, overflow_per_slot);
     }

@@ -144,8 +144,8 @@ int launch_i16(const X* x, const float* base, int16_t* q, size_t n, int k, int V
         hipLaunchKernelGGL(k_sr_i16_vec<X>, dim3(grid_of((n + 511) / 512 * 64, default_grid_cap())), dim3(kBlk), 0, s, x,
                            base, q, n, sc, V, ovf, a);
     } else {
-        if (ovf && hipMemsetAsync(ovf, 0, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        if (ovf && clear_async(ovf, (n + (size_t)V - 1) / (size_t)V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         hipLaunchKernelGGL(k_sr_i16_scalar<X>, dim3(grid_of(n, default_grid_cap())), dim3(kBlk), 0, s, x, base, q, n, sc,
                            V, ovf, a);
     }

@@ -286,8 +286,8 @@ int reduce_i16(const void* const* bufs, int xtype, int W, int16_t* out, size_t n
             default: INA_X16_LAUNCH_W(xtype, k_quant_reduce_x16_i16, 0, g, b, 0, s, pk, W, out, n, sc, V, lps, ovf);
         }
     } else {
-        if (ovf && hipMemsetAsync(ovf, 0, (n + V - 1) / V, s) != hipSuccess)
-            return set_error(INA_EHIP, "memset overflow flags%s", "");
+        if (ovf && clear_async(ovf, (n + V - 1) / V, s) != hipSuccess)
+            return set_error(INA_EHIP, "clear overflow flags%s", "");
         INA_X16_LAUNCH(xtype, k_quant_reduce_x16_i16_scalar, dim3(grid_of(n, default_grid_cap())), dim3(kBlk), 0, s,
                        pk, W, out, n, sc, V, ovf);
     }
@@ -370,8 +370,8 @@ int ina_absmax_multi_x16(const void* const* xs, int xtype, int W, const float* b
     bool al;
     if (int rc = fill_pack(pk, xs, W, al)) return rc;
     hipStream_t s = hs(stream);
-    if (hipMemsetAsync(out_dev, 0, sizeof(float), s) != hipSuccess)
-        return set_error(INA_EHIP, "memset absmax%s", "");
+    if (clear_async(out_dev, sizeof(float), s) != hipSuccess)
+        return set_error(INA_EHIP, "clear absmax%s", "");
     if (n == 0) return INA_OK;
     const int vec = al && (!base || aligned16(base));
     // every block ends in one atomicMax on the same word, so the grid stays small (the

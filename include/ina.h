@@ -323,7 +323,13 @@ int ina_pack_c128(const uint32_t* gradient, int packet_num, int worker_id,
  * word a call reads it has written itself, or it is tagged with the call's epoch (never 0)
  * after the call cleared the tag.  Only which sort path a batch takes may: a batch in slot
  * order is sorted needlessly if the one "descent found" word held this call's epoch on
- * entry (ina_switch_batch_path then says so). */
+ * entry (ina_switch_batch_path then says so).
+ * Captured into a hipGraph, a call freezes what the host read when it was made: the epoch, the
+ * tuning (ina_set_tuning) and the plan.  Every replay then runs under the same epoch and meets
+ * the previous replay's tags: after one replay out of slot order the "descent found" word stays
+ * this epoch's, and a later batch in slot order of that graph no longer reports
+ * INA_PATH_IN_ORDER (it takes the near-sorted lists, INA_PATH_LOCAL, where they apply, else the
+ * sort).  Results are the same on every path. */
 typedef struct ina_switch_state {
     uint32_t num_slots;
     int32_t V;
@@ -365,9 +371,13 @@ typedef struct ina_switch_batch {
  * acks in front of the next step's packets -- is sorted without a gather pass.  The step always
  * runs fused in the switch's run kernel (the layouts below are the ones it takes; others are
  * refused before the switch touches its state).  keep_forwarded = 0: completed packets are
- * consumed and their buffers left as they arrived.  Replaces the Tofino -> PS hop of ngaa.p4:170-175 +
- * NGAPacket.py:62-143 + launch.py:42-52 when both live on the GPU.  16-byte aligned local,
- * out, rows and registers; V % 4 == 0. */
+ * consumed and their buffers left as they arrived.  A slot that completes more than once in one
+ * batch (mixed degrees: a packet whose count is already met, then the others) is written by each
+ * of its completions in no order: what out[slot*V ..] and the slot's ack row then hold is
+ * unspecified and can differ from run to run, as after ina_apply_completed_nga over such a batch.
+ * Workers of one job send one degree, so a slot completes once a batch.  Replaces the Tofino ->
+ * PS hop of ngaa.p4:170-175 + NGAPacket.py:62-143 + launch.py:42-52 when both live on the GPU.
+ * 16-byte aligned local, out, rows and registers; V % 4 == 0. */
 typedef struct ina_switch_ps {
     uint32_t seq0;
     int k;

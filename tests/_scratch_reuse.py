@@ -45,14 +45,65 @@ def host(t):
     return t.cpu().numpy()
 
 
-def make_batch(rng, kind, V, per, seq0, num_slots, stride):
-    """W = 8 senders x `per` slots from seq0 on, arriving as `kind` says."""
+def make_batch(rng, kind, V, per, seq0, num_slots, stride, senders=W):
+    """`senders` (W = 8) senders x `per` slots from seq0 on, arriving as `kind` says."""
     if kind in ("runs", "runs_acks"):
-        return runs_batch(rng, V, worker_major(W, per, seq0, acks=kind == "runs_acks"), W, stride,
+        return runs_batch(rng, V, worker_major(senders, per, seq0, acks=kind == "runs_acks"), senders, stride,
                           num_slots=num_slots)
     J = {"in_order": 0, "near40": 40, "near1500": 1500, "shuffled": 1 << 30, "digits": 1 << 30,
          "one_wg": 40, "tiny": 40}[kind]
-    return rr_batch(rng, V, W, per, seq0, num_slots, stride, J)
+    return rr_batch(rng, V, senders, per, seq0, num_slots, stride, J)
+
+
+# ---- the replay sequences of tests/test_gpu_graph_switch.py -----------------------------------
+REPLAY_KINDS = ("in_order", "runs", "runs_acks", "near40", "near1500", "shuffled")
+DIGIT_KINDS = ("in_order", "shuffled", "near40")  # the graph captured under the digit passes
+REPLAY_PER, REPLAY_SEQ0 = 2000, 1                 # 8 x 2,000 = 16,000 rows, every batch of every graph
+
+
+def replay_kinds(seed, kinds=REPLAY_KINDS):
+    """A seeded walk over `kinds` that starts with kinds[0] and holds every ordered pair of kinds, a kind
+    followed by itself included, exactly once: an Euler circuit of the complete digraph with loops
+    (Hierholzer), len(kinds)^2 + 1 entries -- 37 for the six kinds."""
+    rng = np.random.default_rng(seed)
+    nxt = {a: [kinds[i] for i in rng.permutation(len(kinds))] for a in kinds}
+    stack, walk = [kinds[0]], []
+    while stack:
+        if nxt[stack[-1]]:
+            stack.append(nxt[stack[-1]].pop())
+        else:
+            walk.append(stack.pop())
+    return walk[::-1]
+
+
+def replay_batch(rng, kind, V, num_slots, stride):
+    """One batch of a replay sequence: 16,000 rows whatever the kind (an ack run in front takes the place
+    of one sender)."""
+    return make_batch(rng, kind, V, REPLAY_PER, REPLAY_SEQ0, num_slots, stride,
+                      senders=W - 1 if kind == "runs_acks" else W)
+
+
+_REPLAY = {}
+
+
+def replay_reference(num_slots, V, kinds=REPLAY_KINDS, stride=None):
+    """The sequence's batches and the oracle's results with state carried from batch to batch, computed once
+    per (pool, V, kinds): [(kind, rows, want rows, want actions, registers of slots [0, hi) after it)], the
+    oracle (its final state), hi."""
+    key = (num_slots, V, kinds)
+    if key not in _REPLAY:
+        stride = stride or (15 + 4 * V + 15) // 16 * 16
+        rng = np.random.default_rng(11 + num_slots % 977 + V + len(kinds))
+        ref = orc.Switch(V, num_slots=num_slots, switch_id=1)
+        hi = 1 << 12
+        assert REPLAY_SEQ0 + REPLAY_PER <= hi <= num_slots
+        steps = []
+        for kind in replay_kinds(2000 + num_slots % 991 + len(kinds), kinds):
+            pk = replay_batch(rng, kind, V, num_slots, stride)
+            want_pk, want_act = ref.run(pk, stride=stride)
+            steps.append((kind, pk, want_pk, want_act, tuple(x[:hi].copy() for x in reg_views(ref))))
+        _REPLAY[key] = (steps, ref, hi)
+    return _REPLAY[key]
 
 
 def expected_paths(pk, num_slots, kind, per, seq0):

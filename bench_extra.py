@@ -704,6 +704,50 @@ def run_i8(dev):
     return rows
 
 
+def run_i8_gather(dev):
+    """The requantised 8-bit gather (include/ina_i8_gather.h) at the ResNet-50 size (rounded down to a multiple of
+    256), cold caches, median of 20, the set twice in this process (run 1 / run 2).  Bars, each the parent's own
+    kernel timed twice in the same process (its faster time plus the spread of the two): i8.sum_slices_requant at
+    G = 8 and 64, V = 256 and 32, against i8.sum_slices at the same G, which writes one byte a value more; the
+    rotated decode against rot.dequantize from int16 at the same V, and the plain one against blk.dequantize
+    from int16, which read one byte a value more.  Nothing is gated here; DESIGN 4.1q reads the rows."""
+    from ina_amd import blk, i8, rot
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(53)
+    n, seed = 25_557_032 // 256 * 256, 0x1234
+    parts = [torch.randint(-128, 128, (n,), dtype=torch.int8, device=dev, generator=gen) for _ in range(64)]
+    q8 = torch.empty(n, dtype=torch.int8, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    y = torch.empty(n, device=dev)
+
+    def row(run, name, nbytes, f_new, f_bar, bar_name):
+        ta, tn, tb = _time(f_bar), _time(f_new), _time(f_bar)
+        lo, spread = min(ta, tb), abs(ta - tb)
+        rows.append(_row(f"{name} [i8 gather, run {run}]", tn, nbytes, bar=bar_name,
+                         bar_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], bar_spread_us=round(spread * 1e6, 2),
+                         over_bar=round(tn / lo, 3), bar_met=bool(tn <= lo + spread)))
+
+    for run in (1, 2):
+        for V in (256, 32):
+            nblk = n // V
+            sh = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            kb = torch.randint(8, 12, (nblk,), dtype=torch.int8, device=dev, generator=gen)
+            for G in (8, 64):
+                row(run, f"sum_slices_requant G={G} V={V}", (G + 1) * n + nblk,
+                    lambda: i8.sum_slices_requant(parts[:G], V, out=q8, shift=sh),
+                    lambda: i8.sum_slices(parts[:G], out=o16), f"i8.sum_slices G={G}")
+            i8.sum_slices(parts[:8], out=o16)            # the decodes read the G = 8 sums, as bytes and as int16
+            i8.sum_slices_requant(parts[:8], V, out=q8, shift=sh)
+            row(run, f"dequantize_gather V={V} rot", 5 * n + 2 * nblk,
+                lambda: i8.dequantize_gather(q8, sh, kb, V, rotate=seed, step=run, out=y),
+                lambda: rot.dequantize(o16, kb, V, seed, step=run, out=y), "rot.dequantize i16")
+            row(run, f"dequantize_gather V={V} plain", 5 * n + 2 * nblk,
+                lambda: i8.dequantize_gather(q8, sh, kb, V, out=y),
+                lambda: blk.dequantize(o16, kb, V, out=y), "blk.dequantize i16")
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1405,6 +1449,7 @@ def run_extra(dev):
     rows += run_blk_sr(dev)
     rows += run_rot(dev)
     rows += run_i8(dev)
+    rows += run_i8_gather(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

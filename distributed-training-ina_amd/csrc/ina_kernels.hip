@@ -3019,7 +3019,8 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     if (hipDeviceSynchronize() != hipSuccess) return INA_EHIP;
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
              ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_sr() +
-             ina::store_violations_reduce_sr() + ina::store_violations_rot() + ina::store_violations_i8();
+             ina::store_violations_reduce_sr() + ina::store_violations_rot() + ina::store_violations_i8() +
+             ina::store_violations_i8g();
     return INA_OK;
 }
 #endif

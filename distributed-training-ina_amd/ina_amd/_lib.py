@@ -262,6 +262,12 @@ SIGNATURES_I8 = {
     "ina_quantize_i8_wire": [_vp, _i, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
     "ina_sum_i8_slices": [_vp, _i, _vp, _sz, _vp],
 }
+# the requantised 8-bit gather of that wire (include/ina_i8_gather.h): the slice sum rounded to bytes under
+# per-block shifts, and the decode of those bytes (the ina_sr_t, NULL: no rotation, precedes the stream)
+SIGNATURES_I8G = {
+    "ina_sum_i8_slices_requant": [_vp, _i, _i, _vp, _vp, _sz, _vp],
+    "ina_dequantize_i8_gather": [_vp, _vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -280,7 +286,7 @@ def open_library(path: str) -> C.CDLL:
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
                        **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR,
-                       **SIGNATURES_ROT, **SIGNATURES_I8}.items():
+                       **SIGNATURES_ROT, **SIGNATURES_I8, **SIGNATURES_I8G}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -954,11 +954,22 @@ class ByteWireAggregator:
     `gather_bytes` and `scale_bytes` are what one step brings to each rank over the links: (G-1) x shard x 1,
     (G-1) x shard x 2, and one byte per block.  Shards are aligned to the lcm of `align`, V and 128, so every
     shard starts where a rotated call may start (e0).  No chunks, no error feedback, no stochastic rounding,
-    no layout B."""
+    no layout B.
+    gather="i16" (default) is the step above.  gather="i8" (include/ina_i8_gather.h) takes the second byte off
+    the gather: i8.sum_slices_requant sums the received slices and rounds each block of sums to bytes under a
+    per-block shift in one launch, into the int8 `q8_shard` and the uint8 `shift_shard`; all_gather_shards
+    moves both (into `q8_full` and `gather_shift`, the last call's shifts, one per block); i8.dequantize_gather
+    decodes the bytes on every rank.  `gather_bytes` is then (G-1) x shard x (1 + 1/V), and a step is 1 + 1
+    bytes a value where the default is 1 + 2.  The price is the requantiser's half of 2^shift summand quanta
+    on top of the G halves (DESIGN 4.1q has the measured error); a block whose sums stay within +-127 has
+    shift 0 and decodes as under "i16", bit for bit.  The pad's bytes are zero, so its blocks' shifts are 0."""
 
     def __init__(self, n: int, V: int = 256, group=None, device=None, align: int = 1024, rotate: bool = True,
-                 seed: int = 0):
+                 seed: int = 0, gather: str = "i16"):
         self.seed = _check_seed(seed)
+        if gather not in ("i16", "i8"):
+            raise ValueError(f"gather must be 'i16' or 'i8', got {gather!r}")
+        self.gather = gather
         V = int(V)
         if V < 8 or V > 256 or V & (V - 1):
             raise ValueError(f"V must be a power of two in [8, 256], got {V}")
@@ -977,8 +988,14 @@ class ByteWireAggregator:
         self._kbuf = torch.full((nblk,), 127, dtype=torch.int8, device=dev)
         self._obuf = torch.zeros(nblk, dtype=torch.uint8, device=dev)
         self._recv = torch.empty(tot, dtype=torch.int8, device=dev) if self.world > 1 else None
-        self.s16_shard = torch.empty(self.plan.shard, dtype=torch.int16, device=dev)
-        self.s16_full = torch.empty(tot, dtype=torch.int16, device=dev)
+        if gather == "i16":
+            self.s16_shard = torch.empty(self.plan.shard, dtype=torch.int16, device=dev)
+            self.s16_full = torch.empty(tot, dtype=torch.int16, device=dev)
+        else:
+            self.q8_shard = torch.empty(self.plan.shard, dtype=torch.int8, device=dev)
+            self.shift_shard = torch.empty(self.plan.shard // V, dtype=torch.uint8, device=dev)
+            self.q8_full = torch.empty(tot, dtype=torch.int8, device=dev)
+            self._sbuf = torch.zeros(nblk, dtype=torch.uint8, device=dev)
         self.full = torch.empty(tot, dtype=torch.float32, device=dev)
         self._stage = None           # rotate=False with n % V: the bucket padded with zeros to whole blocks
 
@@ -995,6 +1012,11 @@ class ByteWireAggregator:
         return self._obuf[: -(-self.plan.n // self.V)]
 
     @property
+    def gather_shift(self) -> torch.Tensor:
+        """The requantiser's shifts of the last call under gather="i8" (ceil(n / V) bytes)."""
+        return self._sbuf[: -(-self.plan.n // self.V)]
+
+    @property
     def scale_bytes(self) -> int:
         return -(-self.plan.n // self.V) if self.world > 1 else 0
 
@@ -1005,7 +1027,10 @@ class ByteWireAggregator:
 
     @property
     def gather_bytes(self) -> int:
-        """Bytes the all-gather brings to each rank: the other shards' int16 sums."""
+        """Bytes the all-gather brings to each rank: the other shards' int16 sums, or under gather="i8" their
+        bytes and one shift per block."""
+        if self.gather == "i8":
+            return (self.world - 1) * (self.plan.shard + self.plan.shard // self.V)
         return (self.world - 1) * self.plan.shard * 2
 
     def _bucket(self, grad: torch.Tensor) -> torch.Tensor:
@@ -1042,6 +1067,13 @@ class ByteWireAggregator:
         i8.block_scales([x], V, out=kb, **key)
         agree_block_scales(kb, self.group)
         i8.quantize(x, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
+        if self.gather == "i8":
+            i8.sum_slices_requant(self._exchange(), V, out=self.q8_shard, shift=self.shift_shard)
+            all_gather_shards(self.q8_shard, self.plan, self.group, out=self.q8_full)
+            all_gather_shards(self.shift_shard, self.plan, self.group, out=self._sbuf)
+            i8.dequantize_gather(self.q8_full, self._sbuf, self._kbuf, V, out=self.full, **key)
+            self._step = (self._step + 1) & 0xFFFFFFFF
+            return self.full[: self.plan.n]
         i8.sum_slices(self._exchange(), out=self.s16_shard)
         all_gather_shards(self.s16_shard, self.plan, self.group, out=self.s16_full)
         if self.rotate:

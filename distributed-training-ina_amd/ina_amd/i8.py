@@ -11,6 +11,13 @@ dist.ByteWireAggregator runs the step; tests/_i8_ref.py replays the contract.
     s16 = i8.sum_slices(received)                                   # int16, exact
     g = rot.dequantize(gathered, kblk, V, seed, step=t)
 
+The gather may carry bytes instead of the int16 sums (include/ina_i8_gather.h; ByteWireAggregator(gather="i8")):
+the owner rounds each block of its sums back to bytes under a per-block shift in the launch that sums them, and
+the decode reads those bytes -- one byte a value more off the links, half of 2^shift summand quanta more error.
+
+    q8s, sh = i8.sum_slices_requant(received, V)                    # int8 + one uint8 shift a block
+    g = i8.dequantize_gather(gathered, shifts, kblk, V, rotate=seed, step=t)
+
 `rotate` is None (no rotation) or the seed.  n must be a multiple of V for the block calls, buffers 16-byte
 aligned, e0 a multiple of 128 and of V; no base; no CPU fallback and no value-by-value path.
 """
@@ -72,8 +79,8 @@ def quantize(x: torch.Tensor, kblk: torch.Tensor, V: int, rotate: int | None = N
     return out, overflow
 
 
-def sum_slices(parts, out: torch.Tensor | None = None) -> torch.Tensor:
-    """int16 [n]: the exact element-wise sum of 1..64 int8 slices of n values each (any n)."""
+def _slices(parts):
+    """The 1..64 int8 slices of a sum, of one length: (list, n)."""
     parts = list(parts.unbind(0)) if isinstance(parts, torch.Tensor) and parts.dim() > 1 else list(parts)
     if not 1 <= len(parts) <= MAX_WORKERS:
         raise ValueError(f"1..{MAX_WORKERS} slices, got {len(parts)}")
@@ -82,9 +89,53 @@ def sum_slices(parts, out: torch.Tensor | None = None) -> torch.Tensor:
     n = parts[0].numel()
     if any(p.numel() != n for p in parts):
         raise ValueError("every slice must hold the same number of values")
+    return parts, n
+
+
+def sum_slices(parts, out: torch.Tensor | None = None) -> torch.Tensor:
+    """int16 [n]: the exact element-wise sum of 1..64 int8 slices of n values each (any n)."""
+    parts, n = _slices(parts)
     out = torch.empty(n, dtype=torch.int16, device=parts[0].device) if out is None else out
     _fits(out, n)
     _req(out, torch.int16, "out")
     _same_device(out, *parts)
     check(load().ina_sum_i8_slices(_ptrs(parts), len(parts), out.data_ptr(), n, _stream(out)), "i8.sum_slices")
+    return out
+
+
+def sum_slices_requant(parts, V: int, out: torch.Tensor | None = None, shift: torch.Tensor | None = None):
+    """(int8 [n], uint8 [n / V]): the exact sum of 1..64 int8 slices, each block of V sums rounded to nearest
+    even under the block's shift -- the smallest in [0, 7] that brings its largest |sum| to at most 127 -- in
+    one launch (include/ina_i8_gather.h).  The sum is about q8 * 2^shift; -128 is never written."""
+    parts, n = _slices(parts)
+    V = _v(V, n)
+    out = torch.empty(n, dtype=torch.int8, device=parts[0].device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int8, "out")
+    shift = torch.empty(n // V, dtype=torch.uint8, device=out.device) if shift is None else shift
+    _fits(shift, n // V, "shift")
+    _req(shift, torch.uint8, "shift")
+    _same_device(out, shift, *parts)
+    check(load().ina_sum_i8_slices_requant(_ptrs(parts), len(parts), V, out.data_ptr(), shift.data_ptr(), n,
+                                           _stream(out)), "i8.sum_slices_requant")
+    return out, shift
+
+
+def dequantize_gather(q8: torch.Tensor, shift: torch.Tensor, kblk: torch.Tensor, V: int, rotate: int | None = None,
+                      step: int = 0, sub: int = 0, e0: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """float32: bit for bit rot.dequantize (rotate=seed) or blk.dequantize (rotate=None) of the int16 values
+    q8 << shift[block], read from the bytes.  A shift above 7 is read as 7."""
+    _req(q8, torch.int8, "q8")
+    n = q8.numel()
+    V = _v(V, n)
+    prm = _sr(rotate, step, sub, e0, V)
+    _req(shift, torch.uint8, "shift")
+    _fits(shift, n // V, "shift")
+    kblk = _blk_scales_arg(kblk, n // V, q8, given=True)
+    out = torch.empty(q8.shape, dtype=torch.float32, device=q8.device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.float32, "out")
+    _same_device(q8, shift, out)
+    check(load().ina_dequantize_i8_gather(q8.data_ptr(), shift.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), n,
+                                          prm, _stream(q8)), "i8.dequantize_gather")
     return out

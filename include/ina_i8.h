@@ -57,7 +57,9 @@
  * int16.  Every grid is under the default cap (ina_set_tuning key 0).
  *
  * Not here: stochastic rounding and error feedback on this wire, a base, layout B, the packet path, a
- * pipelined step (chunks > 1), a requantised 8-bit gather, and bench.py.
+ * pipelined step (chunks > 1), a requantised 8-bit gather, and bench.py.  The requantised gather -- the sums
+ * rounded back to bytes under a per-block shift, and a decode that reads them -- is in ina_i8_gather.h, which
+ * this header includes as its last line.
  */
 #ifndef INA_I8_H
 #define INA_I8_H
@@ -75,5 +77,7 @@ int ina_quantize_i8_wire(const void* x, int xtype, const int8_t* kblk, int V, in
                          uint8_t* overflow_per_slot, const ina_sr_t* sr, ina_stream_t stream);
 /* the exact sum of G byte slices into int16 */
 int ina_sum_i8_slices(const int8_t* const* slices, int G, int16_t* out16, size_t n, ina_stream_t stream);
+
+#include "ina_i8_gather.h" /* a requantised 8-bit gather: the slice sums as bytes under per-block shifts */
 
 #endif /* INA_I8_H */

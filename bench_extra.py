@@ -748,6 +748,46 @@ def run_i8_gather(dev):
     return rows
 
 
+def run_i8_ef(dev):
+    """Error feedback on the 8-bit wire (include/ina_i8_ef.h) at the ResNet-50 size (rounded down to a multiple of
+    256), cold caches, median of 20, the set twice in this process (run 1 / run 2): the rotated i8.quantize_ef on
+    fp32 and bf16 buckets at V = 256 and 32 beside (a) the plain i8.quantize row and (b) the composition from the
+    parent's ops, each of its five launches behind its own flush -- torch.add into a temporary, i8.quantize,
+    i8.sum_slices of the one slice, rot.dequantize, torch.sub into the residual: 38 bytes a value against 13.  The bar: the one launch takes at most two thirds of (b).  Nothing is gated here; DESIGN 4.1r reads the
+    rows."""
+    from ina_amd import i8, rot
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(59)
+    n, seed = 25_557_032 // 256 * 256, 0x1234
+    x32 = torch.randn(n, device=dev, generator=gen) * 1e-2
+    res, tmp, y = torch.zeros(n, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
+    q8 = torch.empty(n, dtype=torch.int8, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+    for run in (1, 2):
+        for V in (256, 32):
+            ovf = torch.empty(n // V, dtype=torch.uint8, device=dev)
+            for x, tag in ((x32, "f32"), (x32.to(torch.bfloat16), "bf16")):
+                b, key = x.element_size(), dict(rotate=seed, step=run)
+                res.zero_()
+                kb = i8.block_scales_ef([x], [res], V, **key)
+                steps = (lambda: torch.add(x, res, out=tmp),
+                         lambda: i8.quantize(tmp, kb, V, out=q8, overflow=ovf, **key),
+                         lambda: i8.sum_slices([q8], out=o16),
+                         lambda: rot.dequantize(o16, kb, V, seed, step=run, out=y),
+                         lambda: torch.sub(tmp, y, out=res))
+                t_q = _time(lambda: i8.quantize(x, kb, V, out=q8, overflow=ovf, **key))
+                t_new = _time(lambda: i8.quantize_ef(x, res, kb, V, out=q8, overflow=ovf, **key))
+                t_steps = [_time(f) for f in steps]
+                rows.append(_row(f"quantize_ef {tag}->i8 V={V} rot [i8 ef, run {run}]", t_new, (b + 9) * n + 2 * (n // V),
+                                 quantize_us=round(t_q * 1e6, 2),
+                                 quantize_GBps=round(((b + 1) * n + 2 * (n // V)) / t_q / 1e9, 1),
+                                 composed_us=[round(t * 1e6, 2) for t in t_steps],
+                                 over_composed=round(t_new / sum(t_steps), 3),
+                                 bar_met=bool(t_new <= 2 / 3 * sum(t_steps))))
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1450,6 +1490,7 @@ def run_extra(dev):
     rows += run_rot(dev)
     rows += run_i8(dev)
     rows += run_i8_gather(dev)
+    rows += run_i8_ef(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

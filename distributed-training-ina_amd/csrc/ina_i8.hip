@@ -28,18 +28,12 @@
 #include "ina_device.h"
 #include "ina_chunk.h"
 #include "ina_rot_device.h"
+#include "ina_i8_device.h"
 
 namespace ina {
 namespace {
 
 constexpr int kBlk = 256;
-constexpr double kLimI8 = 126.5;   // ina_scale_for_i8: absmax * 2^k + 1/2 <= 127
-
-// chunk i = values 4i..4i+3; base_ is the wave's first chunk (a multiple of 64)
-#define INA_I8_QUAD_LOOP(nq)                                     \
-    const size_t tid_ = (size_t)blockIdx.x * kBlk + threadIdx.x; \
-    const size_t stride_ = (size_t)gridDim.x * kBlk;             \
-    for (size_t base_ = tid_ & ~(size_t)63; base_ < (nq); base_ += stride_)
 
 // r of the contract for the lane's chunk
 template <bool ROT>
@@ -71,21 +65,6 @@ __global__ __launch_bounds__(kBlk) void k_i8_scales(PtrPack<X> xs, int W, size_t
         m = group_max(m, 1 << shift);
         if (e < n && (lane & ((1 << shift) - 1)) == 0) kblk[i >> shift] = (int8_t)scale_of(m, lim);
     }
-}
-
-// clamp(rne(v * s), -127, 127) of 4 values as 4 bytes, the first in the low byte; NaN -> 0; sat |= clamped or
-// NaN
-__device__ __forceinline__ int q8_of(float y, bool& sat) {
-    const float c = __builtin_amdgcn_fmed3f(y, -127.0f, 127.0f);       // one v_med3_f32
-    sat |= !(c == y);
-    return (y != y) ? 0 : (int)c;
-}
-__device__ __forceinline__ uint32_t q8x4(f32x4 v, float s, bool& sat) {
-    const int a = q8_of(__builtin_rintf(__fmul_rn(v.x, s)), sat), b = q8_of(__builtin_rintf(__fmul_rn(v.y, s)), sat);
-    const int c = q8_of(__builtin_rintf(__fmul_rn(v.z, s)), sat), d = q8_of(__builtin_rintf(__fmul_rn(v.w, s)), sat);
-    const uint32_t lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(a, b));
-    const uint32_t hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(c, d));
-    return __builtin_amdgcn_perm(hi, lo, 0x06040200u);                 // the low byte of each int16
 }
 
 template <typename X, bool ROT>
@@ -170,28 +149,6 @@ __global__ __launch_bounds__(kBlk) void k_sum_i8(PtrPack<int8_t> in, int Gd, int
 // host side
 // ---------------------------------------------------------------------------
 int launched() { return check_launch("int8 wire kernel launch"); }
-
-using bf16_t = h16<INA_X16_BF16>;
-using fp16_t = h16<INA_X16_F16>;
-
-int check_xtype(int xtype) {
-    if (xtype == INA_ROT_F32 || xtype == INA_X16_BF16 || xtype == INA_X16_F16) return INA_OK;
-    return set_error(INA_EINVAL, "xtype must be INA_ROT_F32 (0), INA_X16_BF16 (1) or INA_X16_F16 (2)%s", "");
-}
-int misaligned() { return set_error(INA_EINVAL, "buffers must be 16-byte aligned%s", ""); }
-
-// the block calls' checks up to n == 0, in the header's order; shift = log2(V) - 2
-int check_blocks(int V, const int8_t* kblk, size_t n, int& shift) {
-    if (!vec_v(V, shift)) return set_error(INA_EINVAL, "V must be a power of two in [8, 256]%s", "");
-    if (!kblk) return set_error(INA_EINVAL, "null kblk%s", "");
-    if (n % (size_t)V) return set_error(INA_EINVAL, "n must be a multiple of V%s", "");
-    return INA_OK;
-}
-
-#define INA_I8_X_CALL(xtype, F, ...)                           \
-    ((xtype) == INA_X16_BF16  ? F<bf16_t>(__VA_ARGS__)         \
-     : (xtype) == INA_X16_F16 ? F<fp16_t>(__VA_ARGS__)         \
-                              : F<float>(__VA_ARGS__))
 
 template <typename X>
 int block_scales(const void* const* xs, int W, size_t n, int V, int8_t* kblk, const ina_sr_t* sr, ina_stream_t stream) {

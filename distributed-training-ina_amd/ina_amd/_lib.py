@@ -268,6 +268,12 @@ SIGNATURES_I8G = {
     "ina_sum_i8_slices_requant": [_vp, _i, _i, _vp, _vp, _sz, _vp],
     "ina_dequantize_i8_gather": [_vp, _vp, _vp, _i, _vp, _sz, C.POINTER(SrParams), _vp],
 }
+# error feedback on that wire (include/ina_i8_ef.h): the residual(s) follow the bucket(s) -- after the type code
+# in the quantiser, before it in the scales call
+SIGNATURES_I8_EF = {
+    "ina_block_scales_i8_ef": [_vp, _vp, _i, _i, _sz, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_ef_i8_wire": [_vp, _i, _vp, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -286,7 +292,7 @@ def open_library(path: str) -> C.CDLL:
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
                        **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR,
-                       **SIGNATURES_ROT, **SIGNATURES_I8, **SIGNATURES_I8G}.items():
+                       **SIGNATURES_ROT, **SIGNATURES_I8, **SIGNATURES_I8G, **SIGNATURES_I8_EF}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -953,8 +953,13 @@ class ByteWireAggregator:
     of the block clamped at +-127 under the agreed scale or was NaN; rank-local, never sent).  `wire_bytes`,
     `gather_bytes` and `scale_bytes` are what one step brings to each rank over the links: (G-1) x shard x 1,
     (G-1) x shard x 2, and one byte per block.  Shards are aligned to the lcm of `align`, V and 128, so every
-    shard starts where a rotated call may start (e0).  No chunks, no error feedback, no stochastic rounding,
-    no layout B.
+    shard starts where a rotated call may start (e0).  No chunks, no stochastic rounding, no layout B.
+    error_feedback=True (include/ina_i8_ef.h) keeps what this rank's bytes dropped: the aggregator owns one fp32
+    residual of the padded size on its device, i8.block_scales_ef and i8.quantize_ef take the place of
+    i8.block_scales and i8.quantize -- the residual is added in front of the rotation and rewritten, in the
+    quantiser's launch, with the rounding error taken back through the inverse rotation -- and everything else
+    of the step, every byte on the links included, is as above.  `residual` is its first n values and
+    reset_residual() clears it; it never leaves the rank.  The default is no error feedback.
     gather="i16" (default) is the step above.  gather="i8" (include/ina_i8_gather.h) takes the second byte off
     the gather: i8.sum_slices_requant sums the received slices and rounds each block of sums to bytes under a
     per-block shift in one launch, into the int8 `q8_shard` and the uint8 `shift_shard`; all_gather_shards
@@ -965,8 +970,9 @@ class ByteWireAggregator:
     shift 0 and decodes as under "i16", bit for bit.  The pad's bytes are zero, so its blocks' shifts are 0."""
 
     def __init__(self, n: int, V: int = 256, group=None, device=None, align: int = 1024, rotate: bool = True,
-                 seed: int = 0, gather: str = "i16"):
+                 seed: int = 0, gather: str = "i16", error_feedback: bool = False):
         self.seed = _check_seed(seed)
+        self.error_feedback = bool(error_feedback)
         if gather not in ("i16", "i8"):
             raise ValueError(f"gather must be 'i16' or 'i8', got {gather!r}")
         self.gather = gather
@@ -998,8 +1004,19 @@ class ByteWireAggregator:
             self._sbuf = torch.zeros(nblk, dtype=torch.uint8, device=dev)
         self.full = torch.empty(tot, dtype=torch.float32, device=dev)
         self._stage = None           # rotate=False with n % V: the bucket padded with zeros to whole blocks
+        self._resid = torch.zeros(tot, dtype=torch.float32, device=dev) if self.error_feedback else None
 
     step = ShardedAggregator.step
+
+    @property
+    def residual(self) -> torch.Tensor:
+        """What this rank's bytes have dropped so far (n float32 values; error_feedback=True only)."""
+        if self._resid is None:
+            raise ValueError("no residual: the aggregator was built with error_feedback=False")
+        return self._resid[: self.plan.n]
+
+    def reset_residual(self):
+        self.residual.zero_()
 
     @property
     def kblk(self) -> torch.Tensor:
@@ -1064,9 +1081,15 @@ class ByteWireAggregator:
         nb = x.numel() // V
         key = dict(rotate=self.seed if self.rotate else None, step=self._step)
         kb = self._kbuf[:nb]
-        i8.block_scales([x], V, out=kb, **key)
-        agree_block_scales(kb, self.group)
-        i8.quantize(x, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
+        if self.error_feedback:
+            res = self._resid[: x.numel()]
+            i8.block_scales_ef([x], [res], V, out=kb, **key)
+            agree_block_scales(kb, self.group)
+            i8.quantize_ef(x, res, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
+        else:
+            i8.block_scales([x], V, out=kb, **key)
+            agree_block_scales(kb, self.group)
+            i8.quantize(x, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
         if self.gather == "i8":
             i8.sum_slices_requant(self._exchange(), V, out=self.q8_shard, shift=self.shift_shard)
             all_gather_shards(self.q8_shard, self.plan, self.group, out=self.q8_full)

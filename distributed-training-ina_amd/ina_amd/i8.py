@@ -18,6 +18,13 @@ the decode reads those bytes -- one byte a value more off the links, half of 2^s
     q8s, sh = i8.sum_slices_requant(received, V)                    # int8 + one uint8 shift a block
     g = i8.dequantize_gather(gathered, shifts, kblk, V, rotate=seed, step=t)
 
+A rank may keep what its bytes dropped (include/ina_i8_ef.h; ByteWireAggregator(error_feedback=True)): one fp32
+residual per bucket, added in front of the rotation and rewritten in the quantiser's launch with the rounding
+error taken back through the inverse rotation.  It never travels, and nothing else of the step changes.
+
+    kblk = i8.block_scales_ef([grad], [resid], V, rotate=seed, step=t)      # then MIN across ranks
+    q8, flags = i8.quantize_ef(grad, resid, kblk, V, rotate=seed, step=t)   # resid updated in place
+
 `rotate` is None (no rotation) or the seed.  n must be a multiple of V for the block calls, buffers 16-byte
 aligned, e0 a multiple of 128 and of V; no base; no CPU fallback and no value-by-value path.
 """
@@ -76,6 +83,56 @@ def quantize(x: torch.Tensor, kblk: torch.Tensor, V: int, rotate: int | None = N
     _same_device(x, out, overflow)
     check(load().ina_quantize_i8_wire(x.data_ptr(), xt, kblk.data_ptr(), V, out.data_ptr(), n, overflow.data_ptr(),
                                       prm, _stream(x)), "i8.quantize")
+    return out, overflow
+
+
+def _resid(resid, x: torch.Tensor, name: str = "resid"):
+    """A rank-local residual: float32 whatever x's dtype, one value per value of x, on x's device."""
+    _req(resid, torch.float32, name)
+    if resid.numel() != x.numel():
+        raise ValueError(f"{name} holds {resid.numel()} elements, the bucket {x.numel()}")
+    _same_device(x, resid)
+
+
+def block_scales_ef(xs, resids, V: int, rotate: int | None = None, step: int = 0, sub: int = 0, e0: int = 0,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """block_scales over xs[w] + resids[w] (include/ina_i8_ef.h): the scales of what quantize_ef will quantise.
+    Nothing but the scales is written; ranks agree by taking the MIN of theirs."""
+    xs, n, xt = _grad_bufs(xs, "xs")
+    resids = [resids] if isinstance(resids, torch.Tensor) and resids.dim() == 1 else list(resids)
+    if len(resids) != len(xs):
+        raise ValueError("one residual per bucket")
+    for i, r in enumerate(resids):
+        _resid(r, xs[0], f"resids[{i}]")
+    V = _v(V, n)
+    prm = _sr(rotate, step, sub, e0, V)
+    out = _blk_scales_arg(out, n // V, xs[0], "out")
+    check(load().ina_block_scales_i8_ef(_ptrs(xs), _ptrs(resids), xt, len(xs), n, V, out.data_ptr(), prm,
+                                        _stream(xs[0])), "i8.block_scales_ef")
+    return out
+
+
+def quantize_ef(x: torch.Tensor, resid: torch.Tensor, kblk: torch.Tensor, V: int, rotate: int | None = None,
+                step: int = 0, sub: int = 0, e0: int = 0, out: torch.Tensor | None = None,
+                overflow: torch.Tensor | None = None):
+    """(int8 [n], flags): quantize of x + resid, in one launch with resid's update in place: resid becomes the
+    rounding error r - q8 * 2^-kblk[block] taken back through the inverse rotation (as it is under rotate=None),
+    +0 where that is NaN or inf.  resid must not overlap x or out."""
+    xt = _req_grad(x, "x")
+    n = x.numel()
+    _resid(resid, x)
+    V = _v(V, n)
+    prm = _sr(rotate, step, sub, e0, V)
+    kblk = _blk_scales_arg(kblk, n // V, x, given=True)
+    out = torch.empty(n, dtype=torch.int8, device=x.device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int8, "out")
+    overflow = torch.empty(n // V, dtype=torch.uint8, device=x.device) if overflow is None else overflow
+    _fits(overflow, n // V, "overflow")
+    _req(overflow, torch.uint8, "overflow")
+    _same_device(x, out, overflow)
+    check(load().ina_quantize_ef_i8_wire(x.data_ptr(), xt, resid.data_ptr(), kblk.data_ptr(), V, out.data_ptr(), n,
+                                         overflow.data_ptr(), prm, _stream(x)), "i8.quantize_ef")
     return out, overflow
 
 

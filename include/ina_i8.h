@@ -56,10 +56,12 @@
  * unsigned by flipping their sign bits, the G * 128 taken off again per field), and writes 32 bytes of
  * int16.  Every grid is under the default cap (ina_set_tuning key 0).
  *
- * Not here: stochastic rounding and error feedback on this wire, a base, layout B, the packet path, a
- * pipelined step (chunks > 1), a requantised 8-bit gather, and bench.py.  The requantised gather -- the sums
+ * Not here: stochastic rounding on this wire, a base, layout B, the packet path, a pipelined step
+ * (chunks > 1), a requantised 8-bit gather, error feedback, and bench.py.  The requantised gather -- the sums
  * rounded back to bytes under a per-block shift, and a decode that reads them -- is in ina_i8_gather.h, which
- * this header includes as its last line.
+ * this header includes as its last line; error feedback on this wire -- the rounding error carried back
+ * through the inverse rotation into a rank-local residual, in the quantiser's launch -- is in ina_i8_ef.h,
+ * which that header includes as its last line.
  */
 #ifndef INA_I8_H
 #define INA_I8_H

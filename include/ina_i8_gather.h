@@ -49,8 +49,10 @@
  * of bytes; a block is V/4 adjacent lanes of one wave), the scale and the shift one byte load each.  Every
  * grid is under the default cap (ina_set_tuning key 0).
  *
- * Not here: stochastic rounding or error feedback on either half of the wire, a 4-bit word, a 16-bit output
- * of the decode, layout B, the packet path, a pipelined step (chunks > 1), and bench.py.
+ * Not here: stochastic rounding on either half of the wire, error feedback on the requantiser's rounding, a
+ * 4-bit word, a 16-bit output of the decode, layout B, the packet path, a pipelined step (chunks > 1), and
+ * bench.py.  Error feedback on the rank's own rounding -- the first half of the wire -- is in ina_i8_ef.h,
+ * which this header includes as its last line.
  */
 #ifndef INA_I8_GATHER_H
 #define INA_I8_GATHER_H
@@ -65,5 +67,7 @@ int ina_sum_i8_slices_requant(const int8_t* const* slices, int G, int V, int8_t*
 /* ina_dequantize_rot_i16 (sr != NULL) or ina_dequantize_blk_i16_f32 (sr == NULL) of (int16)q8 << shift[block] */
 int ina_dequantize_i8_gather(const int8_t* q8, const uint8_t* shift, const int8_t* kblk, int V, float* y, size_t n,
                              const ina_sr_t* sr, ina_stream_t stream);
+
+#include "ina_i8_ef.h" /* error feedback on the byte wire: the residual carried through the rotation */
 
 #endif /* INA_I8_GATHER_H */

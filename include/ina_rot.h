@@ -55,9 +55,10 @@
  * The signs of a wave's 256 values are two Philox calls on the scalar unit.  Every grid is under the
  * default cap (ina_set_tuning key 0).
  *
- * Not here: the rotation combined with stochastic rounding or error feedback, a base, the sharded wires,
- * the packet path, and V > 256.  A sharded wire that takes the rotation -- 8 bits a value over an
- * all-to-all -- is in ina_i8.h, which this header includes as its last line.
+ * Not here: the rotation combined with stochastic rounding, error feedback on the calls of this header, a
+ * base, the sharded wires, the packet path, and V > 256.  A sharded wire that takes the rotation -- 8 bits a
+ * value over an all-to-all -- is in ina_i8.h, which this header includes as its last line; the rotation
+ * combined with error feedback, on that wire, is in ina_i8_ef.h at the end of the same chain.
  */
 #ifndef INA_ROT_H
 #define INA_ROT_H

@@ -788,6 +788,46 @@ def run_i8_ef(dev):
     return rows
 
 
+def run_i8_sr(dev):
+    """Stochastic rounding on the 8-bit wire (include/ina_i8_sr.h) at the ResNet-50 size (rounded down to a multiple
+    of 256), cold caches, median of 20, the set twice in this process (run 1 / run 2).  Each new call beside its
+    round-to-nearest sibling timed twice in the same process (the two times' difference is the spread):
+    i8.quantize_sr on fp32 and bf16 buckets at V = 32 and 256, rotated and plain, beside i8.quantize;
+    i8.sum_slices_requant_sr at G = 8 and 64 beside i8.sum_slices_requant.  bytes = the algorithmic HBM bytes, the
+    sibling's.  Nothing is gated here; DESIGN 4.1s reads the rows."""
+    from ina_amd import i8
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(61)
+    n, seed = 25_557_032 // 256 * 256, 0x1234
+    x32 = torch.randn(n, device=dev, generator=gen) * 1e-2
+    parts = [torch.randint(-128, 128, (n,), dtype=torch.int8, device=dev, generator=gen) for _ in range(64)]
+    q8 = torch.empty(n, dtype=torch.int8, device=dev)
+
+    def row(run, name, nbytes, f_new, f_bar, bar_name):
+        ta, tn, tb = _time(f_bar), _time(f_new), _time(f_bar)
+        rows.append(_row(f"{name} [i8 sr, run {run}]", tn, nbytes, bar=bar_name,
+                         bar_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], bar_spread_us=round(abs(ta - tb) * 1e6, 2),
+                         over_bar=round(tn / min(ta, tb), 3)))
+
+    for run in (1, 2):
+        for V in (32, 256):
+            nblk = n // V
+            ovf = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            sh = torch.empty(nblk, dtype=torch.uint8, device=dev)
+            for x, tag in ((x32, "f32"), (x32.to(torch.bfloat16), "bf16")):
+                for rotate, arm in ((seed, "rot"), (None, "plain")):
+                    kb = i8.block_scales_sr([x], V, rotate, step=run)
+                    row(run, f"quantize_sr {tag}->i8 V={V} {arm}", (x.element_size() + 1) * n + 2 * nblk,
+                        lambda: i8.quantize_sr(x, kb, V, seed, rotate, step=run, sub=1, out=q8, overflow=ovf),
+                        lambda: i8.quantize(x, kb, V, rotate, step=run, out=q8, overflow=ovf), "i8.quantize")
+            for G in (8, 64):
+                row(run, f"sum_slices_requant_sr G={G} V={V}", (G + 1) * n + nblk,
+                    lambda: i8.sum_slices_requant_sr(parts[:G], V, seed, step=run, sub=65, out=q8, shift=sh),
+                    lambda: i8.sum_slices_requant(parts[:G], V, out=q8, shift=sh), f"i8.sum_slices_requant G={G}")
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1491,6 +1531,7 @@ def run_extra(dev):
     rows += run_i8(dev)
     rows += run_i8_gather(dev)
     rows += run_i8_ef(dev)
+    rows += run_i8_sr(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

@@ -21,8 +21,6 @@
 // the grid's last lanes.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-
 #include "ina.h"
 #include "ina_internal.h"
 #include "ina_device.h"
@@ -151,7 +149,8 @@ __global__ __launch_bounds__(kBlk) void k_sum_i8(PtrPack<int8_t> in, int Gd, int
 int launched() { return check_launch("int8 wire kernel launch"); }
 
 template <typename X>
-int block_scales(const void* const* xs, int W, size_t n, int V, int8_t* kblk, const ina_sr_t* sr, ina_stream_t stream) {
+int block_scales(const void* const* xs, int W, size_t n, int V, int8_t* kblk, const ina_sr_t* sr, double lim,
+                 ina_stream_t stream) {
     int shift;
     if (int rc = check_blocks(V, kblk, n, shift)) return rc;
     if (n == 0) return INA_OK;
@@ -163,8 +162,8 @@ int block_scales(const void* const* xs, int W, size_t n, int V, int8_t* kblk, co
     if (sr)
         if (int rc = rot_key(sr, V, key)) return rc;
     const dim3 g(grid_of(n / 4, default_grid_cap())), b(kBlk);
-    if (sr) hipLaunchKernelGGL((k_i8_scales<X, true>), g, b, 0, hs(stream), pk, W, n, shift, kLimI8, key, kblk);
-    else hipLaunchKernelGGL((k_i8_scales<X, false>), g, b, 0, hs(stream), pk, W, n, shift, kLimI8, key, kblk);
+    if (sr) hipLaunchKernelGGL((k_i8_scales<X, true>), g, b, 0, hs(stream), pk, W, n, shift, lim, key, kblk);
+    else hipLaunchKernelGGL((k_i8_scales<X, false>), g, b, 0, hs(stream), pk, W, n, shift, lim, key, kblk);
     return launched();
 }
 
@@ -187,6 +186,13 @@ int quantize(const void* x, const int8_t* kblk, int V, int8_t* q8, size_t n, uin
 }
 
 }  // namespace
+
+int block_scales_i8(const void* const* xs, int xtype, int W, size_t n, int V, int8_t* kblk, const ina_sr_t* sr,
+                    double lim, ina_stream_t stream) {
+    if (int rc = check_xtype(xtype)) return rc;
+    return INA_I8_X_CALL(xtype, block_scales, xs, W, n, V, kblk, sr, lim, stream);
+}
+
 }  // namespace ina
 
 using namespace ina;
@@ -194,19 +200,12 @@ using namespace ina;
 extern "C" {
 
 int ina_scale_for_i8(float absmax, int* k_out) {
-    if (!k_out) return set_error(INA_EINVAL, "null k_out%s", "");
-    if (!(absmax >= 0.0f) || std::isinf(absmax)) return set_error(INA_EINVAL, "absmax must be finite and >= 0%s", "");
-    int k = 127;
-    if (absmax != 0.0f)                                 // exact: a float times a power of two, as a double
-        while (k > -126 && (double)absmax * std::ldexp(1.0, k) > kLimI8) --k;
-    *k_out = k;
-    return INA_OK;
+    return scale_for_lim(absmax, k_out, kLimI8);
 }
 
 int ina_block_scales_i8(const void* const* xs, int xtype, int W, size_t n, int V, int8_t* kblk, const ina_sr_t* sr,
                         ina_stream_t stream) {
-    if (int rc = check_xtype(xtype)) return rc;
-    return INA_I8_X_CALL(xtype, block_scales, xs, W, n, V, kblk, sr, stream);
+    return block_scales_i8(xs, xtype, W, n, V, kblk, sr, kLimI8, stream);
 }
 
 int ina_quantize_i8_wire(const void* x, int xtype, const int8_t* kblk, int V, int8_t* q8, size_t n,

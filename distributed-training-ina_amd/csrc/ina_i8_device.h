@@ -1,6 +1,9 @@
-// ina_i8_device.h -- what the byte wire's sources share (ina_i8.hip, ina_i8_ef.hip): the lanes' loop, the
-// scale rule's limit, the byte quantiser of a lane's chunk, and the block calls' host checks.
+// ina_i8_device.h -- what the byte wire's sources share (ina_i8.hip, ina_i8_ef.hip, ina_i8_sr.hip): the lanes'
+// loop, the scale rule's limits and host loop, the byte quantiser of a lane's chunk, and the block calls' host
+// checks and scales dispatch.
 #pragma once
+#include <cmath>
+
 #include "ina_internal.h"
 #include "ina_chunk.h"
 
@@ -8,6 +11,7 @@ namespace ina {
 
 constexpr int kI8Blk = 256;
 constexpr double kLimI8 = 126.5;   // ina_scale_for_i8: absmax * 2^k + 1/2 <= 127
+constexpr double kLimI8Sr = 126.0; // ina_scale_for_i8_sr: absmax * 2^k + 1 <= 127 (include/ina_i8_sr.h)
 
 // chunk i = values 4i..4i+3; base_ is the wave's first chunk (a multiple of 64)
 #define INA_I8_QUAD_LOOP(nq)                                       \
@@ -54,6 +58,20 @@ inline int check_blocks(int V, const int8_t* kblk, size_t n, int& shift) {
     if (n % (size_t)V) return set_error(INA_EINVAL, "n must be a multiple of V%s", "");
     return INA_OK;
 }
+
+// the host scale rule under a limit: the largest k in [-126, 127] with absmax * 2^k <= lim
+inline int scale_for_lim(float absmax, int* k_out, double lim) {
+    if (!k_out) return set_error(INA_EINVAL, "null k_out%s", "");
+    if (!(absmax >= 0.0f) || std::isinf(absmax)) return set_error(INA_EINVAL, "absmax must be finite and >= 0%s", "");
+    int k = 127;
+    if (absmax != 0.0f)                                 // exact: a float times a power of two, as a double
+        while (k > -126 && (double)absmax * std::ldexp(1.0, k) > lim) --k;
+    *k_out = k;
+    return INA_OK;
+}
+// ina_block_scales_i8 under the limit `lim` (ina_i8.hip: the checks, then k_i8_scales)
+int block_scales_i8(const void* const* xs, int xtype, int W, size_t n, int V, int8_t* kblk, const ina_sr_t* sr,
+                    double lim, ina_stream_t stream);
 
 #define INA_I8_X_CALL(xtype, F, ...)                           \
     ((xtype) == INA_X16_BF16  ? F<bf16_t>(__VA_ARGS__)         \

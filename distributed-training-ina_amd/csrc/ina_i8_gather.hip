@@ -2,8 +2,9 @@
 // contract): the sum of up to 64 ranks' byte slices rounded back to bytes under a per-block shift in one pass,
 // and the decode that reads those bytes.
 //
-// Sum + requantise.  The front is k_sum_i8's (ina_i8.hip): a lane owns 16 values, loads 16 bytes of each slice
-// and adds their even and odd bytes as 16-bit fields of 32-bit words (bytes made unsigned by w ^ 0x80808080, a
+// Sum + requantise.  The front is k_sum_i8's (ina_i8.hip; its loads, byte adds and block maximum are in
+// ina_i8_sum_device.h, which ina_i8_sr.hip's stochastic requantiser shares): a lane owns 16 values, loads 16
+// bytes of each slice and adds their even and odd bytes as 16-bit fields of 32-bit words (bytes made unsigned by w ^ 0x80808080, a
 // field starting at 0x8000 - 128 G, its top bit flipped at the end); G = 2, 4, 8, 16 are compile-time with up
 // to 8 loads in flight, any other G runs a loop with two.  The 8 words of signed sums then stay in registers
 // and everything up to the bytes is packed 16-bit arithmetic on them (v_pk_*_i16, written as vector
@@ -35,6 +36,7 @@
 #include "ina_device.h"
 #include "ina_chunk.h"
 #include "ina_rot_device.h"
+#include "ina_i8_sum_device.h"
 
 namespace ina {
 namespace {
@@ -44,62 +46,6 @@ constexpr int kBlk = 256;
 // ---------------------------------------------------------------------------
 // sum + requantise
 // ---------------------------------------------------------------------------
-constexpr uint32_t kTop16 = 0x80008000u, kLow8 = 0x00FF00FFu;
-// DPP controls beyond ina_rot_device.h's: a row of 16 reversed, each half row of 8 reversed
-constexpr int kDppRowMirror = 0x140, kDppHalfMirror = 0x141;
-
-typedef int16_t s16x2 __attribute__((ext_vector_type(2)));   // the two 16-bit fields of a word
-__device__ __forceinline__ s16x2 fields(uint32_t w) { return __builtin_bit_cast(s16x2, w); }
-__device__ __forceinline__ uint32_t word(s16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-
-// the lane's chunk i of B slices: a whole chunk is one 16-byte load; the half chunk of a V = 8 tail is 8 bytes
-// and 8 zeros; a lane past n holds zeros
-template <int B>
-__device__ __forceinline__ void ld_chunks(const PtrPack<int8_t>& in, int g0, size_t i, size_t nfull, bool half,
-                                          u32x4* w) {
-    if (i < nfull) {
-#pragma unroll
-        for (int j = 0; j < B; ++j) w[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in.p[g0 + j]) + i);
-    } else {
-#pragma unroll
-        for (int j = 0; j < B; ++j) w[j] = u32x4{0u, 0u, 0u, 0u};
-        if (half) {
-#pragma unroll
-            for (int j = 0; j < B; ++j) {
-                const u32x2 h = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(in.p[g0 + j] + 16 * i));
-                w[j].x = h.x;
-                w[j].y = h.y;
-            }
-        }
-    }
-}
-__device__ __forceinline__ void add_bytes(u32x4 w, u32x4& ev, u32x4& od) {
-    w ^= 0x80808080u;
-    ev += w & kLow8;
-    od += (w >> 8) & kLow8;
-}
-
-// max |field| over 4 words, as one number
-__device__ __forceinline__ int absmax4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    auto ab = [](uint32_t w) { return __builtin_elementwise_abs(fields(w)); };
-    const s16x2 m = __builtin_elementwise_max(__builtin_elementwise_max(ab(a), ab(b)),
-                                              __builtin_elementwise_max(ab(c), ab(d)));
-    return max((int)m.x, (int)m.y);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_max(int m) {
-    return max(m, __builtin_amdgcn_update_dpp(0, m, CTRL, 0xf, 0xf, true));
-}
-// the max over the 1 << steps adjacent lanes of a group (steps <= 4: inside one row); every lane of the wave
-// must reach it; steps is wave-uniform
-__device__ __forceinline__ int row_group_max(int m, int steps) {
-    if (steps >= 1) m = dpp_max<kDppXor1>(m);
-    if (steps >= 2) m = dpp_max<kDppXor2>(m);
-    if (steps >= 3) m = dpp_max<kDppHalfMirror>(m);
-    if (steps >= 4) m = dpp_max<kDppRowMirror>(m);
-    return m;
-}
-
 // the smallest sh with rne(a / 2^sh) <= 127, for 0 <= a <= 8192
 __device__ __forceinline__ int shift_of(int a) {
     const int s0 = max(0, 25 - (int)__builtin_clz((uint32_t)a | 1u));          // bitlen(a) - 7
@@ -230,20 +176,13 @@ extern "C" {
 
 int ina_sum_i8_slices_requant(const int8_t* const* slices, int G, int V, int8_t* q8, uint8_t* shift, size_t n,
                               ina_stream_t stream) {
-    if (!slices || G < 1 || G > INA_MAX_WORKERS) return set_error(INA_EINVAL, "G must be in [1, %s]", "64");
-    int qs;                                             // log2(V) - 2
-    if (!vec_v(V, qs)) return bad_v();
-    if (!shift) return set_error(INA_EINVAL, "null shift%s", "");
-    if (n % (size_t)V) return bad_n();
-    if (n == 0) return INA_OK;
     PtrPack<int8_t> pk;
-    bool al;
-    if (int rc = fill_pack(pk, slices, G, al)) return rc;
-    if (!q8) return set_error(INA_EINVAL, "null q8%s", "");
-    if (!al || !aligned16(q8)) return misaligned();
+    int lv;
+    if (int rc = check_sum_rq(slices, G, V, q8, shift, n, pk, lv)) return rc;
+    if (n == 0) return INA_OK;
     const dim3 g(grid_of((n + 15) / 16, default_grid_cap())), b(kBlk);
     hipStream_t s = hs(stream);
-#define L(GG) hipLaunchKernelGGL(k_sum_rq_i8<GG>, g, b, 0, s, pk, G, q8, shift, n, qs + 2)
+#define L(GG) hipLaunchKernelGGL(k_sum_rq_i8<GG>, g, b, 0, s, pk, G, q8, shift, n, lv)
     switch (G) {
         case 2: L(2); break;
         case 4: L(4); break;

@@ -274,6 +274,14 @@ SIGNATURES_I8_EF = {
     "ina_block_scales_i8_ef": [_vp, _vp, _i, _i, _sz, _i, _vp, C.POINTER(SrParams), _vp],
     "ina_quantize_ef_i8_wire": [_vp, _i, _vp, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
 }
+# stochastic rounding on both halves of that wire (include/ina_i8_sr.h): the rotation's ina_sr_t (NULL: no
+# rotation) and then the rounding's (required) precede the stream
+SIGNATURES_I8_SR = {
+    "ina_scale_for_i8_sr": [C.c_float, C.POINTER(C.c_int)],
+    "ina_block_scales_i8_sr": [_vp, _i, _i, _sz, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_sr_i8_wire": [_vp, _i, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), C.POINTER(SrParams), _vp],
+    "ina_sum_i8_slices_requant_sr": [_vp, _i, _i, _vp, _vp, _sz, C.POINTER(SrParams), _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -292,7 +300,8 @@ def open_library(path: str) -> C.CDLL:
                        **SIGNATURES_SWITCH_BLK, **SIGNATURES_SHARD_BLK, **SIGNATURES_BLK_X16,
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
                        **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR,
-                       **SIGNATURES_ROT, **SIGNATURES_I8, **SIGNATURES_I8G, **SIGNATURES_I8_EF}.items():
+                       **SIGNATURES_ROT, **SIGNATURES_I8, **SIGNATURES_I8G, **SIGNATURES_I8_EF,
+                       **SIGNATURES_I8_SR}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

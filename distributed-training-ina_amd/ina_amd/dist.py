@@ -953,7 +953,7 @@ class ByteWireAggregator:
     of the block clamped at +-127 under the agreed scale or was NaN; rank-local, never sent).  `wire_bytes`,
     `gather_bytes` and `scale_bytes` are what one step brings to each rank over the links: (G-1) x shard x 1,
     (G-1) x shard x 2, and one byte per block.  Shards are aligned to the lcm of `align`, V and 128, so every
-    shard starts where a rotated call may start (e0).  No chunks, no stochastic rounding, no layout B.
+    shard starts where a rotated call may start (e0).  No chunks, no layout B.
     error_feedback=True (include/ina_i8_ef.h) keeps what this rank's bytes dropped: the aggregator owns one fp32
     residual of the padded size on its device, i8.block_scales_ef and i8.quantize_ef take the place of
     i8.block_scales and i8.quantize -- the residual is added in front of the rotation and rewritten, in the
@@ -967,12 +967,26 @@ class ByteWireAggregator:
     decodes the bytes on every rank.  `gather_bytes` is then (G-1) x shard x (1 + 1/V), and a step is 1 + 1
     bytes a value where the default is 1 + 2.  The price is the requantiser's half of 2^shift summand quanta
     on top of the G halves (DESIGN 4.1q has the measured error); a block whose sums stay within +-127 has
-    shift 0 and decodes as under "i16", bit for bit.  The pad's bytes are zero, so its blocks' shifts are 0."""
+    shift 0 and decodes as under "i16", bit for bit.  The pad's bytes are zero, so its blocks' shifts are 0.
+    rounding="stochastic" (include/ina_i8_sr.h; default "nearest", which leaves every byte of the step as it is)
+    rounds both halves without bias and without state: i8.block_scales_sr (a whole quantum of headroom) and
+    i8.quantize_sr take the place of i8.block_scales and i8.quantize, and under gather="i8"
+    i8.sum_slices_requant_sr that of i8.sum_slices_requant; the decodes, every collective and every byte count
+    are unchanged, and every rank still ends with the same `full`.  The streams of one step, all under `seed`
+    and step = `step`: sub = 0, e0 = 0 is the rotation's, shared by every rank; sub = 1 + rank, e0 = 0 is rank
+    `rank`'s quantiser; sub = 1 + MAX_WORKERS, e0 = rank * shard is the owners' requantiser, each owner on its
+    shard's range of one stream (shards are multiples of 128).  It excludes error_feedback=True."""
 
     def __init__(self, n: int, V: int = 256, group=None, device=None, align: int = 1024, rotate: bool = True,
-                 seed: int = 0, gather: str = "i16", error_feedback: bool = False):
+                 seed: int = 0, gather: str = "i16", error_feedback: bool = False, rounding: str = "nearest"):
         self.seed = _check_seed(seed)
         self.error_feedback = bool(error_feedback)
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"rounding must be 'nearest' or 'stochastic', got {rounding!r}")
+        self.rounding, self.stochastic = rounding, rounding == "stochastic"
+        if self.stochastic and self.error_feedback:
+            raise ValueError("rounding='stochastic' and error_feedback=True exclude each other: stochastic rounding "
+                             "is the stateless alternative to the residual")
         if gather not in ("i16", "i8"):
             raise ValueError(f"gather must be 'i16' or 'i8', got {gather!r}")
         self.gather = gather
@@ -1086,12 +1100,21 @@ class ByteWireAggregator:
             i8.block_scales_ef([x], [res], V, out=kb, **key)
             agree_block_scales(kb, self.group)
             i8.quantize_ef(x, res, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
+        elif self.stochastic:
+            i8.block_scales_sr([x], V, out=kb, **key)
+            agree_block_scales(kb, self.group)
+            i8.quantize_sr(x, kb, V, self.seed, sub=1 + self.rank, out=self.q8[: x.numel()], overflow=self._obuf[:nb],
+                           **key)
         else:
             i8.block_scales([x], V, out=kb, **key)
             agree_block_scales(kb, self.group)
             i8.quantize(x, kb, V, out=self.q8[: x.numel()], overflow=self._obuf[:nb], **key)
         if self.gather == "i8":
-            i8.sum_slices_requant(self._exchange(), V, out=self.q8_shard, shift=self.shift_shard)
+            if self.stochastic:
+                i8.sum_slices_requant_sr(self._exchange(), V, self.seed, step=self._step, sub=1 + _lib.MAX_WORKERS,
+                                         e0=self.rank * self.plan.shard, out=self.q8_shard, shift=self.shift_shard)
+            else:
+                i8.sum_slices_requant(self._exchange(), V, out=self.q8_shard, shift=self.shift_shard)
             all_gather_shards(self.q8_shard, self.plan, self.group, out=self.q8_full)
             all_gather_shards(self.shift_shard, self.plan, self.group, out=self._sbuf)
             i8.dequantize_gather(self.q8_full, self._sbuf, self._kbuf, V, out=self.full, **key)

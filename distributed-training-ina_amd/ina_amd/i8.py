@@ -25,6 +25,15 @@ error taken back through the inverse rotation.  It never travels, and nothing el
     kblk = i8.block_scales_ef([grad], [resid], V, rotate=seed, step=t)      # then MIN across ranks
     q8, flags = i8.quantize_ef(grad, resid, kblk, V, rotate=seed, step=t)   # resid updated in place
 
+Both roundings may be stochastic instead (include/ina_i8_sr.h; ByteWireAggregator(rounding="stochastic")): the
+stateless alternative to the residual, and the only one that reaches the owner's second rounding.  The rounding
+stream (seed, step, sub, e0) is apart from the rotation's (rotate, step, rot_sub, rot_e0): ranks share the
+second and must differ in the first.  tests/_i8_sr_ref.py replays the contract.
+
+    kblk = i8.block_scales_sr([grad], V, rotate=seed, step=t)       # one quantum of headroom; then MIN
+    q8, flags = i8.quantize_sr(grad, kblk, V, seed, rotate=seed, step=t, sub=1 + rank)
+    q8s, sh = i8.sum_slices_requant_sr(received, V, seed, step=t, sub=65, e0=rank * shard)
+
 `rotate` is None (no rotation) or the seed.  n must be a multiple of V for the block calls, buffers 16-byte
 aligned, e0 a multiple of 128 and of V; no base; no CPU fallback and no value-by-value path.
 """
@@ -37,6 +46,7 @@ import torch
 from ._lib import MAX_WORKERS, check, load
 from .ops import _blk_scales_arg, _fits, _grad_bufs, _ptrs, _req, _req_grad, _same_device, _stream
 from .rot import _key, _v
+from .sr import _params
 
 
 def scale_for(absmax: float) -> int:
@@ -83,6 +93,51 @@ def quantize(x: torch.Tensor, kblk: torch.Tensor, V: int, rotate: int | None = N
     _same_device(x, out, overflow)
     check(load().ina_quantize_i8_wire(x.data_ptr(), xt, kblk.data_ptr(), V, out.data_ptr(), n, overflow.data_ptr(),
                                       prm, _stream(x)), "i8.quantize")
+    return out, overflow
+
+
+def scale_for_sr(absmax: float) -> int:
+    """The largest k in [-126, 127] with absmax * 2^k + 1 <= 127: scale_for with the whole quantum of headroom
+    that rounding up by chance needs."""
+    k = C.c_int(0)
+    check(load().ina_scale_for_i8_sr(float(absmax), C.byref(k)), "i8.scale_for_sr")
+    return k.value
+
+
+def block_scales_sr(xs, V: int, rotate: int | None = None, step: int = 0, sub: int = 0, e0: int = 0,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """block_scales under scale_for_sr's rule: the scales quantize_sr never clamps under.  (rotate, step, sub, e0)
+    is the rotation's key; no random stream of the rounding takes part."""
+    xs, n, xt = _grad_bufs(xs, "xs")
+    V = _v(V, n)
+    prm = _sr(rotate, step, sub, e0, V)
+    out = _blk_scales_arg(out, n // V, xs[0], "out")
+    check(load().ina_block_scales_i8_sr(_ptrs(xs), xt, len(xs), n, V, out.data_ptr(), prm, _stream(xs[0])),
+          "i8.block_scales_sr")
+    return out
+
+
+def quantize_sr(x: torch.Tensor, kblk: torch.Tensor, V: int, seed: int, rotate: int | None = None, step: int = 0,
+                sub: int = 0, e0: int = 0, rot_sub: int = 0, rot_e0: int = 0, out: torch.Tensor | None = None,
+                overflow: torch.Tensor | None = None):
+    """(int8 [n], flags): quantize with the rounding replaced by y = floor(t) + (u < t - floor(t)), t = r *
+    2^kblk[block], u 24 bits of Philox under the rounding key (seed, step, sub, e0) -- e0 a multiple of 4.  The
+    rotation's key is (rotate, step, rot_sub, rot_e0).  E[q8] = t where nothing clamps."""
+    xt = _req_grad(x, "x")
+    n = x.numel()
+    V = _v(V, n)
+    prm = _sr(rotate, step, rot_sub, rot_e0, V)
+    rnd = _params(seed, step, sub, e0)
+    kblk = _blk_scales_arg(kblk, n // V, x, given=True)
+    out = torch.empty(n, dtype=torch.int8, device=x.device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int8, "out")
+    overflow = torch.empty(n // V, dtype=torch.uint8, device=x.device) if overflow is None else overflow
+    _fits(overflow, n // V, "overflow")
+    _req(overflow, torch.uint8, "overflow")
+    _same_device(x, out, overflow)
+    check(load().ina_quantize_sr_i8_wire(x.data_ptr(), xt, kblk.data_ptr(), V, out.data_ptr(), n, overflow.data_ptr(),
+                                         prm, C.byref(rnd), _stream(x)), "i8.quantize_sr")
     return out, overflow
 
 
@@ -175,6 +230,28 @@ def sum_slices_requant(parts, V: int, out: torch.Tensor | None = None, shift: to
     _same_device(out, shift, *parts)
     check(load().ina_sum_i8_slices_requant(_ptrs(parts), len(parts), V, out.data_ptr(), shift.data_ptr(), n,
                                            _stream(out)), "i8.sum_slices_requant")
+    return out, shift
+
+
+def sum_slices_requant_sr(parts, V: int, seed: int, step: int = 0, sub: int = 0, e0: int = 0,
+                          out: torch.Tensor | None = None, shift: torch.Tensor | None = None):
+    """(int8 [n], uint8 [n / V]): sum_slices_requant with q8 = (S + u) >> shift, u the low `shift` bits of a
+    Philox byte under (seed, step, sub, e0) -- e0 a multiple of 16 -- and shift the smallest with max |S| <=
+    127 << shift.  Integers only: E[q8] * 2^shift = S exactly; a block within +-127 is sum_slices_requant's."""
+    rnd = _params(seed, step, sub, e0)
+    if e0 % 16:
+        raise ValueError(f"e0 must be a multiple of 16, got {e0}: a lane's 16 values share one Philox call")
+    parts, n = _slices(parts)
+    V = _v(V, n)
+    out = torch.empty(n, dtype=torch.int8, device=parts[0].device) if out is None else out
+    _fits(out, n)
+    _req(out, torch.int8, "out")
+    shift = torch.empty(n // V, dtype=torch.uint8, device=out.device) if shift is None else shift
+    _fits(shift, n // V, "shift")
+    _req(shift, torch.uint8, "shift")
+    _same_device(out, shift, *parts)
+    check(load().ina_sum_i8_slices_requant_sr(_ptrs(parts), len(parts), V, out.data_ptr(), shift.data_ptr(), n,
+                                              C.byref(rnd), _stream(out)), "i8.sum_slices_requant_sr")
     return out, shift
 
 

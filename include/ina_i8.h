@@ -61,7 +61,8 @@
  * rounded back to bytes under a per-block shift, and a decode that reads them -- is in ina_i8_gather.h, which
  * this header includes as its last line; error feedback on this wire -- the rounding error carried back
  * through the inverse rotation into a rank-local residual, in the quantiser's launch -- is in ina_i8_ef.h,
- * which that header includes as its last line.
+ * which that header includes as its last line; stochastic rounding on this wire -- the byte quantiser and the
+ * requantised gather -- is in ina_i8_sr.h at the end of the same chain.
  */
 #ifndef INA_I8_H
 #define INA_I8_H

@@ -55,6 +55,8 @@
  *
  * Not here: stochastic rounding on this wire, scales computed in the quantiser's launch (an AUTO mode), a base,
  * error feedback on the requantised gather's second rounding, layout B, the packet path, and bench.py.
+ * (Stochastic rounding on both halves of the wire, the second rounding included, has since come in
+ * ina_i8_sr.h, which this header includes as its last line; combined with error feedback it is still not here.)
  */
 #ifndef INA_I8_EF_H
 #define INA_I8_EF_H
@@ -69,5 +71,7 @@ int ina_block_scales_i8_ef(const void* const* xs, const float* const* resids, in
 /* (rotate +) quantise x + resid to bytes under given scales; resid becomes the (inverse-rotated) rounding error */
 int ina_quantize_ef_i8_wire(const void* x, int xtype, float* resid, const int8_t* kblk, int V, int8_t* q8, size_t n,
                             uint8_t* overflow_per_slot, const ina_sr_t* sr, ina_stream_t stream);
+
+#include "ina_i8_sr.h" /* stochastic rounding on the byte wire: the quantiser and the requantised gather */
 
 #endif /* INA_I8_EF_H */

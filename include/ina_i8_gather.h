@@ -52,7 +52,7 @@
  * Not here: stochastic rounding on either half of the wire, error feedback on the requantiser's rounding, a
  * 4-bit word, a 16-bit output of the decode, layout B, the packet path, a pipelined step (chunks > 1), and
  * bench.py.  Error feedback on the rank's own rounding -- the first half of the wire -- is in ina_i8_ef.h,
- * which this header includes as its last line.
+ * which this header includes as its last line; stochastic rounding on both halves has since come in ina_i8_sr.h.
  */
 #ifndef INA_I8_GATHER_H
 #define INA_I8_GATHER_H

@@ -58,7 +58,8 @@
  * Not here: the rotation combined with stochastic rounding, error feedback on the calls of this header, a
  * base, the sharded wires, the packet path, and V > 256.  A sharded wire that takes the rotation -- 8 bits a
  * value over an all-to-all -- is in ina_i8.h, which this header includes as its last line; the rotation
- * combined with error feedback, on that wire, is in ina_i8_ef.h at the end of the same chain.
+ * combined with error feedback, on that wire, is in ina_i8_ef.h further down the same chain, and the rotation
+ * combined with stochastic rounding, on that wire, in ina_i8_sr.h at its end.
  */
 #ifndef INA_ROT_H
 #define INA_ROT_H

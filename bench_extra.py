@@ -828,6 +828,50 @@ def run_i8_sr(dev):
     return rows
 
 
+def run_i4(dev):
+    """The 4-bit wire (include/ina_i4.h) at the ResNet-50 size (rounded down to a multiple of 256), cold caches,
+    median of 20, the set twice in this process (run 1 / run 2).  Bars, each the parent's own kernel timed twice in
+    the same process (its faster time plus the spread of the two): the rotated fp32 i4.quantize at V = 32 and 256
+    against i8.quantize, which reads the same and writes half a byte a value more; i4.sum_slices_requant and
+    i4.sum_slices at G = 8 and 64 against i8.sum_slices_requant and i8.sum_slices, which read twice the bytes a
+    slice.  Nothing is gated here; DESIGN 4.1t reads the rows."""
+    from ina_amd import i4, i8
+    rows = []
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(59)
+    n, seed = 25_557_032 // 256 * 256, 0x1234
+    x = torch.randn(n, device=dev, generator=gen) * 1e-2
+    parts8 = [torch.randint(-128, 128, (n,), dtype=torch.int8, device=dev, generator=gen) for _ in range(64)]
+    parts4 = [p[: n // 2].view(torch.uint8) for p in parts8]             # any bytes are nibbles
+    q8, q4 = torch.empty(n, dtype=torch.int8, device=dev), torch.empty(n // 2, dtype=torch.uint8, device=dev)
+    o16 = torch.empty(n, dtype=torch.int16, device=dev)
+
+    def row(run, name, nbytes, f_new, f_bar, bar_name):
+        ta, tn, tb = _time(f_bar), _time(f_new), _time(f_bar)
+        lo, spread = min(ta, tb), abs(ta - tb)
+        rows.append(_row(f"{name} [i4, run {run}]", tn, nbytes, bar=bar_name,
+                         bar_us=[round(ta * 1e6, 2), round(tb * 1e6, 2)], bar_spread_us=round(spread * 1e6, 2),
+                         over_bar=round(tn / lo, 3), bar_met=bool(tn <= lo + spread)))
+
+    for run in (1, 2):
+        for V in (32, 256):
+            nblk = n // V
+            ovf, sh = (torch.empty(nblk, dtype=torch.uint8, device=dev) for _ in range(2))
+            kb4 = i4.block_scales([x], V, rotate=seed, step=run)
+            kb8 = i8.block_scales([x], V, rotate=seed, step=run)
+            row(run, f"quantize V={V} rot f32", 4 * n + n // 2 + 2 * nblk,
+                lambda: i4.quantize(x, kb4, V, rotate=seed, step=run, out=q4, overflow=ovf),
+                lambda: i8.quantize(x, kb8, V, rotate=seed, step=run, out=q8, overflow=ovf), "i8.quantize")
+            for G in (8, 64):
+                row(run, f"sum_slices_requant G={G} V={V}", G * n // 2 + n + nblk,
+                    lambda: i4.sum_slices_requant(parts4[:G], V, out=q8, shift=sh),
+                    lambda: i8.sum_slices_requant(parts8[:G], V, out=q8, shift=sh), f"i8.sum_slices_requant G={G}")
+        for G in (8, 64):
+            row(run, f"sum_slices G={G}", G * n // 2 + 2 * n, lambda: i4.sum_slices(parts4[:G], out=o16),
+                lambda: i8.sum_slices(parts8[:G], out=o16), f"i8.sum_slices G={G}")
+    return rows
+
+
 def run_blk_x16(dev, dtype=torch.bfloat16):
     """Per-block scales for bf16 buckets (include/ina_x16_blk.h) at the ResNet-50 size, V = 256 and 32, cold
     caches, median of 20, the whole set twice in this process (run 1 / run 2).  Each 16-bit call beside (a) the
@@ -1532,6 +1576,7 @@ def run_extra(dev):
     rows += run_i8_gather(dev)
     rows += run_i8_ef(dev)
     rows += run_i8_sr(dev)
+    rows += run_i4(dev)
     rows += run_blk_x16(dev)
     rows += run_blk_packets(dev)
     rows += run_blk_switch(dev)

@@ -82,6 +82,7 @@ unsigned long long store_violations_i8();        // ina_i8.hip
 unsigned long long store_violations_i8g();       // ina_i8_gather.hip
 unsigned long long store_violations_i8ef();      // ina_i8_ef.hip
 unsigned long long store_violations_i8sr();      // ina_i8_sr.hip
+unsigned long long store_violations_i4();        // ina_i4.hip
 // ina_kernels.hip: ina_scale_for with `round` for its 1/2 -- the largest k in [-126, 127] with
 // W * (absmax * 2^k + round) <= 2^(bits-1) - 1; ina_scale_for's refusals
 int scale_for_round(float absmax, int W, int bits, double round, int* k_out);

@@ -3020,7 +3020,8 @@ extern "C" int ina_store_check_violations(unsigned long long* count) {
     *count = ina::store_violations_kernels() + ina::store_violations_shard() + ina::store_violations_switch() +
              ina::store_violations_x16() + ina::store_violations_blk() + ina::store_violations_sr() +
              ina::store_violations_reduce_sr() + ina::store_violations_rot() + ina::store_violations_i8() +
-             ina::store_violations_i8g() + ina::store_violations_i8ef() + ina::store_violations_i8sr();
+             ina::store_violations_i8g() + ina::store_violations_i8ef() + ina::store_violations_i8sr() +
+             ina::store_violations_i4();
     return INA_OK;
 }
 #endif

@@ -13,9 +13,10 @@ the sharded int16 wire's quantisers and decodes for any gradient dtype; ina_amd.
 with unbiased stochastic rounding (counter-based, stateless, any gradient dtype); ina_amd.blk_sr
 stochastic rounding together with block scales; ina_amd.rot a randomised Hadamard rotation of each block in
 front of the block-scaled quantise and reduce; ina_amd.i8 the 8-bit wire of the sharded step (rotated blocks as
-bytes, byte slices summed exactly to int16).
+bytes, byte slices summed exactly to int16); ina_amd.i4 the 4-bit wire of that step (rotated blocks as packed
+nibbles, nibble slices summed exactly or rounded back to bytes).
 """
-from . import blk, blk_sr, ef, i8, rot, sr, wire  # noqa: F401
+from . import blk, blk_sr, ef, i4, i8, rot, sr, wire  # noqa: F401
 from ._lib import (ACT_DROP, ACT_FWD_ACK, ACT_FWD_AGG, ACT_FWD_COLLISION, ACT_FWD_OTHER,  # noqa: F401
                    C128_BYTES, C128_VALUES, FLAG_ACK, FLAG_COLLISION, FLAG_OVERFLOW,
                    FLAG_RESEND, InaError, LIB_PATH, MAX_WORKERS, NGA_HDR_BYTES, NUM_REGISTER)

@@ -282,6 +282,15 @@ SIGNATURES_I8_SR = {
     "ina_quantize_sr_i8_wire": [_vp, _i, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), C.POINTER(SrParams), _vp],
     "ina_sum_i8_slices_requant_sr": [_vp, _i, _i, _vp, _vp, _sz, C.POINTER(SrParams), _vp],
 }
+# the 4-bit wire of the sharded step (include/ina_i4.h): ina_i8.h's block calls and the two slice sums with packed
+# nibbles (two values a byte) where those take bytes
+SIGNATURES_I4 = {
+    "ina_scale_for_i4": [C.c_float, C.POINTER(C.c_int)],
+    "ina_block_scales_i4": [_vp, _i, _i, _sz, _i, _vp, C.POINTER(SrParams), _vp],
+    "ina_quantize_i4_wire": [_vp, _i, _vp, _i, _vp, _sz, _vp, C.POINTER(SrParams), _vp],
+    "ina_sum_i4_slices": [_vp, _i, _vp, _sz, _vp],
+    "ina_sum_i4_slices_requant": [_vp, _i, _i, _vp, _vp, _sz, _vp],
+}
 _RESTYPE = {"ina_version": C.c_char_p, "ina_last_error_string": C.c_char_p,
             "ina_switch_scratch_bytes": C.c_size_t, "ina_host_reduce_scratch_bytes": C.c_size_t,
             "send_gradients": None}
@@ -301,7 +310,7 @@ def open_library(path: str) -> C.CDLL:
                        **SIGNATURES_EF, **SIGNATURES_SHARD_EF, **SIGNATURES_SHARD_X16, **SIGNATURES_SR,
                        **SIGNATURES_PKT_SR, **SIGNATURES_REDUCE_SR, **SIGNATURES_BLK_SR,
                        **SIGNATURES_ROT, **SIGNATURES_I8, **SIGNATURES_I8G, **SIGNATURES_I8_EF,
-                       **SIGNATURES_I8_SR}.items():
+                       **SIGNATURES_I8_SR, **SIGNATURES_I4}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -88,7 +88,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib, blk, blk_sr, ef, i8, ops, rot, sr
+from . import _lib, blk, blk_sr, ef, i4, i8, ops, rot, sr
 from . import wire as _wire          # (the aggregators' `wire` argument is the wire's name)
 
 
@@ -1126,5 +1126,117 @@ class ByteWireAggregator:
             rot.dequantize(self.s16_full, self._kbuf, V, self.seed, step=self._step, out=self.full)
         else:
             blk.dequantize(self.s16_full, self._kbuf, V, out=self.full)
+        self._step = (self._step + 1) & 0xFFFFFFFF
+        return self.full[: self.plan.n]
+
+
+class NibbleWireAggregator:
+    """Layout A on a 4-bit wire (include/ina_i4.h, ina_amd.i4): ByteWireAggregator's step with half the bytes in
+    the all-to-all.  A uniform 4-bit code under a shared per-block scale is still homomorphic, so the owner sums
+    the words as integers, exactly, and everything around the word is the byte wire's.  One step, in order:
+    i4.block_scales of the rank's bucket (i4.scale_for's rule, which does not depend on the number of ranks);
+    agree_block_scales (the MIN over ranks); i4.quantize into the uint8 [padded / 2] buffer `q4`, two values a
+    byte (its pad stays 0, the pad's scales 127); one all_to_all_single of it (host-staged under gloo); then
+    gather="i8" (default): i4.sum_slices_requant of the G received slices into the int8 `q8_shard` and the uint8
+      `shift_shard` (i8.sum_slices_requant's rule; the shift is 0 up to 18 ranks, where the sum of G nibbles is
+      a byte already, and at most 3), all_gather_shards of both (into `q8_full` and `gather_shift`),
+      i8.dequantize_gather on every rank;
+    gather="i16": i4.sum_slices into the int16 `s16_shard`, one all_gather_shards into `s16_full`, rot.dequantize
+      (rotate=True) or blk.dequantize.
+    On one rank the collectives are identities and the same kernels run.  rotate=True (default) rotates every
+    block of V values under the key `seed` at step = `step`, sub = 0, e0 = 0 -- one stream for all ranks; `step`
+    starts at 0, advances by one per call and may be set.  Buckets are float32, bfloat16 or float16; the output
+    is float32.  `kblk` holds the agreed scales of the last call, `local_overflow` this rank's flags (1 where a
+    value of the block clamped at +-7 under the agreed scale or was NaN; rank-local, never sent) and
+    `gather_shift` the last call's shifts under gather="i8".  `wire_bytes`, `gather_bytes` and `scale_bytes` are
+    what one step brings to each rank over the links: (G-1) x shard / 2; (G-1) x shard x (1 + 1/V), or x 2 under
+    "i16"; one byte per block -- 0.5 + 1 bytes a value where the byte wire moves 1 + 1 or 1 + 2 (arithmetic on
+    bytes, not a timing of any link).  Shards are aligned to the lcm of `align`, V and 128, so every nibble slice
+    is 64-byte aligned and starts where a rotated call may start.  Round to nearest only; no error feedback, no
+    chunks, no layout B."""
+
+    def __init__(self, n: int, V: int = 256, group=None, device=None, align: int = 1024, rotate: bool = True,
+                 seed: int = 0, gather: str = "i8"):
+        self.seed = _check_seed(seed)
+        if gather not in ("i16", "i8"):
+            raise ValueError(f"gather must be 'i16' or 'i8', got {gather!r}")
+        self.gather = gather
+        V = int(V)
+        if V < 8 or V > 256 or V & (V - 1):
+            raise ValueError(f"V must be a power of two in [8, 256], got {V}")
+        self.rotate = bool(rotate)
+        if self.rotate and n % V:
+            raise ValueError(f"rotate=True needs n to be a multiple of V: {n} values in blocks of {V}")
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        if self.world > _lib.MAX_WORKERS:
+            raise ValueError(f"the nibble wire sums at most {_lib.MAX_WORKERS} ranks, got {self.world}")
+        self.plan = ShardPlan(n, self.world, math.lcm(align, V, 128))
+        self.V, self.group, self._step = V, group, 0
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        tot, shard, nblk = self.plan.padded, self.plan.shard, self.plan.padded // V
+        self.q4 = torch.zeros(tot // 2, dtype=torch.uint8, device=dev)
+        self._kbuf = torch.full((nblk,), 127, dtype=torch.int8, device=dev)
+        self._obuf = torch.zeros(nblk, dtype=torch.uint8, device=dev)
+        self._recv = torch.empty(tot // 2, dtype=torch.uint8, device=dev) if self.world > 1 else None
+        if gather == "i16":
+            self.s16_shard = torch.empty(shard, dtype=torch.int16, device=dev)
+            self.s16_full = torch.empty(tot, dtype=torch.int16, device=dev)
+        else:
+            self.q8_shard = torch.empty(shard, dtype=torch.int8, device=dev)
+            self.shift_shard = torch.empty(shard // V, dtype=torch.uint8, device=dev)
+            self.q8_full = torch.empty(tot, dtype=torch.int8, device=dev)
+            self._sbuf = torch.zeros(nblk, dtype=torch.uint8, device=dev)
+        self.full = torch.empty(tot, dtype=torch.float32, device=dev)
+        self._stage = None           # rotate=False with n % V: the bucket padded with zeros to whole blocks
+
+    step = ShardedAggregator.step
+    kblk = ByteWireAggregator.kblk
+    local_overflow = ByteWireAggregator.local_overflow
+    gather_shift = ByteWireAggregator.gather_shift
+    scale_bytes = ByteWireAggregator.scale_bytes
+    gather_bytes = ByteWireAggregator.gather_bytes
+    _bucket = ByteWireAggregator._bucket
+
+    @property
+    def wire_bytes(self) -> int:
+        """Bytes the all-to-all brings to each rank: half a byte per value of the other ranks' slices."""
+        return (self.world - 1) * self.plan.shard // 2
+
+    def _exchange(self):
+        """Slice j of `q4` to rank j; the G slices this rank now holds."""
+        if self.world == 1:
+            return [self.q4]
+        if self.q4.is_cuda and _host_staged(self.group):
+            h = torch.empty(self.plan.padded // 2, dtype=torch.uint8)
+            dist.all_to_all_single(h, self.q4.cpu(), group=self.group)
+            self._recv.copy_(h)
+        else:
+            dist.all_to_all_single(self._recv, self.q4, group=self.group)
+        half = self.plan.shard // 2
+        return [self._recv[r * half:(r + 1) * half] for r in range(self.world)]
+
+    def __call__(self, grad: torch.Tensor) -> torch.Tensor:
+        """[n] local bucket -> [n] float32 decoded sum over all ranks."""
+        V = self.V
+        x = self._bucket(grad)
+        nb = x.numel() // V
+        key = dict(rotate=self.seed if self.rotate else None, step=self._step)
+        kb = self._kbuf[:nb]
+        i4.block_scales([x], V, out=kb, **key)
+        agree_block_scales(kb, self.group)
+        i4.quantize(x, kb, V, out=self.q4[: x.numel() // 2], overflow=self._obuf[:nb], **key)
+        if self.gather == "i8":
+            i4.sum_slices_requant(self._exchange(), V, out=self.q8_shard, shift=self.shift_shard)
+            all_gather_shards(self.q8_shard, self.plan, self.group, out=self.q8_full)
+            all_gather_shards(self.shift_shard, self.plan, self.group, out=self._sbuf)
+            i8.dequantize_gather(self.q8_full, self._sbuf, self._kbuf, V, out=self.full, **key)
+        else:
+            i4.sum_slices(self._exchange(), out=self.s16_shard)
+            all_gather_shards(self.s16_shard, self.plan, self.group, out=self.s16_full)
+            if self.rotate:
+                rot.dequantize(self.s16_full, self._kbuf, V, self.seed, step=self._step, out=self.full)
+            else:
+                blk.dequantize(self.s16_full, self._kbuf, V, out=self.full)
         self._step = (self._step + 1) & 0xFFFFFFFF
         return self.full[: self.plan.n]

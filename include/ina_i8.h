@@ -62,7 +62,7 @@
  * this header includes as its last line; error feedback on this wire -- the rounding error carried back
  * through the inverse rotation into a rank-local residual, in the quantiser's launch -- is in ina_i8_ef.h,
  * which that header includes as its last line; stochastic rounding on this wire -- the byte quantiser and the
- * requantised gather -- is in ina_i8_sr.h at the end of the same chain.
+ * requantised gather -- is in ina_i8_sr.h further down the same chain, and a 4-bit wire word in ina_i4.h at its end.
  */
 #ifndef INA_I8_H
 #define INA_I8_H

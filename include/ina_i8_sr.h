@@ -74,7 +74,8 @@
  *
  * Not here: stochastic rounding combined with error feedback, a 4-bit word, fewer Philox rounds or a shorter u
  * on the first half, scales computed in the quantiser's launch (an AUTO mode), layout B, the packet path, a
- * pipelined step (chunks > 1), and bench.py.
+ * pipelined step (chunks > 1), and bench.py.  The 4-bit word -- round to nearest, packed nibbles and their slice
+ * sums -- has since come in ina_i4.h, which this header includes as its last line.
  */
 #ifndef INA_I8_SR_H
 #define INA_I8_SR_H
@@ -94,5 +95,7 @@ int ina_quantize_sr_i8_wire(const void* x, int xtype, const int8_t* kblk, int V,
 /* the sum of G byte slices, each block rounded stochastically to bytes under shift[block] */
 int ina_sum_i8_slices_requant_sr(const int8_t* const* slices, int G, int V, int8_t* q8, uint8_t* shift, size_t n,
                                  const ina_sr_t* rnd, ina_stream_t stream);
+
+#include "ina_i4.h" /* a 4-bit wire word: packed nibbles, their exact and their requantising slice sums */
 
 #endif /* INA_I8_SR_H */

@@ -14,10 +14,10 @@ The stream-order window.  The side stream first runs torch.cuda._sleep for DELAY
 the fresh inputs, the call, the copy-out; an event recorded after the sleep must still be pending when
 the call has returned, or the case is void and fails.  Measured on an MI355X (the figure every case
 prints: the host clock around the copies and the call of a warmed row): 0.022-0.066 ms for the rows of one
-to three buffers, 0.132-0.145 ms for the rows of 17 buckets (18 copies), the slowest absmax_multi_bf16_w17
-at 0.145 ms = HOST_ENQUEUE_MS_MEASURED.  Ten times that is 1.45 ms; DELAY_MS = 5 ms is that rounded up past
-one 4 ms scheduler tick of the host, so that a thread put off once between two enqueues does not void the
-case.
+to three buffers, up to 0.145 ms for the rows of 17 buckets or slices (18 copies; 0.086-0.106 ms in the run
+that first held the rows of the newer wires), and the slowest i4_sum_requant_w33 (34 copies) at 0.149 ms =
+HOST_ENQUEUE_MS_MEASURED.  Ten times that is 1.49 ms; DELAY_MS = 5 ms is that rounded up past one 4 ms
+scheduler tick of the host, so that a thread put off once between two enqueues does not void the case.
 """
 import contextlib
 
@@ -28,7 +28,10 @@ from oracle import oracle as orc
 from tests import _blk_ref as bref
 from tests import _blk_sr_ref as bsref
 from tests import _ef_ref as eref
+from tests import _i4_ref as i4ref
+from tests import _i8_ef_ref as i8eref
 from tests import _i8_ref as i8ref
+from tests import _i8_sr_ref as i8sref
 from tests import _rot_ref as rref
 from tests import _shard_blk_ref as shref
 from tests import _sr_ref as sref
@@ -42,13 +45,13 @@ K = 8                                           # the global scale: int16 satura
 SEED, STEP = 0x5EED1234ABCD, 9
 SENTINEL = 0xA5
 GUARD = 64                                      # bytes in front of and behind every view
-HOST_ENQUEUE_MS_MEASURED = 0.145                # slowest row (W = 17 buckets: 18 copies + the call)
+HOST_ENQUEUE_MS_MEASURED = 0.149                # slowest row (33 nibble slices: 34 copies + the call)
 DELAY_MS = 5.0
 
 
 def mods():
-    from ina_amd import blk_sr, ef, i8, ops, rot, sr
-    return {"o": ops, "ef": ef, "i8": i8, "rot": rot, "sr": sr, "bsr": blk_sr}
+    from ina_amd import blk_sr, ef, i4, i8, ops, rot, sr
+    return {"o": ops, "ef": ef, "i4": i4, "i8": i8, "rot": rot, "sr": sr, "bsr": blk_sr}
 
 
 # ---- inputs --------------------------------------------------------------------------------------
@@ -87,13 +90,16 @@ class Row:
     call(m, t, step) with t the device tensors by name; want(h, step) -> {name: numpy} from the widened
     host inputs h.  mis: names whose view starts off a 16-byte boundary; state: inputs the call updates
     in place (they carry over from replay to replay and are compared); flags / peak: the output that
-    must go down in phase 2; keyed: the call draws random numbers under (SEED, step)."""
+    must go down in phase 2; keyed: the call draws random numbers under (SEED, step).  odd: names whose view
+    starts one byte past a 16-byte boundary (the shift bytes of a requantiser); shifts: the output of block shifts
+    that must hold a non-zero in phase 1 and none in phase 2, as flags must; key_phase: the phase whose inputs the
+    key test replays (a stochastic requantiser draws nothing where every shift is 0, so it takes phase 1)."""
 
     def __init__(self, name, protos, ins, outs, call, want, mis=(), state=(), flags=None, peak=None, cap=False,
-                 keyed=False, src=None):
+                 keyed=False, src=None, odd=(), shifts=None, key_phase=2):
         self.name, self.protos, self.ins, self.outs, self.call, self.want = name, tuple(protos), ins, outs, call, want
         self.mis, self.state, self.flags, self.peak, self.cap, self.keyed = set(mis), tuple(state), flags, peak, cap, keyed
-        self.src = src
+        self.src, self.odd, self.shifts, self.key_phase = src, set(odd), shifts, key_phase
 
     def __repr__(self):
         return self.name
@@ -116,6 +122,58 @@ def _ints16(rng, phase, W, n):
     if phase == 3:
         a[:, 7 * V:8 * V] = 30000
     return [torch.from_numpy(a[w]) for w in range(W)]
+
+
+SAT = {1: 3, 3: 7}                              # the block grads() saturates in phases 1 and 3
+N_I4 = N_BLK + 24                               # the exact nibble sum: whole chunks of 32 and a ragged lane of 3 dwords
+RND = dict(sub=65, e0=16 * 1_000_003)           # the rounding stream of the stochastic requantiser
+
+
+def _ef_scales(phase):
+    """Given scales of the byte wire's error-feedback row.  A block that clamps leaves the clipped part in the
+    residual, thousands here, and the next replay adds it in front of the rotation: so SAT's blocks sit at k = -8
+    (a quantum of 256, nothing of theirs clamps: |r| <= 32 * 5000 / 8 < 127 * 256) except in the phase that is to
+    clamp them, k = 4.  Phase 2 then carries phase 1's residual without a flag."""
+    kb = scales(N_BLK, 4).numpy().copy()
+    kb[list(SAT.values())] = -8
+    if phase in SAT:
+        kb[SAT[phase]] = 4
+    return torch.from_numpy(kb)
+
+
+def _spread(xs):
+    """Block b of every bucket times 2^(b / NBLK): the blocks' maxima cover an octave, so some sit at a scale's
+    threshold and cross it with the rotation's signs -- the scales of STEP and STEP + 1 differ."""
+    f = torch.from_numpy(np.repeat(np.exp2(np.arange(NBLK) / NBLK), V).astype(F32))
+    return [(x.float() * f).to(x.dtype) for x in xs]
+
+
+def _bytes(rng, phase, W, n):
+    """W byte slices.  Phase 1: the full range (17 slices: shifts up to 5); phase 2: within +-7, every |sum| at
+    most 7 W <= 127 up to W = 18, so every shift is 0; phase 3: the full range in every other block."""
+    big = {1: np.ones(n // V, bool), 2: np.zeros(n // V, bool), 3: np.arange(n // V) % 2 == 1}[phase]
+    amp = np.repeat(np.where(big, 127, 7), V)
+    return [torch.from_numpy(a) for a in rng.integers(-amp, amp + 1, (W, n)).astype(np.int8)]
+
+
+def _nibbles(rng, phase, W, n, amp, plants):
+    """W slices of packed nibbles within +-amp; plants: {phase: {block: nibble}}, the block's value 5 is that nibble
+    in every slice (|sum| = W * |nibble|) ."""
+    q = rng.integers(-amp, amp + 1, (W, n))
+    for b, v in plants.get(phase, {}).items():
+        q[:, b * V + 5] = v
+    return [torch.from_numpy(i4ref.pack(r)) for r in q]
+
+
+# 17 slices: |S| <= 7 * 17 = 119, every shift is 0 whatever is planted.  33 slices within +-3 stay within 99; a
+# column of 7 is 231 (shift 1), of -8 is -264 (rne(264 / 2) = 132: shift 2)
+PLANTS17 = {1: {3: 7, 4: -7}, 3: {7: -7}}
+PLANTS33 = {1: {3: 7, 4: -8, 36: -8}, 3: {0: -8, 7: 7}}
+
+
+def _shifted(q8, sh):
+    """The int16 values the requantised gather decodes: q8 << min(shift, 7)."""
+    return q8.astype(np.int16) << np.repeat(np.minimum(sh, 7), V).astype(np.int16)
 
 
 def rows():
@@ -254,6 +312,72 @@ def rows():
         lambda g, p: {"x": grads(g, p, 1, N_RAG)[0], "kb": kb_rag}, {"q": (I32, N_RAG)},
         lambda m, t, s: m["bsr"].quantize(t["x"], t["kb"], V, SEED, step=s, out=t["q"]),
         lambda h, s: {"q": bsref.quantize(h["x"], h["kb"], V, SEED, s)}, keyed=True, src="ina_blk.hip")
+
+    # -- the byte wire's requantised gather, error feedback and stochastic rounding; the nibble wire --------------
+    ROT = dict(rotate=SEED)
+    add("i8_sum_requant_w17", ["ina_sum_i8_slices_requant"],
+        lambda g, p: {"p": _bytes(g, p, 17, N_BLK)}, {"q": (I8, N_BLK), "shift": (U8, NBLK)},
+        lambda m, t, s: m["i8"].sum_slices_requant(t["p"], V, out=t["q"], shift=t["shift"]),
+        lambda h, s: dict(zip(("q", "shift"), i8ref.requant(h["p"], V))),
+        odd=["shift"], shifts="shift", cap=True, src="ina_i8_gather.hip")
+    add("i8_dequantize_gather", ["ina_dequantize_i8_gather"],
+        lambda g, p: {"q8": torch.from_numpy(g.integers(-127, 128, N_BLK).astype(np.int8)),
+                      "sh": torch.from_numpy(((np.arange(NBLK) + p) % 8).astype(np.uint8)), "kb": kb_blk},
+        {"y": (FP, N_BLK)},
+        lambda m, t, s: m["i8"].dequantize_gather(t["q8"], t["sh"], t["kb"], V, step=s, out=t["y"], **ROT),
+        lambda h, s: {"y": i8ref.dequantize(_shifted(h["q8"], h["sh"]), h["kb"], V, step=s, **ROT)},
+        odd=["sh"], keyed=True, src="ina_i8_gather.hip")
+    add("i8_ef_block_scales_w3", ["ina_block_scales_i8_ef"],
+        lambda g, p: {"x": _spread(grads(g, p, 3, N_BLK)), "r": grads(g, 2, 3, N_BLK)}, {"kb": (I8, NBLK)},
+        lambda m, t, s: m["i8"].block_scales_ef(t["x"], t["r"], V, step=s, out=t["kb"], **ROT),
+        lambda h, s: {"kb": i8eref.block_scales(h["x"], h["r"], V, step=s, **ROT)},
+        odd=["kb"], keyed=True, src="ina_i8_ef.hip")
+    add("i8_ef_quantize", ["ina_quantize_ef_i8_wire"],
+        lambda g, p: {"x": grads(g, p, 1, N_BLK)[0], "r": torch.zeros(N_BLK), "kb": _ef_scales(p)},
+        {"q": (I8, N_BLK), "ovf": (U8, NBLK)},
+        lambda m, t, s: m["i8"].quantize_ef(t["x"], t["r"], t["kb"], V, step=s, out=t["q"], overflow=t["ovf"], **ROT),
+        lambda h, s: dict(zip(("q", "ovf", "r"), i8eref.quantize(h["x"], h["r"], h["kb"], V, step=s, **ROT))),
+        odd=["ovf"], state=["r"], flags="ovf", cap=True, keyed=True, src="ina_i8_ef.hip")
+    add("i8_sr_block_scales_w3", ["ina_block_scales_i8_sr"],
+        lambda g, p: {"x": _spread(grads(g, p, 3, N_BLK))}, {"kb": (I8, NBLK)},
+        lambda m, t, s: m["i8"].block_scales_sr(t["x"], V, step=s, sub=1, out=t["kb"], **ROT),
+        lambda h, s: {"kb": i8sref.block_scales(h["x"], V, step=s, sub=1, **ROT)},
+        odd=["kb"], keyed=True, src="ina_i8_sr.hip")
+    add("i8_sr_quantize", ["ina_quantize_sr_i8_wire"],                   # rounding stream sub 3, rotation sub 1
+        lambda g, p: {"x": grads(g, p, 1, N_BLK)[0], "kb": scales(N_BLK, 4)}, {"q": (I8, N_BLK), "ovf": (U8, NBLK)},
+        lambda m, t, s: m["i8"].quantize_sr(t["x"], t["kb"], V, SEED ^ 5, step=s, sub=3, rot_sub=1, out=t["q"],
+                                            overflow=t["ovf"], **ROT),
+        lambda h, s: dict(zip(("q", "ovf"), i8sref.quantize(h["x"], h["kb"], V, SEED ^ 5, step=s, sub=3, rot_sub=1, **ROT))),
+        odd=["ovf"], flags="ovf", cap=True, keyed=True, src="ina_i8_sr.hip")
+    add("i8_sum_requant_sr_w17", ["ina_sum_i8_slices_requant_sr"],
+        lambda g, p: {"p": _bytes(g, p, 17, N_BLK)}, {"q": (I8, N_BLK), "shift": (U8, NBLK)},
+        lambda m, t, s: m["i8"].sum_slices_requant_sr(t["p"], V, SEED, step=s, out=t["q"], shift=t["shift"], **RND),
+        lambda h, s: dict(zip(("q", "shift"), i8sref.requant(h["p"], V, SEED, step=s, **RND))),
+        odd=["shift"], shifts="shift", keyed=True, key_phase=1, src="ina_i8_sr.hip")
+    add("i4_block_scales_w3", ["ina_block_scales_i4"],
+        lambda g, p: {"x": _spread(grads(g, p, 3, N_BLK, torch.bfloat16))}, {"kb": (I8, NBLK)},
+        lambda m, t, s: m["i4"].block_scales(t["x"], V, step=s, out=t["kb"], **ROT),
+        lambda h, s: {"kb": i4ref.block_scales(h["x"], V, step=s, **ROT)},
+        odd=["kb"], keyed=True, src="ina_i4.hip")
+    add("i4_quantize", ["ina_quantize_i4_wire"],                         # nibbles clamp at 7: scales 0..2 for |r| < 1.7
+        lambda g, p: {"x": grads(g, p, 1, N_BLK)[0], "kb": scales(N_BLK, 0)}, {"q": (U8, N_BLK // 2), "ovf": (U8, NBLK)},
+        lambda m, t, s: m["i4"].quantize(t["x"], t["kb"], V, step=s, out=t["q"], overflow=t["ovf"], **ROT),
+        lambda h, s: dict(zip(("q", "ovf"), i4ref.quantize(h["x"], h["kb"], V, step=s, **ROT))),
+        odd=["ovf"], flags="ovf", cap=True, keyed=True, src="ina_i4.hip")
+    add("i4_sum_slices_w17", ["ina_sum_i4_slices"],                      # a batch of 16 and one; -8 G = -136
+        lambda g, p: {"p": _nibbles(g, p, 17, N_I4, 7, {1: {3: -8}, 2: {4: -8}, 3: {7: 7}})}, {"out": (I16, N_I4)},
+        lambda m, t, s: m["i4"].sum_slices(t["p"], out=t["out"]),
+        lambda h, s: {"out": i4ref.sum_slices(h["p"])}, src="ina_i4.hip")
+    add("i4_sum_requant_w17", ["ina_sum_i4_slices_requant"],
+        lambda g, p: {"p": _nibbles(g, p, 17, N_BLK, 7, PLANTS17)}, {"q": (I8, N_BLK), "shift": (U8, NBLK)},
+        lambda m, t, s: m["i4"].sum_slices_requant(t["p"], V, out=t["q"], shift=t["shift"]),
+        lambda h, s: dict(zip(("q", "shift"), i4ref.requant(h["p"], V))),
+        odd=["shift"], cap=True, src="ina_i4.hip")
+    add("i4_sum_requant_w33", ["ina_sum_i4_slices_requant"],
+        lambda g, p: {"p": _nibbles(g, p, 33, N_BLK, 3, PLANTS33)}, {"q": (I8, N_BLK), "shift": (U8, NBLK)},
+        lambda m, t, s: m["i4"].sum_slices_requant(t["p"], V, out=t["q"], shift=t["shift"]),
+        lambda h, s: dict(zip(("q", "shift"), i4ref.requant(h["p"], V))),
+        odd=["shift"], shifts="shift", src="ina_i4.hip")
     return R
 
 
@@ -265,7 +389,12 @@ CLEARING = {"ina_quantize_f32_i16_sat", "ina_sum_reduce_i16_sat", "ina_quantize_
             "ina_i16_wire_finish", "ina_i16_wire_finish_blk"}
 # sources that must have two single-launch rows; those with an entry point over W buckets must have one of them
 SINGLE = {"ina_blk.hip": True, "ina_ef.hip": True, "ina_rot.hip": True, "ina_i8.hip": True, "ina_x16.hip": True,
-          "ina_shard.hip": False}
+          "ina_shard.hip": False, "ina_i8_gather.hip": True, "ina_i8_ef.hip": True, "ina_i8_sr.hip": True,
+          "ina_i4.hip": True}
+# the device entry points of the four newer wire sources: every one must appear in some row's protos
+WIRES = {"ina_sum_i8_slices_requant", "ina_dequantize_i8_gather", "ina_block_scales_i8_ef", "ina_quantize_ef_i8_wire",
+         "ina_block_scales_i8_sr", "ina_quantize_sr_i8_wire", "ina_sum_i8_slices_requant_sr", "ina_block_scales_i4",
+         "ina_quantize_i4_wire", "ina_sum_i4_slices", "ina_sum_i4_slices_requant"}
 
 
 # ---- device side ---------------------------------------------------------------------------------
@@ -275,19 +404,21 @@ class Stage:
     def __init__(self, row, like):
         self.row, self.bufs, self.t = row, {}, {}
         for name, h in like.items():
-            self.t[name] = ([self._view(f"{name}{w}", x.dtype, x.numel(), name in row.mis) for w, x in enumerate(h)]
-                            if isinstance(h, list) else self._view(name, h.dtype, h.numel(), name in row.mis))
+            self.t[name] = ([self._view(f"{name}{w}", x.dtype, x.numel(), name) for w, x in enumerate(h)]
+                            if isinstance(h, list) else self._view(name, h.dtype, h.numel(), name))
         for name, (dt, numel) in row.outs.items():
-            self.t[name] = self._view(name, dt, numel, name in row.mis)
+            self.t[name] = self._view(name, dt, numel, name)
 
-    def _view(self, key, dtype, numel, mis):
+    def _view(self, key, dtype, numel, name):
         size = torch.empty(0, dtype=dtype).element_size()
-        off = GUARD + (size if mis else 0)                      # 2 or 4 bytes past a 16-byte boundary
+        skew = size if name in self.row.mis else 1 if name in self.row.odd else 0   # 2 or 4 bytes past a 16-byte
+        assert size == 1 or name not in self.row.odd                               # boundary; `odd`: one byte past
+        off = GUARD + skew
         nbytes = numel * size
         buf = torch.full((off + nbytes + GUARD,), SENTINEL, dtype=torch.uint8, device=DEV)
         self.bufs[key] = (buf, off, nbytes)
         v = buf[off:off + nbytes].view(dtype)
-        assert (v.data_ptr() % 16 != 0) == bool(mis)
+        assert v.data_ptr() % 16 == skew
         return v
 
     def load(self, hosts, skip=(), non_blocking=False):

@@ -42,6 +42,14 @@ def sum_slices(parts) -> np.ndarray:
     return np.sum(np.stack(parts).astype(np.int32), axis=0).astype(np.int16)
 
 
+def requant(parts, V):
+    """(q8, shift) of include/ina_i8_gather.h from exact sums: np.rint is round half to even, and S / 2^sh is exact."""
+    S = np.asarray(parts).astype(np.int64).sum(0)
+    A = np.abs(S).reshape(-1, V).max(1)
+    sh = (np.rint(A[:, None] / 2.0 ** np.arange(8)) > 127).sum(1)      # rne is monotone in sh: the first that fits
+    return np.rint(S / 2.0 ** np.repeat(sh, V)).astype(np.int8), sh.astype(np.uint8)
+
+
 def dequantize(s16, kblk, V, rotate=None, dtype=F32, **key) -> np.ndarray:
     """The existing decodes on the int16 sums."""
     if rotate is None:

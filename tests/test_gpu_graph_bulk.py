@@ -38,7 +38,10 @@ def test_table_covers_the_entry_points():
     """The coverage rule, over the `_lib` prototype names: every entry point that clears in front of its
     kernel has a row whose output must go down in phase 2 (or, the checksum, must not accumulate); two
     single-launch rows per source, one over W buckets where the source has such an entry point; W = 3 and
-    a run-time W of 17 both occur; one grid-cap-1 row per family."""
+    a run-time W of 17 both occur; one grid-cap-1 row per family; every device entry point of the four newer wire
+    sources (G.WIRES) has a row.  Then, from the yardsticks alone, that the phases do what the GPU tests rely on:
+    flags and shifts go down in phase 2 -- with the carried state too -- and a keyed row's first output differs
+    between STEP and STEP + 1 on the very inputs test_replay_repeats_the_captured_key draws."""
     from ina_amd import _lib
     sigs = {}
     for name in dir(_lib):
@@ -60,7 +63,13 @@ def test_table_covers_the_entry_points():
     assert any("_w3" in r.name for r in ROWS) and any("_w17" in r.name for r in ROWS)
     capped_srcs = {r.src for r in ROWS if r.cap}
     assert capped_srcs >= {"ina_kernels.hip", "ina_x16.hip", "ina_sr.hip", "ina_reduce_sr.hip", "ina_shard.hip",
-                           "ina_blk.hip", "ina_ef.hip", "ina_rot.hip", "ina_i8.hip"}, capped_srcs
+                           "ina_blk.hip", "ina_ef.hip", "ina_rot.hip", "ina_i8.hip", "ina_i8_gather.hip",
+                           "ina_i8_ef.hip", "ina_i8_sr.hip", "ina_i4.hip"}, capped_srcs
+    assert G.WIRES <= named, sorted(G.WIRES - named)
+    assert all(sigs[p][-1] is sigs["ina_sum_i8_slices"][-1] for p in G.WIRES)      # each ends in the stream argument
+    for p in G.WIRES - {"ina_dequantize_i8_gather"} - {q for q in G.WIRES if "block_scales" in q}:
+        rs = [r for r in ROWS if p in r.protos]                   # a quantiser clears flags, a requantiser writes shifts
+        assert any(r.flags or r.shifts or p == "ina_sum_i4_slices" for r in rs), p
     rng = np.random.default_rng(1)
     for r in ROWS:                                    # the phases do what the replays rely on
         w = [r.want(wide(r.ins(rng, p)), STEP) for p in (1, 2, 3)]
@@ -69,6 +78,24 @@ def test_table_covers_the_entry_points():
             assert not np.array_equal(w[0][r.flags], w[2][r.flags]), r.name
         if r.peak:
             assert w[0][r.peak][0] > 100 * w[1][r.peak][0] > 0, r.name
+        if r.shifts:                                  # a stale shift byte of phase 1 would show in phase 2
+            assert r.shifts in r.odd and w[0][r.shifts].max() >= 1 and not w[1][r.shifts].any() and w[2][r.shifts].any(), r.name
+            assert not np.array_equal(w[0][r.shifts], w[2][r.shifts]), r.name
+        if r.name == "i4_sum_requant_w33":
+            assert {1, 2} <= set(w[0][r.shifts].tolist()), w[0][r.shifts]
+        if r.state and r.flags:                       # test_replay's chain: the state the yardstick leaves goes on
+            g = np.random.default_rng(200 + len(r.name))
+            h, seen = None, []
+            for i, ph in enumerate([r.ins(g, p) for p in (1, 2, 3)]):
+                h = {**wide(ph), **({n: want[n] for n in r.state} if i else {})}
+                want = r.want(h, STEP)
+                seen.append(want[r.flags].copy())
+            assert seen[0].any() and not seen[1].any() and seen[2].any() and not np.array_equal(seen[0], seen[2]), r.name
+            assert all(np.isfinite(want[n]).all() and want[n].any() for n in r.state), r.name
+        if r.keyed:
+            hosts = wide(r.ins(np.random.default_rng(300 + len(r.name)), r.key_phase))
+            first = next(iter(r.outs))
+            assert not np.array_equal(r.want(hosts, STEP)[first], r.want(hosts, STEP + 1)[first]), r.name
 
 
 def _read(st):
@@ -146,7 +173,7 @@ def test_replay_repeats_the_captured_key(name, cycles_per_ms):
     capture, whose replays are the yardstick's at step + 1 and differ from the first graph's."""
     row = BY_NAME[name]
     rng = np.random.default_rng(300 + len(name))
-    hosts = row.ins(rng, 2)
+    hosts = row.ins(rng, row.key_phase)
     st = Stage(row, hosts)
     s = torch.cuda.Stream(DEV)
     warm(row, st, hosts, s)
@@ -154,6 +181,7 @@ def test_replay_repeats_the_captured_key(name, cycles_per_ms):
     for step in (STEP, STEP + 1):
         g = _capture(row, st, s, step)
         for rep in range(2):
+            st.load(hosts)                            # a state the call updates starts every replay from the same values
             st.sentinel_outputs()
             torch.cuda.synchronize()
             g.replay()

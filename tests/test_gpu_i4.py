@@ -16,7 +16,7 @@ from tests.test_gpu_dist import _free_port
 from tests.test_gpu_rot import DEV, DTYPES, E0, F32, SEED, STEP, SUB, _need_gpu, dev, grid_cap, host, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-GS = (1, 2, 3, 8, 16, 17, 18, 33, 64)                  # the compile-time counts and either side of a batch of 16
+GS = (1, 2, 3, 4, 8, 16, 17, 18, 33, 64)                  # the compile-time counts and either side of a batch of 16
 
 
 def check_replay(ts, xs, V, rotate, e0=0, caps=(None,)):

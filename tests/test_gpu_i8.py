@@ -78,7 +78,7 @@ FILLS = {"random": lambda rng, G, n: rng.integers(-128, 128, (G, n)), "min": lam
 
 
 @pytest.mark.parametrize("n", (1, 15, 16, 17, 4099, 70_001))      # tails alone, whole chunks, both; a capped grid
-@pytest.mark.parametrize("G", (1, 2, 3, 8, 17, 64))               # compile-time and run-time slice counts
+@pytest.mark.parametrize("G", (1, 2, 3, 4, 8, 16, 17, 64))       # compile-time and run-time slice counts
 def test_slice_sum_is_exact(G, n):
     """Whole slices of -128 (the bias at its limit), of 127 (the fields at their largest) and of alternating
     +-127 (neighbouring fields of opposite sign), and random bytes; nothing is written past n."""

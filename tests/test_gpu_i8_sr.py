@@ -85,7 +85,7 @@ def slices(G, V, nblk):
 
 @pytest.mark.parametrize("nblk", (37, 1061))           # n mod 16 = 8 at V = 8; several passes of a capped grid
 @pytest.mark.parametrize("V", (8, 16, 256))
-@pytest.mark.parametrize("G", (1, 2, 3, 8, 17, 64))    # compile-time and run-time slice counts
+@pytest.mark.parametrize("G", (1, 2, 3, 4, 8, 16, 17, 64))    # compile-time and run-time slice counts
 def test_requantiser_replay(G, V, nblk):
     from ina_amd import i8
     parts, n = slices(G, V, nblk), nblk * V
